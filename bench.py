@@ -2,6 +2,8 @@
 """Benchmark of the BBBP multi-modal hot path on N GPUs of one node, one process per GPU.
 
     python bench.py --gpus 1 --steps 20 --warmup 3                      # BASELINE config 3, the headline (one process, no child)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full               # + roofline, CPU baseline and the per-kernel passes
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
     python bench.py --gpus N --steps K --warmup W                       # N > 1 typed as is: the parent starts N ranks itself (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--config C] [--scaling weak|strong]
@@ -24,7 +26,11 @@ os.exec*).  With WORLD_SIZE set (the driver's torch.distributed.run form) the pr
 --exact-batch runs configs 3 / 4 in exact-global-batch mode on the fused engine (the configuration's GLOBAL batch sharded over the ranks, K|V
   all-gather + dK|dV reduce-scatter per encoder layer, BatchNorm on global statistics): an N-rank step equals the single-GPU step.
 
-Prints ONE JSON line on rank 0 (contract in the build prompt) with two extra objects:
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64; a fixed, seeded sample of an output
+  larger than DUMP_CAP elements), so that two builds can be compared output for output on identical inputs.
+
+Prints ONE JSON line on rank 0: the headline (metric, value, unit, ms_per_step, ...).  A plain run does nothing beyond set-up,
+warm-up, the timed steps and --dump-outputs.  With --full the line carries two extra objects, each measured by passes of its own:
   roofline     -- the configuration's dominant kernel, timed with HIP events on its own stream inside the timed region;
                   achieved = algorithmic FLOPs per launch / mean launch time; peak = the ceiling of the pipe the kernel issues to:
                   416.7 TFLOP/s of float32 products for the split-bf16 kernels (dense bf16 MFMA peak 2500 / 6 MFMAs per product),
@@ -48,6 +54,7 @@ sys.path.insert(0, ROOT)
 # never load torch.cuda or touch HIP itself (a process that has initialised the GPU may not be replaced or forked on this pool)
 torch = None
 
+DUMP_CAP = 1 << 22                  # elements per --dump-outputs array (16 MB in float32, 32 MB in float64)
 IMG_FLAT = 3 * 128 * 128
 PEAK_F32_MFMA_TFLOPS = 157.3
 PEAK_BF16_MFMA_TFLOPS = 2500.0      # dense (MI355X_MICROARCH.md: Matrix cores)
@@ -173,6 +180,36 @@ def traffic_for(config, kernel):
     if d.get("sources_sha") != sources_sha():
         return None, f"{os.path.basename(path)} was collected with other kernel sources ({d.get('sources_sha')})"
     return d.get(kernel), os.path.basename(path)
+
+
+def dump_sample(x, seed=0):
+    """Flat float32 / float64 numpy copy of ``x`` (torch tensor on any device, or numpy array).  More than DUMP_CAP elements: a fixed,
+    seeded sample -- one element from each of DUMP_CAP equal strata, its offset in the stratum drawn from RandomState(seed) --
+    gathered where ``x`` lives."""
+    import numpy as np
+    x = x.reshape(-1)
+    n = x.shape[0]
+    if n > DUMP_CAP:
+        lo = np.arange(DUMP_CAP, dtype=np.int64) * n // DUMP_CAP
+        hi = np.arange(1, DUMP_CAP + 1, dtype=np.int64) * n // DUMP_CAP
+        idx = lo + (np.random.RandomState(seed).random_sample(DUMP_CAP) * (hi - lo)).astype(np.int64)
+        x = x[torch.from_numpy(idx).to(x.device)] if torch is not None and isinstance(x, torch.Tensor) else x[idx]
+    if torch is not None and isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    return x if x.dtype in (np.float32, np.float64) else x.astype(np.float64)
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, at most 64 MB in all."""
+    import numpy as np
+    arrays = {k: dump_sample(v, seed=i) for i, (k, v) in enumerate(arrays.items())}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes exceed 64 MB"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    print(f"[bench] wrote {', '.join(f'{k}{list(a.shape)}' for k, a in arrays.items())} ({total / 2 ** 20:.1f} MB) to {path}",
+          file=sys.stderr, flush=True)
 
 
 def free_port():
@@ -376,6 +413,7 @@ def bench_model(args, cfg_id, rank, world, dev, dist):
     opt_events = []                       # (start, end) around the optimizer step, only while `time_opt` is set (untimed pass)
     time_opt = [False]
     n_coll = [0]                          # collectives the last step issued (N > 1)
+    last_out = [None]                     # --dump-outputs: the model output of the last training step
 
     def batch_of(i):
         if feeder is not None:
@@ -391,6 +429,8 @@ def bench_model(args, cfg_id, rank, world, dev, dist):
                 nn_col = model(bfp, bimg).reshape(-1)
                 return stack.predict_device(nn_col, rf_col[s:s + BATCH], xgb_col[s:s + BATCH])
         out = model(bfp, bimg).squeeze()
+        if args.dump_outputs:
+            last_out[0] = out.detach()
         loss = crit(out, by)
         loss.backward()
         if time_opt[0]:
@@ -444,8 +484,8 @@ def bench_model(args, cfg_id, rank, world, dev, dist):
     ms_sum = (ctypes.c_float * nsec)()
     cnt = (ctypes.c_int * nsec)()
     # HIP events on the launch stream, recorded INSIDE the timed region, around the candidates for the dominant kernel only;
-    # the full per-section breakdown comes from an untimed pass below
-    timed_sections = set(cfg["candidates"])
+    # the full per-section breakdown comes from an untimed pass below.  --full only: a plain run records nothing
+    timed_sections = set(cfg["candidates"]) if args.full else set()
     per_step_pre = {}
     dom_timed = None
     if len(timed_sections) > 1:
@@ -470,8 +510,9 @@ def bench_model(args, cfg_id, rank, world, dev, dist):
             dom_pre = pick[0]
         timed_sections = {dom_pre}
         dom_timed = dom_pre
-    L.bbbp_profile_select(sum(1 << i for i, n in enumerate(names) if n in timed_sections))
-    L.bbbp_profile_enable(1)
+    if timed_sections:
+        L.bbbp_profile_select(sum(1 << i for i, n in enumerate(names) if n in timed_sections))
+        L.bbbp_profile_enable(1)
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -482,6 +523,13 @@ def bench_model(args, cfg_id, rank, world, dev, dist):
     L.bbbp_profile_enable(0)
     sections = {names[i]: ms_sum[i] / cnt[i] for i in range(nsec) if cnt[i]}
     launches_per_step = {names[i]: cnt[i] / args.steps for i in range(nsec) if cnt[i]}
+    if args.dump_outputs and rank == 0:
+        # what the caller of the last timed step receives, taken before any --full pass below steps the model again
+        if train:
+            state = torch.cat([v.detach().reshape(-1).float() for v in model.state_dict().values() if v.dtype.is_floating_point])
+            write_outputs(args.dump_outputs, {"prediction": last_out[0], "loss": last.detach(), "state": state})
+        else:
+            write_outputs(args.dump_outputs, {"prediction": last})
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -491,7 +539,7 @@ def bench_model(args, cfg_id, rank, world, dev, dist):
     # (rank 0 only -- except in exact-global-batch mode, where every step holds the engine's own collectives and all ranks must take it)
     all_ranks_step = bool(args.exact_batch) and world > 1
     untimed_launches = {}                 # launches per step of every section, from the untimed all-sections pass
-    if rank == 0 or all_ranks_step:
+    if args.full and (rank == 0 or all_ranks_step):
         L.bbbp_profile_enable(1)
         time_opt[0] = train
         for i in range(5):
@@ -507,7 +555,7 @@ def bench_model(args, cfg_id, rank, world, dev, dist):
                 untimed_launches[names[i]] = cnt[i] / 5.0
     # ... and the same kernels with the branch overlap off, i.e. each kernel alone on the GPU
     isolated, clock = {}, {}
-    if (rank == 0 or all_ranks_step) and not args.no_isolated:
+    if args.full and (rank == 0 or all_ranks_step) and not args.no_isolated:
         old = L.bbbp_set_overlap(0)
         for i in range(2):
             step(i, collective=False)
@@ -673,8 +721,9 @@ def bench_model(args, cfg_id, rank, world, dev, dist):
                    "gflop_per_step_per_gpu": round(total_flops / 1e9, 1),
                    "input": "host-fed (pinned, double-buffered copy stream)" if args.host_fed else "device-resident"},
         "model_tflops_per_gpu": round(total_flops / (ms_per_step * 1e-3) / 1e12, 2),
-        "roofline": roofline,
     }
+    if args.full:
+        result["roofline"] = roofline
     if roofline_encoder is not None:
         result["roofline_encoder"] = roofline_encoder
     if comm is not None:
@@ -688,9 +737,10 @@ def bench_model(args, cfg_id, rank, world, dev, dist):
         result["optimizer"] = ("fused AdamW pipelined into the backward pass, slice by slice (distributed.OverlappedGradAllReduce.step)" if pipelined
                                else "fused AdamW after the pass; the image-FC weight's slice on a side stream beside the next forward pass (read there 0.8 ms in)"
                                if defer is not None else "fused AdamW, one launch after the pass")
-        result["optimizer_ms_per_step"] = round(sum(a.elapsed_time(b) for a, b in opt_events) / len(opt_events), 4) if opt_events else None
+        if args.full:
+            result["optimizer_ms_per_step"] = round(sum(a.elapsed_time(b) for a, b in opt_events) / len(opt_events), 4) if opt_events else None
         result["final_loss"] = round(float(last.detach()), 5)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         if feeder is not None:
             bfp, bimg, by = feeder.host_batch(0)
         else:
@@ -748,6 +798,11 @@ def bench_mlp_grid(args, rank, world, dev, dist):
     if rank != 0:
         return None
     assert all(m.n_iter_ == args.steps for m in fitted), "every fit must run exactly --steps epochs"
+    if args.dump_outputs:
+        # the fitted models: every fit's coefs_ then intercepts_, fit after fit, and the [fits, epochs] loss curves
+        write_outputs(args.dump_outputs, {
+            "weights": np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1) for m in fitted for a in (*m.coefs_, *m.intercepts_)]),
+            "loss_curve": np.asarray([m.loss_curve_ for m in fitted], dtype=np.float64)})
     flops = 0
     for m in fitted:
         u = [f] + list(m.config.hidden_layer_sizes) + [1]
@@ -770,7 +825,7 @@ def bench_mlp_grid(args, rank, world, dev, dist):
     if comm is not None:
         result["rccl"] = comm
         result["collectives_per_step"] = 0
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         import warnings
         from sklearn.neural_network import MLPClassifier
         sample = [0, 100, 200, 269]
@@ -805,12 +860,19 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-isolated", action="store_true",
                     help="skip the untimed overlap-off leg (profiles: every launch of the rocprofv3 kernel table is then an in-step one)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the dominant kernel's roofline (HIP events in the timed region, "
+                         "untimed all-sections and overlap-off passes), the encoder chain's roofline, the optimizer's time, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
     default_steps = {1: (10, 2), 2: (300, 20), 3: (200, 20), 4: (40, 5), 5: (60, 5)}[args.config]
     if args.steps is None:
         args.steps = default_steps[0]
     if args.warmup is None:
         args.warmup = default_steps[1]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # typed as `python bench.py --gpus N`: start the N ranks as children BEFORE anything here touches torch or HIP
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))

@@ -14,7 +14,7 @@ for B in 512 4096; do
 done
 for T in 0 1; do
   echo "headline BBBP_C1_PIPE=1 BBBP_C1_TRAIN=$T" >> $O
-  BBBP_C1_PIPE=1 BBBP_C1_TRAIN=$T python3 bench.py --no-cpu-baseline > gpurun_out/r04_c1_train$T.log 2>&1 || { tail -5 gpurun_out/r04_c1_train$T.log; exit 1; }
+  BBBP_C1_PIPE=1 BBBP_C1_TRAIN=$T python3 bench.py --full --no-cpu-baseline > ${O%/*}/r04_c1_train$T.log 2>&1 || { tail -5 ${O%/*}/r04_c1_train$T.log; exit 1; }
   python3 - gpurun_out/r04_c1_train$T.log >> $O <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]
@@ -23,7 +23,7 @@ PY
 done
 for W in 1 2; do
   echo "config 5 BBBP_C1_PIPE=1 BBBP_C1_PER_CU=$W" >> $O
-  BBBP_C1_PIPE=1 BBBP_C1_PER_CU=$W python3 bench.py --config 5 --no-cpu-baseline > gpurun_out/r04_c5_pipe$W.log 2>&1 || exit 1
+  BBBP_C1_PIPE=1 BBBP_C1_PER_CU=$W python3 bench.py --full --config 5 --no-cpu-baseline > ${O%/*}/r04_c5_pipe$W.log 2>&1 || exit 1
   python3 - gpurun_out/r04_c5_pipe$W.log >> $O <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]

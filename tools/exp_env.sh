@@ -4,7 +4,7 @@ for cfg in "$@"; do
   for ss in 0 1; do
     echo "== $cfg single_stream=$ss"
     if [ "$cfg" = "-" ]; then envs=""; else envs="$cfg"; fi
-    env $envs BBBP_SINGLE_STREAM=$ss python bench.py --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+    env $envs BBBP_SINGLE_STREAM=$ss python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 r = d['roofline']

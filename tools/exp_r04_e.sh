@@ -5,7 +5,7 @@ O=gpurun_out/r04_e.txt
 python3 -m pytest tests/test_gpu_parity_sizes.py -q -m gpu -k "adamw" > gpurun_out/r04_e_t.log 2>&1; tail -1 gpurun_out/r04_e_t.log >> $O
 for PR in 0 3 1 0 3; do
   echo "BBBP_CONV_BWD_PRIO=$PR" >> $O
-  BBBP_CONV_BWD_PRIO=$PR python3 bench.py --no-cpu-baseline --no-isolated > gpurun_out/r04_e_bench$PR.log 2>&1 || { tail -5 gpurun_out/r04_e_bench$PR.log; echo FAILED >> $O; }
+  BBBP_CONV_BWD_PRIO=$PR python3 bench.py --full --no-cpu-baseline --no-isolated > ${O%/*}/r04_e_bench$PR.log 2>&1 || { tail -5 ${O%/*}/r04_e_bench$PR.log; echo FAILED >> $O; }
   python3 - gpurun_out/r04_e_bench$PR.log >> $O <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]

@@ -7,7 +7,7 @@ tail -1 gpurun_out/r04_f_t1.log >> $O
 python3 -m pytest tests/test_gpu_variants.py tests/test_gpu_parity_sizes.py -q -m gpu > gpurun_out/r04_f_t2.log 2>&1 || { tail -30 gpurun_out/r04_f_t2.log; echo "VARIANT/PARITY TESTS FAILED" >> $O; }
 tail -1 gpurun_out/r04_f_t2.log >> $O
 for i in 1 2; do
-  python3 bench.py --no-cpu-baseline --no-isolated > gpurun_out/r04_f_bench$i.log 2>&1 || { tail -5 gpurun_out/r04_f_bench$i.log; echo FAILED >> $O; }
+  python3 bench.py --full --no-cpu-baseline --no-isolated > ${O%/*}/r04_f_bench$i.log 2>&1 || { tail -5 ${O%/*}/r04_f_bench$i.log; echo FAILED >> $O; }
   python3 - gpurun_out/r04_f_bench$i.log >> $O <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]

@@ -11,7 +11,7 @@ for v in 0 1; do
   echo "== MLP_PRELOAD=$v" >> $O
   step timeout -k 10 300 python3 -m pytest tests/test_gpu_mlp.py -q -m gpu > gpurun_out/r04_o_tests$v.log 2>&1; tail -1 gpurun_out/r04_o_tests$v.log >> $O
   step timeout -k 10 300 python3 tools/mlp_phases.py 4 >> $O 2>&1
-  step timeout -k 10 300 python3 bench.py --config 1 --no-cpu-baseline >> $O 2>&1
+  step timeout -k 10 300 python3 bench.py --full --config 1 --no-cpu-baseline >> $O 2>&1
 done
 grep -v amdgpu.ids $O | cut -c1-260
 exit 0

@@ -12,8 +12,8 @@ BBBP_C2_PIPE=1 step timeout -k 10 400 python3 -m pytest tests/test_gpu_ops.py te
 for v in 0 1 0 1; do
   echo "== BBBP_C2_PIPE=$v" >> $O
   BBBP_C2_PIPE=$v step timeout -k 10 300 python3 tools/bench_conv2.py 512 2>&1 | grep "split-bf16 B=512" | cut -c1-120 >> $O
-  BBBP_C2_PIPE=$v step timeout -k 10 200 python3 bench.py --no-cpu-baseline 2>/dev/null | line headline >> $O
-  BBBP_C2_PIPE=$v step timeout -k 10 200 python3 bench.py --config 5 --no-cpu-baseline 2>/dev/null | line config5 >> $O
+  BBBP_C2_PIPE=$v step timeout -k 10 200 python3 bench.py --full --no-cpu-baseline 2>/dev/null | line headline >> $O
+  BBBP_C2_PIPE=$v step timeout -k 10 200 python3 bench.py --full --config 5 --no-cpu-baseline 2>/dev/null | line config5 >> $O
 done
 cat $O
 exit 0

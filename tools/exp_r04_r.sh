@@ -8,12 +8,12 @@ import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); print(d['ms_per_step'], d['value'], d.get('optimizer','')[:60])"; }
-echo "config 4 default" >> $O; step timeout -k 10 200 python3 bench.py --config 4 --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
+echo "config 4 default" >> $O; step timeout -k 10 200 python3 bench.py --full --config 4 --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
 for bg in 0 32 64 128 256; do
   echo "config 4 pipelined step, BBBP_ADAMW_BACKGROUND=$bg" >> $O
-  BBBP_BENCH_PIPELINED_STEP=1 BBBP_ADAMW_BACKGROUND=$bg step timeout -k 10 200 python3 bench.py --config 4 --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
+  BBBP_BENCH_PIPELINED_STEP=1 BBBP_ADAMW_BACKGROUND=$bg step timeout -k 10 200 python3 bench.py --full --config 4 --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
 done
 echo "config 3 pipelined step, BBBP_ADAMW_BACKGROUND=64" >> $O
-BBBP_BENCH_PIPELINED_STEP=1 BBBP_ADAMW_BACKGROUND=64 step timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
+BBBP_BENCH_PIPELINED_STEP=1 BBBP_ADAMW_BACKGROUND=64 step timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
 cat $O
 exit 0

@@ -5,10 +5,10 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/r04_s.txt; : > $O
 step() { "$@"; rc=$?; if [ $rc -ge 124 ]; then echo "step killed (rc $rc): stopping" | tee -a $O; exit $rc; fi; }
 export BBBP_BENCH_BACKEND=gloo
 echo "== smoke" >> $O; step timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" >> $O 2>&1
-echo "== config 3 --gpus 2" >> $O; step timeout -k 10 300 python3 bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/r04_bench_n2_gloo_one_gpu.log 2>&1; echo "rc $?" >> $O; tail -1 gpurun_out/r04_bench_n2_gloo_one_gpu.log > gpurun_out/r04_bench_n2_gloo_one_gpu.json
-echo "== config 3 --gpus 2 --exact-batch" >> $O; step timeout -k 10 300 python3 bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --exact-batch > gpurun_out/r04_bench_exact_batch_n2_gloo_one_gpu.log 2>&1; echo "rc $?" >> $O; tail -1 gpurun_out/r04_bench_exact_batch_n2_gloo_one_gpu.log > gpurun_out/r04_bench_exact_batch_n2_gloo_one_gpu.json
+echo "== config 3 --gpus 2" >> $O; step timeout -k 10 300 python3 bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline > ${O%/*}/r04_bench_n2_gloo_one_gpu.log 2>&1; echo "rc $?" >> $O; tail -1 ${O%/*}/r04_bench_n2_gloo_one_gpu.log > ${O%/*}/r04_bench_n2_gloo_one_gpu.json
+echo "== config 3 --gpus 2 --exact-batch" >> $O; step timeout -k 10 300 python3 bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --exact-batch > ${O%/*}/r04_bench_exact_batch_n2_gloo_one_gpu.log 2>&1; echo "rc $?" >> $O; tail -1 ${O%/*}/r04_bench_exact_batch_n2_gloo_one_gpu.log > ${O%/*}/r04_bench_exact_batch_n2_gloo_one_gpu.json
 for c in 1 2 4 5; do
-  echo "== config $c --gpus 2" >> $O; step timeout -k 10 300 python3 bench.py --config $c --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/r04_bench_config${c}_n2.log 2>&1; echo "rc $?" >> $O; tail -1 gpurun_out/r04_bench_config${c}_n2.log | cut -c1-400 >> $O
+  echo "== config $c --gpus 2" >> $O; step timeout -k 10 300 python3 bench.py --full --config $c --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > ${O%/*}/r04_bench_config${c}_n2.log 2>&1; echo "rc $?" >> $O; tail -1 ${O%/*}/r04_bench_config${c}_n2.log | cut -c1-400 >> $O
 done
 python3 - <<'P' >> $O
 import json

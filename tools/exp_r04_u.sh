@@ -9,9 +9,9 @@ for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); print(d['ms_per_step'], round(d['value']))"; }
 for rep in 1 2; do
-echo "one stream" >> $O; step timeout -k 10 200 python3 bench.py --config 5 --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
-echo "two streams, conv1 1 per CU" >> $O; BBBP_SCREEN_OVERLAP=1 step timeout -k 10 200 python3 bench.py --config 5 --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
-echo "two streams, conv1 2 per CU" >> $O; BBBP_SCREEN_OVERLAP=1 BBBP_SCREEN_C1_PER_CU=2 step timeout -k 10 200 python3 bench.py --config 5 --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
+echo "one stream" >> $O; step timeout -k 10 200 python3 bench.py --full --config 5 --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
+echo "two streams, conv1 1 per CU" >> $O; BBBP_SCREEN_OVERLAP=1 step timeout -k 10 200 python3 bench.py --full --config 5 --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
+echo "two streams, conv1 2 per CU" >> $O; BBBP_SCREEN_OVERLAP=1 BBBP_SCREEN_C1_PER_CU=2 step timeout -k 10 200 python3 bench.py --full --config 5 --no-cpu-baseline --no-isolated 2>/dev/null | line >> $O
 done
 cat $O
 exit 0

@@ -12,9 +12,9 @@ for l in sys.stdin:
 for v in 1 0 1 0; do
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -DB3_EARLY_LOADS=$v -I include -c $P/csrc/conv_b3.hip -o $P/build/conv_b3.o && /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $P/libbbbp_hip.so $P/build/*.o || exit 1
   echo "== B3_EARLY_LOADS=$v" >> $O
-  step timeout -k 10 200 python3 bench.py --no-cpu-baseline 2>/dev/null | line headline >> $O
-  step timeout -k 10 200 python3 bench.py --config 5 --no-cpu-baseline 2>/dev/null | line config5 >> $O
-  step timeout -k 10 200 python3 bench.py --config 2 --no-cpu-baseline 2>/dev/null | line config2 >> $O
+  step timeout -k 10 200 python3 bench.py --full --no-cpu-baseline 2>/dev/null | line headline >> $O
+  step timeout -k 10 200 python3 bench.py --full --config 5 --no-cpu-baseline 2>/dev/null | line config5 >> $O
+  step timeout -k 10 200 python3 bench.py --full --config 2 --no-cpu-baseline 2>/dev/null | line config2 >> $O
 done
 cat $O
 exit 0

@@ -1,5 +1,5 @@
 out=gpurun_out/direct_sweep.log; : > $out
-run() { echo "## $*" >> $out; env "$@" timeout -k 10 120 python bench.py --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 >> $out || exit 1; }
+run() { echo "## $*" >> $out; env "$@" timeout -k 10 120 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 >> $out || exit 1; }
 run A=0
 run BBBP_GEMM_DIRECT_T=2
 run BBBP_GEMM_DIRECT_KS=1

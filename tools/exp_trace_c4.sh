@@ -3,7 +3,7 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
-rocprofv3 --kernel-trace --output-format csv -d $O/r03_trace4 -- python3 bench.py --config ${CFG:-4} --steps 3 --warmup 1 --no-cpu-baseline --no-isolated > $O/r03_trace4.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --output-format csv -d $O/r03_trace4 -- python3 bench.py --full --config ${CFG:-4} --steps 3 --warmup 1 --no-cpu-baseline --no-isolated > $O/r03_trace4.log 2>&1 || exit 1
 f=$(find $O/r03_trace4 -name '*kernel_trace.csv' | head -1)
 python3 - "$f" <<'PY' > $O/r03_trace_config${CFG:-4}.txt
 import csv, sys, collections

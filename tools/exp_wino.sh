@@ -2,7 +2,7 @@
 # In-situ effect of the Winograd conv2 kernels (one GPU): conv2 form x schedule, then the sweep over the CUs their grids take
 # while the branches overlap.  Full bench lines -> gpurun_out/wino_insitu.log, summary on stdout.
 out=gpurun_out/wino_insitu.log; mkdir -p gpurun_out; : > $out
-run() { echo "## $*" >> $out; env "$@" timeout -k 10 120 python bench.py --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 >> $out || exit 1; }
+run() { echo "## $*" >> $out; env "$@" timeout -k 10 120 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 >> $out || exit 1; }
 run BBBP_CONV_WINOGRAD=0
 run BBBP_CONV_WINOGRAD=0 BBBP_SINGLE_STREAM=1
 run BBBP_CONV_WINOGRAD=3 BBBP_SINGLE_STREAM=1
