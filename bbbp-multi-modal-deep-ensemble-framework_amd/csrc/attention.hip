@@ -409,7 +409,7 @@ int head_parts(int nhead, int B) {
 // at F = 2048 (256 heads) a head's query blocks are split over two groups, and two groups per CU cover each other's exp / Philox / LDS
 // latencies: 135 -> 124 us per layer at B = 512 (256: one group per head, 1024: 138 us)
 int fwd_parts(int nhead, int B) {
-    static const int target = [] { const char* e = getenv("BBBP_ATTN_FWD_WGS"); return e ? atoi(e) : 512; }();
+    static const int target = bbbp_env_int("BBBP_ATTN_FWD_WGS", 512);
     int parts = (target > 0 ? target : 512) / (nhead > 0 ? nhead : 1);
     const int blocks = (B + 15) / 16;
     if (parts > (blocks + NW - 1) / NW) parts = (blocks + NW - 1) / NW;
@@ -765,7 +765,7 @@ int bbbp_attn_small_bwd(hipStream_t st, const float* qkv, const float* ctx, cons
         return BBBP_OK;
     }
     // one work-group per head and at most NW * BWD1_NKT key tiles: the single-sweep kernel (BBBP_ATTN_BWD1=0: the two-sweep kernel)
-    static const int bwd1 = [] { const char* e = getenv("BBBP_ATTN_BWD1"); return e ? atoi(e) : 1; }();
+    static const int bwd1 = bbbp_env_int("BBBP_ATTN_BWD1", 1);
     if (bwd1 && (p == 0.f || keep != nullptr) && head_parts(nhead, B) == 1 && (B + 15) / 16 <= NW * BWD1_NKT && bwd1_lds(B, D) <= LDS_MAX) {
         const size_t lds1 = bwd1_lds(B, D);
         if (D == 8) { int rc = set_dyn_lds(attn_small_bwd1_kernel<2, BWD1_NKT>, lds1); if (rc) return rc; hipLaunchKernelGGL((attn_small_bwd1_kernel<2, BWD1_NKT>), dim3(nhead), dim3(NTH), lds1, st, P); }

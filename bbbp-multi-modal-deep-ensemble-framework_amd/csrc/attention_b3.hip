@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void attn_b3_merge_kernel(B3AttnParams p) {
 
 int plan_splits(int B, int NH, int* keys_per_split) {
     const int nqb = (B + QBLK - 1) / QBLK;
-    static const int wg_per_cu_x2 = [] { const char* e = getenv("BBBP_ATTN_B3_WG_X2"); return e ? atoi(e) : 2; }();      // tuning: work-groups per CU x 2 (one per CU: two cannot co-reside)
+    static const int wg_per_cu_x2 = bbbp_env_int("BBBP_ATTN_B3_WG_X2", 2);      // tuning: work-groups per CU x 2 (one per CU: two cannot co-reside)
     int ns = (wg_per_cu_x2 * bbbp_num_cus() / 2 + nqb * NH - 1) / (nqb * NH);
     const int max_ns = (B + 255) / 256;                                 // at least 256 keys (8 tiles) per range
     if (ns > max_ns) ns = max_ns;
@@ -295,7 +295,7 @@ int bbbp_attn_b3_fwd(hipStream_t st, const float* qkv, float* ctx, int B, int F,
     const int D = F / nhead;
     BBBP_CHECK_ARG(bbbp_attn_b3_supported(B, nhead, D) && F == nhead * D, "attn_b3: B=%d nhead=%d head_dim=%d not supported", B, nhead, D);
     BBBP_CHECK_ARG(qkv && ctx, "attn_b3: null pointer");
-    static const int exp_bits = [] { const char* e = getenv("BBBP_ATTN_B3_EXP"); return e ? atoi(e) : 0; }();
+    static const int exp_bits = bbbp_env_int("BBBP_ATTN_B3_EXP", 0);
     B3AttnParams p{qkv, ctx, workspace, B, F, nhead, D, scale * 1.4426950408889634f, 1, 0, exp_bits};
     p.nsplit = plan_splits(B, nhead, &p.keys_per_split);
     if (p.nsplit > 1) BBBP_CHECK_ARG(workspace && workspace_bytes >= bbbp_attn_b3_workspace_bytes(B, nhead, D), "attn_b3: workspace too small");

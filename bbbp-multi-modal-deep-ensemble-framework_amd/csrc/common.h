@@ -42,28 +42,52 @@ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; 
 int bbbp_num_cus();   // cached multiProcessorCount of the current device
 int bbbp_ensure_dyn_lds(const void* kernel, size_t bytes);   // hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device)
 
+// Knobs.  Every BBBP_* environment variable is an integer read through bbbp_env_int (`dflt` when unset); call sites keep the value in a
+// `static const`, so it is read once.  bbbp_env is the raw string (NULL when unset) for the one knob that is not parsed as a number.
+const char* bbbp_env(const char* name);
+int bbbp_env_int(const char* name, int dflt);
+static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// A knob that also has an exported setter: the environment's value at first use, then whatever set() stored.  `norm` is the knob's mask or
+// clamp; it is applied to both.
+struct Knob {
+    const char* env; int dflt; int (*norm)(int);
+    int v = -1;
+    int get() { if (v < 0) v = norm(bbbp_env_int(env, dflt)); return v; }
+    int set(int x) { const int prev = get(); v = norm(x); return prev; }
+};
+static inline int knob_bool(int v) { return v != 0; }
+
 // CU partitioning for the two-branch overlap (engine.hip).  A persistent conv work-group takes >= 120 KB of a CU's
 // 160 KB LDS, so exactly one fits per CU; with `reserved_cus` > 0 the conv grids shrink to (CUs - reserved) and the
 // small side-stream kernels request `small_lds_pad` bytes (> 40 KB) so that they can ONLY land on the CUs the conv
 // grids left free.  Measured without it: a 5 us kernel sharing CUs with a conv kernel takes 35-85 us.
 extern thread_local int g_bbbp_reserved_cus;
 extern thread_local size_t g_bbbp_small_lds_pad;
-// engine scope: keep the first conv stage's forward on the f32 kernel for this call even when bit 6 of the conv mask selects the split-bf16
-// form.  Set while a training step's encoder chain runs beside the image branch: the split-bf16 kernel is faster alone (0.19 vs 0.26 ms
-// at B = 512) but holds 2 x 248 registers per lane slot on every SIMD, and the forward pass of that step is bound by the encoder's
-// latency chain, which then finds no wave slots (measured: conv1 0.31 -> 0.20 ms in-step, encoder forward 1.21 -> 1.33, step 2.61 -> 2.70)
-extern thread_local int g_bbbp_conv1_fwd_f32;
-// engine scope: work-groups per CU for the split-bf16 conv1 forward (0 = the kernel's own default).  The software-pipelined form keeps the
-// matrix pipe busy with ONE wave per SIMD, so beside an encoder chain the engine asks for one work-group per CU (half the register file and
-// 100 KB of LDS stay free for the chain's kernels)
-extern thread_local int g_bbbp_conv1_fwd_per_cu;
-// conv2's weight gradient on the structured-sparse MFMA (conv_b3.hip: conv_b3_wgrad_sp_kernel) has an 8-wave form (fastest alone: two waves
-// of 256 registers per SIMD) and a 4-wave form that leaves ~200 registers per lane slot to the fingerprint branch's kernels; the engine
-// asks for the latter while an encoder chain runs beside the image branch (0 = no preference: 8 waves)
-extern thread_local int g_bbbp_conv_wgrad_beside_encoder;
-// conv_b3.hip, forward of the 64 x 64-map stages: 1 = the software-pipelined one-work-group-per-CU kernel (what the engine asks for while an encoder
-// chain runs beside the image branch: slower alone, but it leaves the chain three quarters of every SIMD), 0 = two work-groups per CU
-extern thread_local int g_bbbp_conv2_fwd_pipe;
+// Which form of a conv stage's kernels a caller wants: chosen by the engine from its plan (engine.hip), or from the calling thread's two
+// settable values by the C entry points (conv.hip); passed down to the launch functions below as arguments.
+struct ConvPrefs {
+    // keep the first conv stage's forward on the f32 kernel for this call even when bit 6 of the conv mask selects the split-bf16
+    // form.  Set while a training step's encoder chain runs beside the image branch: the split-bf16 kernel is faster alone (0.19 vs 0.26 ms
+    // at B = 512) but holds 2 x 248 registers per lane slot on every SIMD, and the forward pass of that step is bound by the encoder's
+    // latency chain, which then finds no wave slots (measured: conv1 0.31 -> 0.20 ms in-step, encoder forward 1.21 -> 1.33, step 2.61 -> 2.70)
+    int conv1_fwd_f32 = 0;
+    // work-groups per CU for the split-bf16 conv1 forward (0 = the kernel's own default).  The software-pipelined form keeps the
+    // matrix pipe busy with ONE wave per SIMD, so beside an encoder chain the engine asks for one work-group per CU (half the register file and
+    // 100 KB of LDS stay free for the chain's kernels)
+    int conv1_fwd_per_cu = 0;
+    // conv_b3.hip, forward of the 64 x 64-map stages: 1 = the software-pipelined one-work-group-per-CU kernel (what the engine asks for while an encoder
+    // chain runs beside the image branch: slower alone, but it leaves the chain three quarters of every SIMD), 0 = two work-groups per CU
+    int conv2_fwd_pipe = 0;
+    // conv2's weight gradient on the structured-sparse MFMA (conv_b3.hip: conv_b3_wgrad_sp_kernel) has an 8-wave form (fastest alone: two waves
+    // of 256 registers per SIMD) and a 4-wave form that leaves ~200 registers per lane slot to the fingerprint branch's kernels; the engine
+    // asks for the latter while an encoder chain runs beside the image branch (0 = no preference: 8 waves)
+    int wgrad_beside_encoder = 0;
+};
+// conv.hip: the C entry points bbbp_conv3x3_relu_pool_fwd / _bwd_weight with the form choices as an argument
+int conv3x3_relu_pool_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int cin, int cout,
+                          int H, int W, void* workspace, size_t workspace_bytes, const ConvPrefs& prefs);
+int conv3x3_relu_pool_bwd_weight(hipStream_t st, const float* x, const float* gy, const uint8_t* gmask, float* dw, float* dbias, int B, int cin,
+                                 int cout, int H, int W, void* workspace, size_t workspace_bytes, const ConvPrefs& prefs);
 extern thread_local int g_bbbp_wino_side_cus;      // CUs the Winograd conv grids leave free while the engine overlaps its branches
 // head.hip: fused fusion-block + regression-head forward (two launches); `partial`: ceil(B/16) * 2 * 256 floats
 int bbbp_head_forward_fused(hipStream_t st, const float* comb, const float* const* fw1, const float* const* fb1,
@@ -119,19 +143,19 @@ size_t bbbp_b3_workspace_bytes();
 // round 4: the same kernels for the two large stages of the wide / deep variant (64 -> 128 @ 64 x 64, 128 -> 256 @ 32 x 32)
 bool bbbp_b3_conv_supported(int cin, int cout, int hw);
 size_t bbbp_b3_workspace_bytes(int cin, int cout);
-int bbbp_b3_conv_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int cin, int cout, void* workspace);
+int bbbp_b3_conv_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int cin, int cout, void* workspace,
+                     int pipe);      // pipe: ConvPrefs::conv2_fwd_pipe (64 x 64 maps)
 int bbbp_b3_conv_dgrad(hipStream_t st, const float* gy, const uint8_t* gmask, const float* w, float* dx, int B, int cin, int cout, void* workspace);
-int bbbp_b3_conv2_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, void* workspace);
-int bbbp_b3_conv2_dgrad(hipStream_t st, const float* gy, const uint8_t* gmask, const float* w, float* dx, int B, void* workspace);
-// form: 0 dense split-bf16, 1 structured-sparse MFMA (8 waves, or 4 beside an encoder chain), 2 structured-sparse, 4 waves
+// form: 0 dense split-bf16, 1 structured-sparse MFMA (8 waves, or 4 with beside_encoder: ConvPrefs::wgrad_beside_encoder), 2 structured-sparse, 4 waves
 // (cin_total, cout_total, groups: the stage's channel counts and the work-groups per (32 ci, 64 co) block pair; grid = pairs * groups;
 //  map: 64 x 64 maps, or 32 x 32 for the sparse forms)
 int bbbp_b3_conv2_wgrad(hipStream_t st, const float* x, const float* gy, const uint8_t* mask, float* slab, float* bslab, int B, int grid, int form,
-                        int cin_total = 32, int cout_total = 64, int groups = 0, int map = 64);
+                        int beside_encoder, int cin_total = 32, int cout_total = 64, int groups = 0, int map = 64);
 int bbbp_b3_last_clock(unsigned long long* shader_cycles, unsigned long long* ticks_100mhz);
 // conv_b3c1.hip: forward of the first stage (3 -> 32 @ 128x128) in the same arithmetic, channel-innermost LDS strip, no operand assembly
 size_t bbbp_b3_conv1_fwd_workspace_bytes();
-int bbbp_b3_conv1_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, void* workspace);
+int bbbp_b3_conv1_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, void* workspace,
+                      int want_per_cu);      // ConvPrefs::conv1_fwd_per_cu
 int bbbp_b3_conv1_wgrad(hipStream_t st, const float* x, const float* gy, const uint8_t* mask, float* slab, float* bslab, int B, int grid);
 int bbbp_wino_last_phases(unsigned long long* phases4);     // BBBP_WINO_PROBE=1 builds of the kernel only
 // rowops.hip: a slice of the optimizer step deferred to a side stream (bbbp_adamw_step_deferred).  Entry points that read parameters

@@ -770,8 +770,7 @@ int launch_conv(const ConvParams& p, hipStream_t st) {
     int per_cu = (int)((160 * 1024) / lds);
     if (per_cu > 2) per_cu = 2;      // measured: more than 2 groups per CU buys nothing and crowds out the side-stream kernels
     if (per_cu < 1) per_cu = 1;
-    static int cap = -1;
-    if (cap < 0) { const char* e = getenv("BBBP_CONV_PER_CU"); cap = e ? atoi(e) : 0; }
+    static const int cap = bbbp_env_int("BBBP_CONV_PER_CU", 0);
     if (cap > 0 && per_cu > cap) per_cu = cap;
     int cus = bbbp_num_cus() - (part ? g_bbbp_reserved_cus : 0);
     if (cus < 1) cus = 1;
@@ -793,25 +792,25 @@ inline bool supported(int cin, int cout, int h, int w) {
 // Algorithm of the 32 -> 64 @ 64x64 stage.  bit 0 / 1: forward / data gradient as Winograd F(2x2,3x3) (conv_wino.hip);
 // bit 2 / 3 / 4: forward / data gradient / weight gradient as the split-bf16 direct form (conv_b3.hip; takes precedence over
 // the Winograd bit).
-int g_winograd = -1;
+// default since round 2: all three as split-bf16 (28; the weight gradient alone 0.63 -> 0.42 ms, and beside it the encoder's
+// backward chain runs 1.93 -> 1.45 ms: 4 waves x 180 registers instead of conv_wgrad32's 8 x 224) -- alone as fast as the Winograd form (0.42 / 0.41 vs 0.42 / 0.44 ms at B = 512), and in
+// the training step 0.47 / 0.42 vs 0.57 / 0.61 ms: 66 KB of LDS and 160 registers per wave leave room for the other branch's
+// kernels on every CU (the Winograd work-groups take whole CUs and give 64 of them up), and a bf16 MFMA holds the vector issue
+// for 8 of its 32 cycles where the f32 MFMA blocks it for all 64
+// round 3: + bit 7, conv2's weight gradient on the 2:4 structured-sparse MFMA (conv_b3.hip: conv_b3_wgrad_sp_kernel; 0.54 -> 0.33 ms in
+// the step); bit 8 (test hook) forces its 4-wave form
+Knob g_winograd{"BBBP_CONV_WINOGRAD", 252, [](int v) { return v & 511; }};
+inline int winograd_mask() { return g_winograd.get(); }
 int g_last_clock_wino = 0;
-inline int winograd_mask() {
-    // default since round 2: all three as split-bf16 (28; the weight gradient alone 0.63 -> 0.42 ms, and beside it the encoder's
-    // backward chain runs 1.93 -> 1.45 ms: 4 waves x 180 registers instead of conv_wgrad32's 8 x 224) -- alone as fast as the Winograd form (0.42 / 0.41 vs 0.42 / 0.44 ms at B = 512), and in
-    // the training step 0.47 / 0.42 vs 0.57 / 0.61 ms: 66 KB of LDS and 160 registers per wave leave room for the other branch's
-    // kernels on every CU (the Winograd work-groups take whole CUs and give 64 of them up), and a bf16 MFMA holds the vector issue
-    // for 8 of its 32 cycles where the f32 MFMA blocks it for all 64
-    // round 3: + bit 7, conv2's weight gradient on the 2:4 structured-sparse MFMA (conv_b3.hip: conv_b3_wgrad_sp_kernel; 0.54 -> 0.33 ms in
-    // the step); bit 8 (test hook) forces its 4-wave form
-    if (g_winograd < 0) { const char* e = getenv("BBBP_CONV_WINOGRAD"); g_winograd = e ? atoi(e) & 511 : 252; }
-    return g_winograd;
-}
+// the calling thread's two settable form choices (bbbp_set_conv2_fwd_pipe, bbbp_set_conv_wgrad_beside_encoder): read by the C entry points only
+thread_local int g_bbbp_conv2_fwd_pipe = 0;
+thread_local int g_bbbp_conv_wgrad_beside_encoder = 0;
 
 }  // namespace
 
 extern "C" int bbbp_set_conv_winograd(int mask) {
     BBBP_CHECK_ARG(mask >= 0 && mask <= 511, "set_conv_winograd: mask %d (bits 0/1 Winograd forward / data gradient, bits 2/3/4 split-bf16 forward / data gradient / weight gradient of conv2, bits 5/6 split-bf16 weight gradient / forward of conv1, bit 7 conv2's split-bf16 weight gradient on the structured-sparse MFMA, bit 8 its 4-wave form)", mask);
-    g_winograd = mask;
+    g_winograd.set(mask);
     return BBBP_OK;
 }
 
@@ -843,13 +842,39 @@ extern "C" size_t bbbp_conv3x3_workspace_bytes(int B, int cin, int cout, int H, 
     return align_up(m > slab ? m : slab, 256);
 }
 
+// The conv2-family weight gradient has two structured-sparse forms (conv_b3.hip): 8 waves (fastest alone) and 4 waves (one wave per SIMD: the
+// form to run while ANOTHER branch's small kernels share the GPU).  bbbp_mixed_backward picks by itself; a caller that composes the model
+// op by op and overlaps its branches on two streams says so for the calling thread around its bbbp_conv3x3_relu_pool_bwd_weight call.
+// Returns the previous setting.
+extern "C" int bbbp_set_conv_wgrad_beside_encoder(int on) {
+    const int prev = g_bbbp_conv_wgrad_beside_encoder;
+    g_bbbp_conv_wgrad_beside_encoder = on ? 1 : 0;
+    return prev;
+}
+
+// Forward of the 32 -> 64 / 64 -> 128 stages on 64 x 64 maps: 1 selects, for the calling thread, the software-pipelined kernel that runs ONE
+// work-group per CU (conv_b3.hip: conv_b3p_kernel) -- 3 % slower alone, but beside an encoder chain the step is 2.8 % faster
+// (bbbp_mixed_forward asks for it by itself for training plans with an encoder).  Same arithmetic in the same order: bit-identical outputs
+// and decisions.  Returns the previous setting.  BBBP_C2_PIPE=0 / 1 overrides every caller.
+extern "C" int bbbp_set_conv2_fwd_pipe(int on) {
+    const int prev = g_bbbp_conv2_fwd_pipe;
+    g_bbbp_conv2_fwd_pipe = on ? 1 : 0;
+    return prev;
+}
+
 extern "C" int bbbp_conv3x3_relu_pool_fwd(void* stream, const float* x, const float* w, const float* bias,
                                           float* y, uint8_t* mask, int B, int cin, int cout, int H, int W,
                                           void* workspace, size_t workspace_bytes) {
+    ConvPrefs prefs;
+    prefs.conv2_fwd_pipe = g_bbbp_conv2_fwd_pipe;
+    return conv3x3_relu_pool_fwd(static_cast<hipStream_t>(stream), x, w, bias, y, mask, B, cin, cout, H, W, workspace, workspace_bytes, prefs);
+}
+
+int conv3x3_relu_pool_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int cin, int cout,
+                          int H, int W, void* workspace, size_t workspace_bytes, const ConvPrefs& prefs) {
     BBBP_CHECK_ARG(supported(cin, cout, H, W), "conv fwd: unsupported shape cin=%d cout=%d H=%d W=%d", cin, cout, H, W);
     BBBP_CHECK_ARG(x && w && bias && y && workspace, "conv fwd: null pointer");      // mask may be null: forward-only call, no decisions kept
     if (B == 0) return BBBP_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     int cinp = cin < 8 ? 4 : cin;
     size_t need = (size_t)9 * cinp * cout * sizeof(float);
     BBBP_CHECK_ARG(workspace_bytes >= need, "conv fwd: workspace %zu < %zu", workspace_bytes, need);
@@ -858,16 +883,16 @@ extern "C" int bbbp_conv3x3_relu_pool_fwd(void* stream, const float* x, const fl
     if (bbbp_b3_conv_supported(cin, cout, H) && H == W && (winograd_mask() & 4)) {
         BBBP_CHECK_ARG(workspace_bytes >= bbbp_b3_workspace_bytes(cin, cout), "conv fwd: workspace too small");
         g_last_clock_wino = 2;               // split-bf16 kernel: its own stamps (conv_b3.hip)
-        return bbbp_b3_conv_fwd(st, x, w, bias, y, mask, B, cin, cout, workspace);
+        return bbbp_b3_conv_fwd(st, x, w, bias, y, mask, B, cin, cout, workspace, prefs.conv2_fwd_pipe);
     }
     if (cin == 32 && cout == 64 && (winograd_mask() & 1)) {
         BBBP_CHECK_ARG(workspace_bytes >= (size_t)16 * 32 * 64 * sizeof(float), "conv fwd: workspace too small");
         g_last_clock_wino = 1;
         return bbbp_wino_conv2_fwd(st, x, w, bias, y, mask, B, wt);
     }
-    if (cin == 3 && cout == 32 && W == 128 && (winograd_mask() & 64) && !g_bbbp_conv1_fwd_f32) {          // split-bf16 forward of the first stage (conv_b3c1.hip)
+    if (cin == 3 && cout == 32 && W == 128 && (winograd_mask() & 64) && !prefs.conv1_fwd_f32) {          // split-bf16 forward of the first stage (conv_b3c1.hip)
         BBBP_CHECK_ARG(workspace_bytes >= bbbp_b3_conv1_fwd_workspace_bytes(), "conv fwd: workspace too small");
-        return bbbp_b3_conv1_fwd(st, x, w, bias, y, mask, B, workspace);
+        return bbbp_b3_conv1_fwd(st, x, w, bias, y, mask, B, workspace, prefs.conv1_fwd_per_cu);
     }
     int total = 9 * cinp * cout;
     hipLaunchKernelGGL(conv_prep_weights_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, w, wt, cin, cout, cinp, MODE_FWD);
@@ -927,9 +952,15 @@ static int launch_wgrad32(WgradParams p, int grid, hipStream_t st) {
 extern "C" int bbbp_conv3x3_relu_pool_bwd_weight(void* stream, const float* x, const float* gy, const uint8_t* mask,
                                                  float* dw, float* db, int B, int cin, int cout, int H, int W,
                                                  void* workspace, size_t workspace_bytes) {
+    ConvPrefs prefs;
+    prefs.wgrad_beside_encoder = g_bbbp_conv_wgrad_beside_encoder;
+    return conv3x3_relu_pool_bwd_weight(static_cast<hipStream_t>(stream), x, gy, mask, dw, db, B, cin, cout, H, W, workspace, workspace_bytes, prefs);
+}
+
+int conv3x3_relu_pool_bwd_weight(hipStream_t st, const float* x, const float* gy, const uint8_t* mask, float* dw, float* db, int B, int cin,
+                                 int cout, int H, int W, void* workspace, size_t workspace_bytes, const ConvPrefs& prefs) {
     BBBP_CHECK_ARG(supported(cin, cout, H, W), "conv bwd_weight: unsupported shape cin=%d cout=%d H=%d W=%d", cin, cout, H, W);
     BBBP_CHECK_ARG(x && gy && mask && dw && db && workspace, "conv bwd_weight: null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
     if (B == 0) {
         BBBP_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)cout * cin * 9 * sizeof(float), st));
         BBBP_CHECK_HIP(hipMemsetAsync(db, 0, (size_t)cout * sizeof(float), st));
@@ -977,10 +1008,10 @@ extern "C" int bbbp_conv3x3_relu_pool_bwd_weight(void* stream, const float* x, c
         // second stage (one pair) and, round 4, the wide / deep variant's 64 -> 128 stage (four pairs)
         if (W == 64 && H == 64 && ((cin == 32 && cout == 64) || (cin == 64 && cout == 128)) && (winograd_mask() & 16))
             rc = bbbp_b3_conv2_wgrad(st, x, gy, mask, slab, p.bslab, B, grid, (winograd_mask() & 128) ? ((winograd_mask() & 256) ? 2 : 1) : 0,
-                                     cin, cout, groups);
+                                     prefs.wgrad_beside_encoder, cin, cout, groups);
         else if (W == 32 && H == 32 && cin == 128 && cout == 256 && (winograd_mask() & 16) && (winograd_mask() & 128))
             // the variant's third stage on the structured-sparse form (16 block pairs; a stage = two pooled rows)
-            rc = bbbp_b3_conv2_wgrad(st, x, gy, mask, slab, p.bslab, B, grid, (winograd_mask() & 256) ? 2 : 1, cin, cout, groups, 32);
+            rc = bbbp_b3_conv2_wgrad(st, x, gy, mask, slab, p.bslab, B, grid, (winograd_mask() & 256) ? 2 : 1, prefs.wgrad_beside_encoder, cin, cout, groups, 32);
         else rc = cin == 32 ? launch_wgrad32<64, 32, 64>(p, grid, st)
                : cin == 64 ? launch_wgrad32<64, 64, 128>(p, grid, st) : launch_wgrad32<32, 128, 256>(p, grid, st);
         if (rc) return rc;

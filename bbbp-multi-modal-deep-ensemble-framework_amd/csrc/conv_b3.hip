@@ -18,7 +18,7 @@
 // filter taps and swaps the channel roles, the epilogue stores full-resolution rows.
 #include "common.h"
 #include "bbbp_hip.h"
-#include <stdlib.h>
+#include <limits.h>
 
 namespace {
 
@@ -372,7 +372,7 @@ template <int MODE>
 __global__ __launch_bounds__(256) void conv_b3_probe_kernel(B3Params p) { conv_b3_body<MODE, true, GeomFlagship>(p); }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// Round 4: the FORWARD kernel software-pipelined inside a wave, ONE work-group per CU (g_bbbp_conv2_fwd_pipe: training plans beside an
+// Round 4: the FORWARD kernel software-pipelined inside a wave, ONE work-group per CU (ConvPrefs::conv2_fwd_pipe: training plans beside an
 // encoder chain; BBBP_C2_PIPE=0 / 1 overrides).
 // conv_b3_kernel's waves spend ~40 % of their time in the MFMA block and the rest issuing loads, splitting, writing LDS, waiting at two
 // barriers per stage and in the epilogue; a second work-group on the CU fills those gaps (matrix pipe ~60 % busy).  Here a stage's LDS
@@ -834,7 +834,7 @@ __global__ __launch_bounds__(256) void conv_b3_wgrad_kernel(B3WgradParams p) {
 // Work-group: NW waves = (m-tile 2) x (k-group NW / 2); a stage (one pooled row, as before) is four k-blocks of 32 pixels (upper / lower
 // row x left / right half).  NW = 8: one k-block per wave, two waves per SIMD -- fastest alone (0.236 ms at B = 512 against 0.405 dense), but
 // its 2 x 256 registers per SIMD lane leave nothing for the fingerprint branch's kernels beside it (whole step 2.59 -> 2.67 ms).  NW = 4
-// (what the engine asks for while an encoder chain runs beside the image branch, common.h: g_bbbp_conv_wgrad_beside_encoder;
+// (what the engine asks for while an encoder chain runs beside the image branch, common.h: ConvPrefs::wgrad_beside_encoder;
 // BBBP_C2_WGRAD_SPARSE_WAVES overrides): two k-blocks per wave, one wave of 297 registers per SIMD: 0.26 ms alone, 0.33 in the step
 // (dense: 0.39 / 0.54), whole step 2.59 -> 2.52 ms; the two-branch model without an encoder takes the 8-wave form (1.126 -> 1.046 ms).
 constexpr int ASP_CO = 32 + 8;                  // pooled pixels of one output channel and row (+ 16 B: bank spread), quads in slot order
@@ -1226,13 +1226,13 @@ __global__ __launch_bounds__(256) void conv_b3_wgrad3_kernel(B3Wgrad3Params p) {
 }
 
 template <int MODE, class G>
-int launch_b3(const B3Params& p, hipStream_t st) {
-    static const int probe = [] { const char* e = getenv("BBBP_B3_PROBE"); return e ? atoi(e) : 0; }();
+int launch_b3(const B3Params& p, hipStream_t st, int fwd_pipe = 0) {
+    static const int probe = bbbp_env_int("BBBP_B3_PROBE", 0);
     constexpr bool flagship = G::CIN == 32 && G::COUT == 64 && G::IMGS == 64;
     if constexpr (G::IMGS == 64) {
-        static const int pipe_env = [] { const char* e = getenv("BBBP_C2_PIPE"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-        static const int dpipe_env = [] { const char* e = getenv("BBBP_C2_DGRAD_PIPE"); return e ? (atoi(e) != 0 ? 1 : 0) : 0; }();
-        const int pipe = MODE == B3_FWD ? (pipe_env >= 0 ? pipe_env : g_bbbp_conv2_fwd_pipe) : dpipe_env;
+        static const int pipe_env = bbbp_env_int("BBBP_C2_PIPE", INT_MIN);       // set in the environment (any integer): wins over the caller's choice
+        static const int dpipe_env = bbbp_env_int("BBBP_C2_DGRAD_PIPE", 0);
+        const int pipe = MODE == B3_FWD ? (pipe_env != INT_MIN ? pipe_env : fwd_pipe) : dpipe_env;
         if (pipe && !probe) {
             auto pk = MODE == B3_FWD ? (p.ymask ? conv_b3p_kernel<MODE, G, true> : conv_b3p_kernel<MODE, G, false>) : conv_b3p_kernel<MODE, G, false>;
             constexpr size_t plds = (size_t)2 * (3 * (256 / G::IMGS + 2) * (G::IMGS + 2) * CH + WSTAGE) * 2;
@@ -1255,7 +1255,7 @@ int launch_b3(const B3Params& p, hipStream_t st) {
     { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(kernel), lds); if (rc_) return rc_; }
     constexpr int NMB = (MODE == B3_FWD ? G::COUT : G::CIN) / 32;
     const int nwork = p.B * (IMGL / RL) * NMB;
-    static const int per_cu = [] { const char* e = getenv("BBBP_B3_PER_CU"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 2 ? 2 : v); }();
+    static const int per_cu = clampi(bbbp_env_int("BBBP_B3_PER_CU", 2), 1, 2);
     int grid = bbbp_num_cus() * per_cu;
     if (grid >= 8 * NMB) grid -= grid % (8 * NMB);
     if (grid > nwork) grid = nwork - nwork % NMB;
@@ -1281,20 +1281,17 @@ size_t bbbp_b3_workspace_bytes() { return bbbp_b3_workspace_bytes(32, 64); }
 // (<= 224 registers), the image branch is the longer pole of the backward pass, and equal priority (3: the older conv waves then go first)
 // hands the arbitration back to it.
 static int conv_bwd_prio() {
-    static const int v = [] { const char* e = getenv("BBBP_CONV_BWD_PRIO"); const int x = e ? atoi(e) : 0; return x < 0 ? 0 : (x > 3 ? 3 : x); }();
+    static const int v = clampi(bbbp_env_int("BBBP_CONV_BWD_PRIO", 0), 0, 3);
     return v;
 }
 
-int bbbp_b3_conv_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int cin, int cout, void* workspace) {
+int bbbp_b3_conv_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int cin, int cout, void* workspace, int pipe) {
     hipLaunchKernelGGL(b3_prep_kernel, dim3(cin * cout >= 64 * 128 ? 288 : 72), dim3(256), 0, st, w, static_cast<uint16_t*>(workspace), B3_FWD, cin, cout);
     BBBP_CHECK_LAUNCH();
     B3Params p{x, nullptr, static_cast<const uint16_t*>(workspace), bias, y, mask, B, 0};
-    if (cin == 32) return launch_b3<B3_FWD, GeomFlagship>(p, st);
-    if (cin == 64) return launch_b3<B3_FWD, B3Geom<64, 128, 64>>(p, st);
-    return launch_b3<B3_FWD, B3Geom<128, 256, 32>>(p, st);
-}
-int bbbp_b3_conv2_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, void* workspace) {
-    return bbbp_b3_conv_fwd(st, x, w, bias, y, mask, B, 32, 64, workspace);
+    if (cin == 32) return launch_b3<B3_FWD, GeomFlagship>(p, st, pipe);
+    if (cin == 64) return launch_b3<B3_FWD, B3Geom<64, 128, 64>>(p, st, pipe);
+    return launch_b3<B3_FWD, B3Geom<128, 256, 32>>(p, st, pipe);
 }
 
 int bbbp_b3_conv_dgrad(hipStream_t st, const float* gy, const uint8_t* gmask, const float* w, float* dx, int B, int cin, int cout, void* workspace) {
@@ -1305,9 +1302,6 @@ int bbbp_b3_conv_dgrad(hipStream_t st, const float* gy, const uint8_t* gmask, co
     if (cin == 64) return launch_b3<B3_DGRAD, B3Geom<64, 128, 64>>(p, st);
     return launch_b3<B3_DGRAD, B3Geom<128, 256, 32>>(p, st);
 }
-int bbbp_b3_conv2_dgrad(hipStream_t st, const float* gy, const uint8_t* gmask, const float* w, float* dx, int B, void* workspace) {
-    return bbbp_b3_conv_dgrad(st, gy, gmask, w, dx, B, 32, 64, workspace);
-}
 
 extern "C" int bbbp_conv_b3_phases(unsigned long long* phases4) {
     BBBP_CHECK_ARG(phases4, "conv_b3_phases: null pointer");
@@ -1317,12 +1311,12 @@ extern "C" int bbbp_conv_b3_phases(unsigned long long* phases4) {
 
 // grid work-groups, each writes slab[g][64][288] and bslab[g][64] (conv.hip: conv_wgrad32_reduce_kernel finishes)
 int bbbp_b3_conv2_wgrad(hipStream_t st, const float* x, const float* gy, const uint8_t* mask, float* slab, float* bslab, int B, int grid, int form,
-                        int cin_total, int cout_total, int groups, int map) {
+                        int beside_encoder, int cin_total, int cout_total, int groups, int map) {
     B3WgradParams p{x, gy, mask, slab, bslab, B, conv_bwd_prio(), cin_total, cout_total, groups > 0 ? groups : grid};
     BBBP_CHECK_ARG(map == 64 || (map == 32 && form != 0), "b3 weight gradient: 64 x 64 maps (any form) or 32 x 32 maps (structured-sparse forms), got %d / form %d", map, form);
     const bool sparse = form != 0;
-    static const int waves_env = [] { const char* e = getenv("BBBP_C2_WGRAD_SPARSE_WAVES"); return e ? atoi(e) : 0; }();
-    const int waves = waves_env ? waves_env : ((form == 2 || g_bbbp_conv_wgrad_beside_encoder) ? 4 : 8);
+    static const int waves_env = bbbp_env_int("BBBP_C2_WGRAD_SPARSE_WAVES", 0);
+    const int waves = waves_env ? waves_env : ((form == 2 || beside_encoder) ? 4 : 8);
     if (map == 32) {
         if (waves == 8) {
             { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(conv_b3_wgrad_sp_kernel<8, 32>), WGS_LDS_BYTES); if (rc_) return rc_; }

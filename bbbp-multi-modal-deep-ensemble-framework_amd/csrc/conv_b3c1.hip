@@ -447,15 +447,15 @@ __global__ __launch_bounds__(256, 2) void conv1_b3p_fwd_kernel(C1Params p) {
 // workspace: WFRAG_WORDS uint32 of pre-split filter fragments (9 KB)
 size_t bbbp_b3_conv1_fwd_workspace_bytes() { return (size_t)WFRAG_WORDS * sizeof(uint32_t); }
 
-int bbbp_b3_conv1_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, void* workspace) {
+int bbbp_b3_conv1_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, void* workspace, int want_per_cu) {
     uint32_t* wf = static_cast<uint32_t*>(workspace);
-    static const int pipe = [] { const char* e = getenv("BBBP_C1_PIPE"); return e ? atoi(e) : 1; }();     // round 4: the software-pipelined form (0: round 3's phase-by-phase kernel)
+    static const int pipe = bbbp_env_int("BBBP_C1_PIPE", 1);     // round 4: the software-pipelined form (0: round 3's phase-by-phase kernel)
     hipLaunchKernelGGL(c1_prep_kernel, dim3(3), dim3(256), 0, st, w, wf, pipe ? bias : nullptr);
     BBBP_CHECK_LAUNCH();
-    static const int exp_bits = [] { const char* e = getenv("BBBP_C1_EXP"); return e ? atoi(e) : 0; }();
+    static const int exp_bits = bbbp_env_int("BBBP_C1_EXP", 0);
     C1Params p{x, wf, bias, y, mask, B, exp_bits};
-    static const int per_cu_env = [] { const char* e = getenv("BBBP_C1_PER_CU"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
-    const int per_cu = g_bbbp_conv1_fwd_per_cu > 0 ? g_bbbp_conv1_fwd_per_cu : per_cu_env;
+    static const int per_cu_env = clampi(bbbp_env_int("BBBP_C1_PER_CU", 2), 1, 4);
+    const int per_cu = want_per_cu > 0 ? want_per_cu : per_cu_env;
     const int nstrips = B * (W1 / R1);
     int grid = bbbp_num_cus() * per_cu;
     if (grid >= 8) grid -= grid % 8;

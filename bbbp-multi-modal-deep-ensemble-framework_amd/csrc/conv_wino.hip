@@ -293,12 +293,8 @@ __global__ void wino_prep_kernel(const float* w, float* u, int mode) {
 template <int MODE>
 int launch_wino(const WinoParams& p, hipStream_t st) {
     using C = WinoCfg<MODE>;
-    static const int cu_cap = [] {
-        const char* e = getenv(MODE == W_FWD ? "BBBP_WINO_CUS_FWD" : "BBBP_WINO_CUS_DGRAD");
-        if (!e) e = getenv("BBBP_WINO_CUS");
-        return e ? atoi(e) : 0;
-    }();
-    static const int probe = [] { const char* e = getenv("BBBP_WINO_PROBE"); return e ? atoi(e) : 0; }();
+    static const int cu_cap = bbbp_env_int(MODE == W_FWD ? "BBBP_WINO_CUS_FWD" : "BBBP_WINO_CUS_DGRAD", bbbp_env_int("BBBP_WINO_CUS", 0));
+    static const int probe = bbbp_env_int("BBBP_WINO_PROBE", 0);
     auto kernel = probe ? wino_conv_probe_kernel<MODE> : wino_conv_kernel<MODE>;
     { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(kernel), (size_t)C::LDS_BYTES); if (rc_) return rc_; }
     const int nwork = p.B * (IMG / 8) * C::NCB;
@@ -321,7 +317,7 @@ int bbbp_wino_conv2_fwd(hipStream_t st, const float* x, const float* w, const fl
                         float* workspace) {
     hipLaunchKernelGGL(wino_prep_kernel, dim3(128), dim3(256), 0, st, w, workspace, W_FWD);
     BBBP_CHECK_LAUNCH();
-    static const int pairing = [] { const char* e = getenv("BBBP_WINO_XCD_PAIRS"); return e ? atoi(e) : 1; }();
+    static const int pairing = bbbp_env_int("BBBP_WINO_XCD_PAIRS", 1);
     WinoParams p{x, nullptr, workspace, bias, y, mask, B, pairing};
     return launch_wino<W_FWD>(p, st);
 }

@@ -89,31 +89,22 @@ struct Plan {
 };
 
 // Fused attention for many small heads (attention.hip); 0 selects the GEMM + softmax schedule with materialised probabilities.
-int g_flash_attention = -1;
+Knob g_flash_attention{"BBBP_FLASH_ATTENTION", 13, [](int v) { return v & 31; }};
 
 // out_proj folded into the value projection for one-head layers (fold.hip): two launches fewer per layer on the encoder's forward and
 // backward chains.  A bit mask (default 3): bit 0 the launch-per-op schedule with materialised probabilities; bit 1 also the
 // forward-only split-bf16 attention kernel of 2048+ row plans -- there the encoder alone gets faster (1.88 -> 1.76 ms at B = 4096); beside the
 // conv kernels on a second stream the step measured slower with it (7.54 -> 7.79 ms; profiles/r03_fold_outproj.txt), which is one of the
 // reasons those plans run on one stream (forward_enqueue).  BBBP_FOLD_OUTPROJ=0 / bbbp_set_fold_outproj(0) keep the reference's operation order.
-int g_fold_outproj = -1;
-int g_fused_encoder = -1;              // bit 0: row-fused kernels (opt-in); bits 1 / 2: sliced persistent forward / backward for small batches
-int fold_outproj_on() {
-    if (g_fold_outproj < 0) { const char* e = getenv("BBBP_FOLD_OUTPROJ"); g_fold_outproj = e ? (atoi(e) & 3) : 3; }
-    return g_fold_outproj;
-}
+Knob g_fold_outproj{"BBBP_FOLD_OUTPROJ", 3, [](int v) { return v & 3; }};
+Knob g_fused_encoder{"BBBP_FUSED_ENCODER", 0, [](int v) { return v & 7; }};      // bit 0: row-fused kernels (opt-in); bits 1 / 2: sliced persistent forward / backward for small batches
+int fold_outproj_on() { return g_fold_outproj.get(); }
 // LayerNorm absorbed by the consuming Linear (gemm.hip: gemm_direct_lna_kernel).  Default OFF: measured SLOWER inside the B = 512 step
 // (profiles/r04_ln_absorb.txt: the encoder's forward chain 0.826 -> 0.857 ms on the device timeline, step 2.487 -> 2.504 ms -- the absorbing
 // GEMMs pay more for their row statistics / gamma / beta work beside the conv kernels than the twelve LayerNorm launches cost).
-int g_ln_absorb = -1;
-int ln_absorb_on() {
-    if (g_ln_absorb < 0) { const char* e = getenv("BBBP_LN_ABSORB"); g_ln_absorb = e ? (atoi(e) != 0) : 0; }
-    return g_ln_absorb;
-}
-int fused_encoder_mode() {
-    if (g_fused_encoder < 0) { const char* e = getenv("BBBP_FUSED_ENCODER"); g_fused_encoder = e ? atoi(e) & 7 : 0; }
-    return g_fused_encoder;
-}
+Knob g_ln_absorb{"BBBP_LN_ABSORB", 0, knob_bool};
+int ln_absorb_on() { return g_ln_absorb.get(); }
+int fused_encoder_mode() { return g_fused_encoder.get(); }
 
 int make_plan(const bbbp_mixed_desc* d, Plan* p) {
     BBBP_CHECK_ARG(d, "null desc");
@@ -134,15 +125,15 @@ int make_plan(const bbbp_mixed_desc* d, Plan* p) {
     p->world = p->exact && d->world > 1 ? d->world : 1; p->rank = p->exact ? d->rank : 0;
     BBBP_CHECK_ARG(p->rank >= 0 && p->rank < p->world, "rank %d of %d", d->rank, p->world);
     p->Bg = (size_t)p->B * p->world;
-    if (g_flash_attention < 0) { const char* e = getenv("BBBP_FLASH_ATTENTION"); g_flash_attention = e ? atoi(e) & 31 : 13; }
+    const int flash_mask = g_flash_attention.get();
     // bit 3 (round 3): forward-only plans of 2048 rows and more with a wide head run the split-bf16 attention kernel (attention_b3.hip);
     // bit 4: that kernel from 256 rows on (tests; below ~2048 rows its 128-query work-groups leave most CUs idle)
-    p->attn_b3 = (g_flash_attention & 8) && p->inference && p->L > 0 && p->B >= ((g_flash_attention & 16) ? 256 : 2048) &&
+    p->attn_b3 = (flash_mask & 8) && p->inference && p->L > 0 && p->B >= ((flash_mask & 16) ? 256 : 2048) &&
                  bbbp_attn_b3_supported(p->B, p->NH, p->D) && !p->exact;
     // bit 2: the wide-head kernel where it wins -- forward-only plans of 2048 rows and more (256+ work-groups fill the chip and the
     // [B, B] probability tensor, 67 MB per layer at B = 4096, is never written): config 5 8.28 -> 7.84 ms per 4096 molecules
-    const bool wide = (g_flash_attention & 2) || ((g_flash_attention & 4) && p->inference && p->B >= 2048);
-    p->flash = p->L > 0 && !p->exact && (p->attn_b3 || ((g_flash_attention & 1) && bbbp_attn_small_supported(p->B, p->NH, p->D)) ||
+    const bool wide = (flash_mask & 2) || ((flash_mask & 4) && p->inference && p->B >= 2048);
+    p->flash = p->L > 0 && !p->exact && (p->attn_b3 || ((flash_mask & 1) && bbbp_attn_small_supported(p->B, p->NH, p->D)) ||
                             (wide && bbbp_attn_wide_supported(p->B, p->NH, p->D)));
     // the fused / sliced encoder schedules (opt-in) and the fused attention kernels keep the reference's operation order
     // (the forward-only split-bf16 attention kernel reads VW where it read V: its rows of P sum to one, so bo rides in b')
@@ -243,6 +234,8 @@ int run_collective(const bbbp_mixed_desc* d, int op, int what, int layer, size_t
     return BBBP_OK;
 }
 
+#define TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+
 struct Ctx {
     hipStream_t st;
     char* ws;
@@ -262,36 +255,43 @@ struct Ctx {
 constexpr int NEV = 32;
 struct SideStream { hipStream_t s = nullptr; hipStream_t leaf = nullptr; hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr;
                     hipEvent_t ev[NEV]; int next = 0; };
-SideStream g_side[64];
-// recorded on the caller's stream when the image-FC weight gradient (33.5 MB of the 53.9 MB of gradients at F = 167) is
-// final, i.e. after the first GEMM of the image branch's backward: a data-parallel caller can start reducing that bucket
-// while the remaining ~2 ms of the backward pass run (bbbp_mixed_backward_wait_bucket)
-hipEvent_t g_bucket_event[64];
-hipEvent_t g_bucket0_released[64];      // recorded after the last READ of the image-FC weight in a backward pass ...
-bool g_release_events = false;          // ... only on request (bbbp_set_release_events): one more record on the image branch's stream
-bool g_bucket0_released_recorded[64];
-bool g_bucket_recorded[64];
-// bucket 1: everything except the image-FC weight and the four conv tensors -- final when the fingerprint branch's chain
-// and all weight-gradient leaves are done (~0.25 ms before the image branch's last kernel); recorded on the leaf stream
-hipEvent_t g_bucket1_event[64];
-bool g_bucket1_recorded[64];
-// buckets 2 + l: the twelve tensors of encoder layer l (one contiguous slice in named_parameters order) -- final when that
-// layer's weight-gradient leaves are, layer L-1 first.  At F = 2048 these are 100 MB each and 94 % of all gradient bytes.
-hipEvent_t g_layer_event[64][32];
-bool g_layer_recorded[64][32];
-int record_layer_bucket(hipStream_t leaf, int layer) {
+// A gradient bucket's event and whether the most recent backward pass on the device recorded it (bbbp_mixed_backward_wait_bucket)
+struct BucketEvent { hipEvent_t ev = nullptr; bool recorded = false; };
+struct DeviceState {
+    SideStream side;
+    // recorded on the caller's stream when the image-FC weight gradient (33.5 MB of the 53.9 MB of gradients at F = 167) is
+    // final, i.e. after the first GEMM of the image branch's backward: a data-parallel caller can start reducing that bucket
+    // while the remaining ~2 ms of the backward pass run
+    BucketEvent bucket0;
+    BucketEvent bucket0_released;      // recorded after the last READ of the image-FC weight in a backward pass, only on request (g_release_events)
+    // bucket 1: everything except the image-FC weight and the four conv tensors -- final when the fingerprint branch's chain
+    // and all weight-gradient leaves are done (~0.25 ms before the image branch's last kernel); recorded on the leaf stream
+    BucketEvent bucket1;
+    // buckets 2 + l: the twelve tensors of encoder layer l (one contiguous slice in named_parameters order) -- final when that
+    // layer's weight-gradient leaves are, layer L-1 first.  At F = 2048 these are 100 MB each and 94 % of all gradient bytes.
+    BucketEvent layer[32];
+};
+DeviceState g_device[64];
+bool g_release_events = false;          // bbbp_set_release_events: one more record on the image branch's stream
+// the current device's record (and its index); nullptr for a device beyond the table: the callers skip their events then, or report it
+int device_state(DeviceState** out, int* dev_out = nullptr) {
     int dev = 0;
     BBBP_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || layer < 0 || layer >= 32) return BBBP_OK;
-    if (!g_layer_event[dev][layer]) BBBP_CHECK_HIP(hipEventCreateWithFlags(&g_layer_event[dev][layer], hipEventDisableTiming));
+    if (dev_out) *dev_out = dev;
+    *out = (dev >= 0 && dev < 64) ? &g_device[dev] : nullptr;
+    return BBBP_OK;
+}
+// record bucket `b` (created at first use) as final at this point of `st`
+int record_bucket(BucketEvent& b, hipStream_t st) {
+    if (!b.ev) BBBP_CHECK_HIP(hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(leaf, &cap);
-    g_layer_recorded[dev][layer] = cap == hipStreamCaptureStatusNone;       // an event recorded inside a graph capture means nothing outside it
-    if (g_layer_recorded[dev][layer]) BBBP_CHECK_HIP(hipEventRecord(g_layer_event[dev][layer], leaf));
+    (void)hipStreamIsCapturing(st, &cap);
+    b.recorded = cap == hipStreamCaptureStatusNone;       // an event recorded inside a graph capture means nothing outside it
+    if (b.recorded) BBBP_CHECK_HIP(hipEventRecord(b.ev, st));
     return BBBP_OK;
 }
 int g_overlap = -1;
-int g_fused_head_bwd = -1;
+Knob g_fused_head_bwd{"BBBP_FUSED_HEAD_BWD", 1, knob_bool};
 // Row-local stretches of an encoder layer as single launches (encoder.hip) instead of 6 + 6 per layer: BBBP_FUSED_ENCODER=1 /
 // bbbp_set_fused_encoder(1).  Correct (tests compare the two schedules) but OFF by default: a 16-row work-group streams a whole
 // layer's weights by itself (3.2 MB forward) through ONE wave per SIMD, which is bound by load latency -- 176 / 289 us per
@@ -304,23 +304,21 @@ bool sliced_encoder(const Plan& p, int bit = 2) {
     return (fused_encoder_mode() & bit) && p.L > 0 && !p.flash && !p.exact && bbbp_enc_sliced_supported(p.B, p.F, p.NH, p.DFF, p.L);
 }
 bool overlap_enabled() {
-    if (g_overlap < 0) { const char* e = getenv("BBBP_SINGLE_STREAM"); g_overlap = (e && e[0] == '1') ? 0 : 1; }
+    if (g_overlap < 0) { const char* e = bbbp_env("BBBP_SINGLE_STREAM"); g_overlap = (e && e[0] == '1') ? 0 : 1; }
     return g_overlap == 1;
 }
 int reserved_cus() {
-    static int v = -1;
     // default 0: measured (tools/exp_overlap.py, bench sweeps) the reservation costs the conv kernels what it gives
-    if (v < 0) { const char* e = getenv("BBBP_RESERVED_CUS"); v = e ? atoi(e) : 0; if (v < 0 || v > 128) v = 0; }
-    return v;
+    static const int v = bbbp_env_int("BBBP_RESERVED_CUS", 0);
+    return (v < 0 || v > 128) ? 0 : v;
 }
 // scoped CU partition (common.h): conv grids leave `reserved_cus()` CUs to the side stream's small kernels
 // The Winograd conv2 kernels take a whole CU each (496 registers per lane, 110-154 KB LDS): nothing of the side stream
 // can start beside them, so while the branches overlap their grids leave `wino_side_cus()` CUs entirely to the side
 // stream.  Measured (tools/exp_wino.sh, ms/step): 256 CUs 3.65, 224 3.51, 192 3.42, 160 3.51, 128 3.76.
 int wino_side_cus() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("BBBP_WINO_SIDE_CUS"); v = e ? atoi(e) : 64; if (v < 0 || v > 192) v = 64; }
-    return v;
+    static const int v = bbbp_env_int("BBBP_WINO_SIDE_CUS", 64);
+    return (v < 0 || v > 192) ? 64 : v;
 }
 struct Partition {
     bool on, side;
@@ -334,10 +332,10 @@ struct Partition {
     }
 };
 int get_side(SideStream** out) {
-    int dev = 0;
-    BBBP_CHECK_HIP(hipGetDevice(&dev));
-    BBBP_CHECK_ARG(dev >= 0 && dev < 64, "device index %d", dev);
-    SideStream& ss = g_side[dev];
+    DeviceState* ds = nullptr; int dev = 0;
+    TRY(device_state(&ds, &dev));
+    BBBP_CHECK_ARG(ds, "device index %d", dev);
+    SideStream& ss = ds->side;
     if (!ss.s) {
         // (queue priorities -- hipStreamCreateWithPriority, chain stream highest / leaf stream lowest -- were measured on the headline step:
         // 2.497 ms default, 2.501 / 2.508 with them, profiles/r03_rebalance.txt; the wave priority set inside the kernels is what matters)
@@ -370,8 +368,6 @@ int join_side(hipStream_t main, SideStream* ss) {
     BBBP_CHECK_HIP(hipStreamWaitEvent(main, ss->join, 0));
     return BBBP_OK;
 }
-
-#define TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
 // ---- optional per-section timing with HIP events on the launch stream (bench.py roofline leg) ----
 enum { SEC_CONV1_FWD = 0, SEC_CONV2_FWD, SEC_IMGFC_FWD, SEC_ENCODER_FWD, SEC_HEAD_FWD, SEC_HEAD_BWD, SEC_IMGFC_BWD,
@@ -436,7 +432,7 @@ bbbp_gemm_desc gemm_desc(int transA, int transB, int M, int N, int K, float alph
 // dW[N,K] = dy[M,N]^T x[M,K] and db[N] = column sums of dy: ONE launch when the product takes the small-GEMM path (the bias
 // gradient rides through the same MFMAs as a virtual all-ones column of x), else the GEMM plus a column-sum kernel
 int linear_bwd_weight_bias(const Ctx& c, const float* dy, int lddy, const float* x, int ldx, float* dW, float* db, int M, int N, int K) {
-    static const int fold = [] { const char* e = getenv("BBBP_FOLD_BIAS_GRAD"); return e ? atoi(e) : 1; }();
+    static const int fold = bbbp_env_int("BBBP_FOLD_BIAS_GRAD", 1);
     if (fold && bbbp_gemm_folds_asum(N, K, M, 1)) {
         bbbp_gemm_desc g = gemm_desc(1, 0, N, K, M, 1.f, dy, lddy, x, ldx, dW, K, 1, 0, 0, 0);
         g.asum = db;
@@ -505,9 +501,9 @@ long g_graph_replays = 0, g_graph_captures = 0;
 // streams (whole step, B = 512: 3.67 ms eager, 4.50 ms replayed; the host loop is not shorter either, hipGraphLaunch of
 // a 260-node graph costs about what the eager enqueue does).  Kept as an opt-in (BBBP_GRAPHS=1 / bbbp_set_graphs) with a
 // bit-exactness test, for runtimes where graph launch is cheaper.
-int g_graphs_mode = -1;
+int g_graphs_mode = -1;          // BBBP_GRAPHS is taken as it stands; the setter stores 0 / 1
 int graphs_mode() {
-    if (g_graphs_mode < 0) { const char* e = getenv("BBBP_GRAPHS"); g_graphs_mode = e ? atoi(e) : 0; }
+    if (g_graphs_mode < 0) g_graphs_mode = bbbp_env_int("BBBP_GRAPHS", 0);
     return g_graphs_mode;
 }
 uint64_t hash_ptrs(const void* const* a, int n, uint64_t h = 1469598103934665603ull) {
@@ -535,31 +531,14 @@ int graph_lookup(const GraphKey& k, GraphEntry** slot) {
 
 // Branch overlap on/off at run time (default on; env BBBP_SINGLE_STREAM=1 starts with it off).  Returns the old value.
 extern "C" int bbbp_set_fused_head_bwd(int on) {
-    const int prev = g_fused_head_bwd > 0 ? 1 : 0;
-    g_fused_head_bwd = on ? 1 : 0;
+    const int prev = g_fused_head_bwd.v > 0 ? 1 : 0;          // (0 until the knob has been read or set, as it always was)
+    g_fused_head_bwd.v = on ? 1 : 0;
     return prev;
 }
-
-extern "C" int bbbp_set_fused_encoder(int mode) {
-    const int prev = fused_encoder_mode();
-    g_fused_encoder = mode & 7;
-    return prev;
-}
-
-extern "C" int bbbp_set_fold_outproj(int on) {
-    const int prev = fold_outproj_on();
-    g_fold_outproj = on & 3;
-    return prev;
-}
-
-extern "C" int bbbp_set_flash_attention(int on) {
-    if (g_flash_attention < 0) { const char* e = getenv("BBBP_FLASH_ATTENTION"); g_flash_attention = e ? atoi(e) & 31 : 13; }
-    const int prev = g_flash_attention;
-    g_flash_attention = on & 31;
-    return prev;
-}
-
-extern "C" int bbbp_set_ln_absorb(int on) { const int prev = ln_absorb_on(); g_ln_absorb = on ? 1 : 0; return prev; }
+extern "C" int bbbp_set_fused_encoder(int mode) { return g_fused_encoder.set(mode); }
+extern "C" int bbbp_set_fold_outproj(int on) { return g_fold_outproj.set(on); }
+extern "C" int bbbp_set_flash_attention(int on) { return g_flash_attention.set(on); }
+extern "C" int bbbp_set_ln_absorb(int on) { return g_ln_absorb.set(on); }
 
 extern "C" int bbbp_set_overlap(int on) { int old = overlap_enabled() ? 1 : 0; g_overlap = on ? 1 : 0; return old; }
 
@@ -605,17 +584,10 @@ extern "C" size_t bbbp_mixed_workspace_bytes(const bbbp_mixed_desc* d) {
     return p.total;
 }
 
-static int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const float* const* P, float* const* bn_running,
-                           const float* fingerprint, const float* image, float* out, void* workspace,
-                           size_t workspace_bytes) {
-    Plan plan;
-    TRY(make_plan(d, &plan));
+// `plan`: made from `d` and checked against the arguments and the workspace size by the caller (bbbp_mixed_forward)
+static int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& plan, const float* const* P, float* const* bn_running,
+                           const float* fingerprint, const float* image, float* out, void* workspace) {
     SeedScope seed_scope(reinterpret_cast<const unsigned long long*>(static_cast<char*>(workspace) + plan.seed_slot));
-    BBBP_CHECK_ARG(P && fingerprint && image && out && workspace && bn_running, "mixed_forward: null pointer");
-    if (workspace_bytes < plan.total) {
-        bbbp_set_error("mixed_forward: workspace %zu < %zu bytes", workspace_bytes, plan.total);
-        return BBBP_ERR_WORKSPACE;
-    }
     Ctx c{static_cast<hipStream_t>(stream), static_cast<char*>(workspace), &plan};
     const PIdx ix(d);
     // a deferred optimizer slice that is NOT this model's image-FC weight (another model's step, another tensor): wait before anything runs
@@ -632,7 +604,7 @@ static int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const float* 
     // pipe, so the second stream only time-shares it -- measured equal on one box (6.66 / 6.83 ms overlapped, 6.59 / 6.85 one stream) and
     // WORSE than the sum of the branches on others (7.6 ms against 5.29 + 1.85 + 0.06; profiles/r03_config5_streams.txt); alone, the
     // encoder also takes the out_proj fold's gain (fold mask bit 1).  BBBP_SCREEN_OVERLAP=1 restores the two-stream schedule.
-    static const bool screen_overlap = [] { const char* e = getenv("BBBP_SCREEN_OVERLAP"); return e && atoi(e) != 0; }();
+    static const bool screen_overlap = bbbp_env_int("BBBP_SCREEN_OVERLAP", 0) != 0;
     if (overlap_enabled() && (screen_overlap || !plan.attn_b3)) {
         TRY(get_side(&ss));
         TRY(fork_side(c.st, ss));
@@ -647,31 +619,29 @@ static int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const float* 
     float* pool1 = c.f(plan.pool1); float* pool2 = c.f(plan.pool2);
     {
         Section s1(c.st, SEC_CONV1_FWD);
-        // beside a training step's encoder chain the f32 form stays (common.h: g_bbbp_conv1_fwd_f32); screening batches, eval loops and
+        // beside a training step's encoder chain the f32 form stays (common.h: ConvPrefs::conv1_fwd_f32); screening batches, eval loops and
         // the encoder-less two-branch model take the split-bf16 form when the conv mask selects it (bit 6, default)
         // (the rule looks at the plan only, not at the stream mode: one stream or three give bit-identical steps)
         // round 4: training steps run the software-pipelined split-bf16 kernel (conv_b3c1.hip) too, ONE work-group per CU beside the chain
         // (BBBP_C1_TRAIN=0: the f32 kernel of rounds 1-3 there; 2: two work-groups per CU, measured slower for the step)
-        static const int c1_train = [] { const char* e = getenv("BBBP_C1_TRAIN"); return e ? atoi(e) : 1; }();      // default 1: step 2.517 -> 2.487 ms (profiles/r04_c1_pipe.txt)
+        static const int c1_train = bbbp_env_int("BBBP_C1_TRAIN", 1);      // default 1: step 2.517 -> 2.487 ms (profiles/r04_c1_pipe.txt)
         const bool beside_chain = !plan.inference && plan.L > 0;
-        g_bbbp_conv1_fwd_f32 = (beside_chain && !c1_train) ? 1 : 0;
-        g_bbbp_conv1_fwd_per_cu = (beside_chain && c1_train) ? (c1_train >= 2 ? 2 : 1) : 0;      // BBBP_C1_TRAIN=2: two work-groups per CU there too
-        const int rc1 = bbbp_conv3x3_relu_pool_fwd(c.st, image, P[ix.c1_w()], P[ix.c1_b()], pool1, plan.inference ? nullptr : c.u8(plan.mask1), B, 3, C1, IMG, IMG,
-                                                   c.scratch(), c.scratch_bytes());
-        g_bbbp_conv1_fwd_f32 = 0; g_bbbp_conv1_fwd_per_cu = 0;
-        TRY(rc1);
+        ConvPrefs prefs;
+        prefs.conv1_fwd_f32 = (beside_chain && !c1_train) ? 1 : 0;
+        prefs.conv1_fwd_per_cu = (beside_chain && c1_train) ? (c1_train >= 2 ? 2 : 1) : 0;      // BBBP_C1_TRAIN=2: two work-groups per CU there too
+        TRY(conv3x3_relu_pool_fwd(c.st, image, P[ix.c1_w()], P[ix.c1_b()], pool1, plan.inference ? nullptr : c.u8(plan.mask1), B, 3, C1, IMG, IMG,
+                                  c.scratch(), c.scratch_bytes(), prefs));
     }
     {
         Section s2(c.st, SEC_CONV2_FWD);
         // round 4: beside a training step's encoder chain the software-pipelined one-work-group-per-CU kernel (conv_b3.hip): 0.40 instead of
         // 0.387 ms alone, but the chain -- the forward half's critical path -- keeps three quarters of every SIMD: step 2.41 -> 2.34 ms
         // (profiles/r04_conv2_pipe.txt).  BBBP_C2_TRAIN=0: the two-work-group kernel there too.  Bit-identical outputs either way.
-        static const int c2_train = [] { const char* e = getenv("BBBP_C2_TRAIN"); return e ? atoi(e) : 1; }();
-        g_bbbp_conv2_fwd_pipe = (!plan.inference && plan.L > 0 && c2_train) ? 1 : 0;
-        const int rc2 = bbbp_conv3x3_relu_pool_fwd(c.st, pool1, P[ix.c2_w()], P[ix.c2_b()], pool2, plan.inference ? nullptr : c.u8(plan.mask2), B, C1, C2, IMG / 2,
-                                                   IMG / 2, c.scratch(), c.scratch_bytes());
-        g_bbbp_conv2_fwd_pipe = 0;
-        TRY(rc2);
+        static const int c2_train = bbbp_env_int("BBBP_C2_TRAIN", 1);
+        ConvPrefs prefs;
+        prefs.conv2_fwd_pipe = (!plan.inference && plan.L > 0 && c2_train) ? 1 : 0;
+        TRY(conv3x3_relu_pool_fwd(c.st, pool1, P[ix.c2_w()], P[ix.c2_b()], pool2, plan.inference ? nullptr : c.u8(plan.mask2), B, C1, C2, IMG / 2,
+                                  IMG / 2, c.scratch(), c.scratch_bytes(), prefs));
     }
     {
         Section s3(c.st, SEC_IMGFC_FWD);
@@ -811,7 +781,7 @@ static int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const float* 
         // OPT-IN (BBBP_FUSED_LINEAR_LN=1), measured slower at B = 512: the 11-wave work-groups need three wave slots on three SIMDs of a CU
         // beside the resident conv work-groups (encoder forward 0.98 -> 1.15 ms in the step, 0.58 -> 0.60 alone); linear2 -> norm2 is never
         // fused (one wave per tile walking K = 2048 alone: 90 us against 22 + 4)
-        static const bool ln_opt_in = [] { const char* e = getenv("BBBP_FUSED_LINEAR_LN"); return e && atoi(e) != 0; }();
+        static const bool ln_opt_in = bbbp_env_int("BBBP_FUSED_LINEAR_LN", 0) != 0;
         const bool ln_fused = !plan.fold && ln_opt_in && bbbp_linear_layernorm_supported(B, F, F) && F <= 512;
         if (ln_fused) {
             TRY(bbbp_linear_layernorm_fwd(ce.st, ctx, F, P[ix.layer(l, L_OUTW)], P[ix.layer(l, L_OUTB)], x, F, z1, F, y1, F, P[ix.layer(l, L_N1W)],
@@ -886,7 +856,7 @@ static int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const float* 
     part.reset();
     Section sec_head(c.st, SEC_HEAD_FWD);
 
-    static const int fused_head = [] { const char* e = getenv("BBBP_FUSED_HEAD"); return e ? atoi(e) : 1; }();
+    static const int fused_head = bbbp_env_int("BBBP_FUSED_HEAD", 1);
     BBBP_CHECK_ARG(!plan.exact || (fused_head && NHEADS_FUSION == 4), "the exact-global-batch mode needs the fused head (BBBP_FUSED_HEAD=1)");
     if (fused_head && NHEADS_FUSION == 4) {
         // fusion block + head in two launches (head.hip); with torch.cat fusion the first launch starts at fc.0
@@ -932,19 +902,14 @@ static int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const float* 
     return BBBP_OK;
 }
 
-static int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const float* const* P, float* const* G,
-                            const float* fingerprint, const float* image, const float* dout, void* workspace,
-                            size_t workspace_bytes) {
-    Plan plan;
-    TRY(make_plan(d, &plan));
+// `plan`: as for forward_enqueue (bbbp_mixed_backward)
+static int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& plan, const float* const* P, float* const* G,
+                            const float* fingerprint, const float* image, const float* dout, void* workspace) {
     SeedScope seed_scope(reinterpret_cast<const unsigned long long*>(static_cast<char*>(workspace) + plan.seed_slot));
-    BBBP_CHECK_ARG(P && G && fingerprint && image && dout && workspace, "mixed_backward: null pointer");
     BBBP_CHECK_ARG(!plan.inference, "mixed_backward: the forward call used an inference workspace (desc.inference = 1)");
     (void)bbbp_param_wait(static_cast<hipStream_t>(stream), nullptr);      // (a deferred optimizer slice: normally consumed by the forward pass already)
-    if (workspace_bytes < plan.total) {
-        bbbp_set_error("mixed_backward: workspace %zu < %zu bytes", workspace_bytes, plan.total);
-        return BBBP_ERR_WORKSPACE;
-    }
+    DeviceState* ds = nullptr;          // this device's gradient-bucket events
+    TRY(device_state(&ds));
     // Three streams: `c` (caller's stream) carries the head, the fusion block and the image branch; `ce` carries the
     // fingerprint branch's dependency chain (dy -> dx through the encoder layers); `cl` carries the LEAVES -- weight
     // and bias gradients, LayerNorm parameter gradients -- which nothing downstream waits for, so the chain's
@@ -970,9 +935,10 @@ static int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const float*
         float* dg[2] = {G[ixl.layer(l, L_N2W)], G[ixl.layer(l, L_N1W)]}; float* db[2] = {G[ixl.layer(l, L_N2B)], G[ixl.layer(l, L_N1B)]};
         return bbbp_ln_param_grad_multi(cl.st, 2, dy, zz, mm, rr, dg, db, plan.B, plan.F);
     };
+    auto record_layer_bucket = [&](int l) -> int { return (ds && l >= 0 && l < 32) ? record_bucket(ds->layer[l], cl.st) : BBBP_OK; };
     auto layer_norm_leaves = [&](int l) -> int {
         TRY(layer_norm_grads(l));
-        return record_layer_bucket(cl.st, l);
+        return record_layer_bucket(l);
     };
     const PIdx ix(d);
     const int B = plan.B, F = plan.F, NH = plan.NH, D = plan.D, DFF = plan.DFF;
@@ -993,8 +959,7 @@ static int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const float*
     // default ON since round 2 (bbbp_set_fused_head_bwd / BBBP_FUSED_HEAD_BWD=0 select the launch-per-op chain): with the bias
     // gradients folded into the weight-gradient GEMMs the leaves it feeds are short enough that the shorter chain shows --
     // B = 512 3.32 -> 3.27 ms, B = 256 2.12 -> 2.08, B = 128 2.36 -> 2.23 (round 1, with 38 separate column-sum leaves: neutral)
-    if (g_fused_head_bwd < 0) { const char* e = getenv("BBBP_FUSED_HEAD_BWD"); g_fused_head_bwd = e ? atoi(e) != 0 : 1; }
-    const int fused_head_bwd = g_fused_head_bwd && !plan.concat;
+    const int fused_head_bwd = g_fused_head_bwd.get() && !plan.concat;
     float* dlogit = c.f(plan.dlogit); float* dpre = c.f(plan.dpre);
     bool head_leaves_pending = false;
     auto head_leaves = [&]() -> int {
@@ -1097,43 +1062,25 @@ static int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const float*
     float* dpool2 = c.f(plan.dpool2); float* dpool1 = c.f(plan.dpool1);
     next_section(SEC_IMGFC_BWD);
     TRY(linear_bwd_weight(c, dcomb + FC, COMB, pool2, IMG_FLAT, G[ix.ifc_w()], B, FC, IMG_FLAT));
-    {
-        int dev = 0;
-        BBBP_CHECK_HIP(hipGetDevice(&dev));
-        if (dev >= 0 && dev < 64) {
-            if (!g_bucket_event[dev]) BBBP_CHECK_HIP(hipEventCreateWithFlags(&g_bucket_event[dev], hipEventDisableTiming));
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            (void)hipStreamIsCapturing(c.st, &cap);
-            if (cap == hipStreamCaptureStatusNone) {        // an event recorded inside a graph capture means nothing outside it
-                BBBP_CHECK_HIP(hipEventRecord(g_bucket_event[dev], c.st));
-                g_bucket_recorded[dev] = true;
-            } else {
-                g_bucket_recorded[dev] = false;
-            }
-        }
-    }
+    if (ds) TRY(record_bucket(ds->bucket0, c.st));
     TRY(linear_bwd_input(c, dcomb + FC, COMB, P[ix.ifc_w()], dpool2, IMG_FLAT, B, FC, IMG_FLAT));
-    {
+    if (ds) {
         // ... and from here on the image-FC weight itself is no longer read by this pass (bbbp_mixed_backward_wait_released, bucket 0)
-        int dev = 0;
-        BBBP_CHECK_HIP(hipGetDevice(&dev));
-        if (g_release_events && dev >= 0 && dev < 64 && g_bucket_recorded[dev]) {
-            if (!g_bucket0_released[dev]) BBBP_CHECK_HIP(hipEventCreateWithFlags(&g_bucket0_released[dev], hipEventDisableTiming));
-            BBBP_CHECK_HIP(hipEventRecord(g_bucket0_released[dev], c.st));
-            g_bucket0_released_recorded[dev] = true;
-        } else if (dev >= 0 && dev < 64) {
-            g_bucket0_released_recorded[dev] = false;
+        BucketEvent& rel = ds->bucket0_released;
+        rel.recorded = g_release_events && ds->bucket0.recorded;
+        if (rel.recorded) {
+            if (!rel.ev) BBBP_CHECK_HIP(hipEventCreateWithFlags(&rel.ev, hipEventDisableTiming));
+            BBBP_CHECK_HIP(hipEventRecord(rel.ev, c.st));
         }
     }
     next_section(SEC_CONV2_WGRAD);
     {
         // beside the encoder's backward chain the sparse weight-gradient kernel runs one wave per SIMD (common.h); the rule looks at the
         // plan only, not at the stream mode: one stream or three give bit-identical steps
-        g_bbbp_conv_wgrad_beside_encoder = plan.L > 0 ? 1 : 0;
-        const int rcw = bbbp_conv3x3_relu_pool_bwd_weight(c.st, pool1, dpool2, c.u8(plan.mask2), G[ix.c2_w()], G[ix.c2_b()], B, C1, C2, IMG / 2,
-                                                          IMG / 2, c.scratch(), c.scratch_bytes());
-        g_bbbp_conv_wgrad_beside_encoder = 0;
-        TRY(rcw);
+        ConvPrefs prefs;
+        prefs.wgrad_beside_encoder = plan.L > 0 ? 1 : 0;
+        TRY(conv3x3_relu_pool_bwd_weight(c.st, pool1, dpool2, c.u8(plan.mask2), G[ix.c2_w()], G[ix.c2_b()], B, C1, C2, IMG / 2, IMG / 2,
+                                         c.scratch(), c.scratch_bytes(), prefs));
     }
     next_section(SEC_CONV2_DGRAD);
     TRY(bbbp_conv3x3_relu_pool_bwd_data(c.st, dpool2, c.u8(plan.mask2), P[ix.c2_w()], dpool1, B, C1, C2, IMG / 2, IMG / 2,
@@ -1342,25 +1289,17 @@ static int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const float*
             Section sw(cl.st, SEC_QKV_WGRAD);
             TRY(linear_bwd_weight_bias(cl, dqkv, 3 * F, xin, F, G[ix.layer(l, L_INW)], G[ix.layer(l, L_INB)], B, 3 * F, F));
         }
-        if (ln_grads_early) TRY(record_layer_bucket(cl.st, l));
+        if (ln_grads_early) TRY(record_layer_bucket(l));
         else TRY(layer_norm_leaves(l));
         if (l > 0 || d->need_input_grad) {
             Section sg(ce.st, SEC_QKV_DGRAD);
             TRY(linear_bwd_input(ce, dqkv, 3 * F, plan.fold ? c.f(plan.fwf[l]) : P[ix.layer(l, L_INW)], l > 0 ? c.f(plan.lgrad[l - 1].dyout) : c.f(plan.dA), F, B, 3 * F, F, dz1, F));
         }
     }
-    {
+    if (ds) {
         // bucket 1 is final when the chain AND the leaves are: make the leaf stream wait for the chain's tail, record there
-        int dev = 0;
-        BBBP_CHECK_HIP(hipGetDevice(&dev));
-        if (dev >= 0 && dev < 64) {
-            if (!g_bucket1_event[dev]) BBBP_CHECK_HIP(hipEventCreateWithFlags(&g_bucket1_event[dev], hipEventDisableTiming));
-            if (ss) TRY(after(ss, ce.st, cl.st));
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            (void)hipStreamIsCapturing(cl.st, &cap);
-            g_bucket1_recorded[dev] = cap == hipStreamCaptureStatusNone;
-            if (g_bucket1_recorded[dev]) BBBP_CHECK_HIP(hipEventRecord(g_bucket1_event[dev], cl.st));
-        }
+        if (ss) TRY(after(ss, ce.st, cl.st));
+        TRY(record_bucket(ds->bucket1, cl.st));
     }
     if (ss) {
         TRY(join_side(c.st, ss));
@@ -1425,13 +1364,12 @@ GraphKey make_key(int kind, const bbbp_mixed_desc* d, const void* a, const void*
 // event exists (no backward yet, or the backward was replayed from a graph): the caller then waits for the whole stream.
 extern "C" int bbbp_mixed_backward_wait_bucket(void* stream, int bucket) {
     BBBP_CHECK_ARG(bucket >= 0 && bucket < 2 + 32, "wait_bucket: unknown bucket %d", bucket);
-    int dev = 0;
-    BBBP_CHECK_HIP(hipGetDevice(&dev));
-    BBBP_CHECK_ARG(dev >= 0 && dev < 64, "wait_bucket: device %d", dev);
-    hipEvent_t ev = bucket == 0 ? g_bucket_event[dev] : bucket == 1 ? g_bucket1_event[dev] : g_layer_event[dev][bucket - 2];
-    const bool ok = bucket == 0 ? g_bucket_recorded[dev] : bucket == 1 ? g_bucket1_recorded[dev] : g_layer_recorded[dev][bucket - 2];
-    BBBP_CHECK_ARG(ev && ok, "wait_bucket: no event for bucket %d on device %d", bucket, dev);
-    BBBP_CHECK_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream), ev, 0));
+    DeviceState* ds = nullptr; int dev = 0;
+    TRY(device_state(&ds, &dev));
+    BBBP_CHECK_ARG(ds, "wait_bucket: device %d", dev);
+    const BucketEvent& b = bucket == 0 ? ds->bucket0 : bucket == 1 ? ds->bucket1 : ds->layer[bucket - 2];
+    BBBP_CHECK_ARG(b.ev && b.recorded, "wait_bucket: no event for bucket %d on device %d", bucket, dev);
+    BBBP_CHECK_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream), b.ev, 0));
     return BBBP_OK;
 }
 
@@ -1449,11 +1387,11 @@ extern "C" int bbbp_set_release_events(int on) {
 extern "C" int bbbp_mixed_backward_wait_released(void* stream, int bucket) {
     BBBP_CHECK_ARG(bucket >= 0 && bucket < 2 + 32, "wait_released: unknown bucket %d", bucket);
     if (bucket == 0) {
-        int dev = 0;
-        BBBP_CHECK_HIP(hipGetDevice(&dev));
-        BBBP_CHECK_ARG(dev >= 0 && dev < 64 && g_bucket_recorded[dev] && g_bucket0_released[dev] && g_bucket0_released_recorded[dev],
+        DeviceState* ds = nullptr; int dev = 0;
+        TRY(device_state(&ds, &dev));
+        BBBP_CHECK_ARG(ds && ds->bucket0.recorded && ds->bucket0_released.ev && ds->bucket0_released.recorded,
                        "wait_released: no event for bucket 0 on device %d (bbbp_set_release_events(1) before the backward pass)", dev);
-        BBBP_CHECK_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream), g_bucket0_released[dev], 0));
+        BBBP_CHECK_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream), ds->bucket0_released.ev, 0));
         return BBBP_OK;
     }
     return bbbp_mixed_backward_wait_bucket(stream, bucket >= 3 ? bucket - 1 : 1);
@@ -1534,9 +1472,9 @@ extern "C" int bbbp_mixed_forward(void* stream, const bbbp_mixed_desc* d, const 
     h = hash_ptrs(reinterpret_cast<const void* const*>(bn_running), 2, h);
     const GraphKey key = make_key(0, d, fingerprint, image, out, workspace, h);
     if (d->collective)              // host callbacks between the launches: nothing to capture
-        return forward_enqueue(st, d, P, bn_running, fingerprint, image, out, workspace, workspace_bytes);
+        return forward_enqueue(st, d, plan, P, bn_running, fingerprint, image, out, workspace);
     return run_or_replay(key, st, [&](hipStream_t s) {
-        return forward_enqueue(s, d, P, bn_running, fingerprint, image, out, workspace, workspace_bytes);
+        return forward_enqueue(s, d, plan, P, bn_running, fingerprint, image, out, workspace);
     });
 }
 
@@ -1557,8 +1495,8 @@ extern "C" int bbbp_mixed_backward(void* stream, const bbbp_mixed_desc* d, const
     h = hash_ptrs(reinterpret_cast<const void* const*>(G), np, h);
     const GraphKey key = make_key(1, d, fingerprint, image, dout, workspace, h);
     if (d->collective)
-        return backward_enqueue(st, d, P, G, fingerprint, image, dout, workspace, workspace_bytes);
+        return backward_enqueue(st, d, plan, P, G, fingerprint, image, dout, workspace);
     return run_or_replay(key, st, [&](hipStream_t s) {
-        return backward_enqueue(s, d, P, G, fingerprint, image, dout, workspace, workspace_bytes);
+        return backward_enqueue(s, d, plan, P, G, fingerprint, image, dout, workspace);
     });
 }

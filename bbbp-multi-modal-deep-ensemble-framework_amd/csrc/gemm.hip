@@ -1311,7 +1311,7 @@ struct DirectPlan { bool use; int t, wsm, wsn, ks; };
 
 // The direct path serves launches that cannot fill the chip with 64x64 tiles anyway; big GEMMs keep the LDS tiling.
 DirectPlan direct_plan(int M, int N, int K, int batch) {
-    static const int enabled = [] { const char* e = getenv("BBBP_GEMM_DIRECT"); return e ? atoi(e) : 1; }();
+    static const int enabled = bbbp_env_int("BBBP_GEMM_DIRECT", 1);
     DirectPlan d{false, 1, 1, 1, 1};
     const double flops = 2.0 * M * N * (double)K * batch;
     if (!enabled || flops > 1.2e9 || K > 8192) return d;
@@ -1321,7 +1321,7 @@ DirectPlan direct_plan(int M, int N, int K, int batch) {
     // VGPRs on every SIMD of one CU and cannot start while the persistent conv work-groups of the other stream hold
     // theirs (measured: the conv beside it slowed from 0.72 to 1.25 ms and the encoder gained nothing).  Whole training
     // step, B = 512 (tools/exp_step.py): K slices capped at 1 / 2 / 4 -> 3.95 / 3.75 / 3.78 ms; LDS-tiled path 4.25 ms.
-    static const int max_ks = [] { const char* e = getenv("BBBP_GEMM_DIRECT_KS"); return e ? atoi(e) : 2; }();
+    static const int max_ks = bbbp_env_int("BBBP_GEMM_DIRECT_KS", 2);
     d.ks = nch <= 12 ? 1 : (cdiv(nch, 8) < max_ks ? cdiv(nch, 8) : max_ks);
     if (d.ks == 3) d.ks = 4;
     const long wt = (long)cdiv(M, 16) * cdiv(N, 16) * batch;
@@ -1329,7 +1329,7 @@ DirectPlan direct_plan(int M, int N, int K, int batch) {
     // placed until the conv kernel ends -- rocprofv3 showed the dhff GEMM of every layer waiting up to 0.65 ms.  The
     // 16x16 variant fits the 64 VGPRs that are left, so it serves everything up to 4096 wave tiles (all of B = 512,
     // F = 167: whole step 3.81 -> 3.75 ms); larger outputs (B = 4096 screening) take 32x32 tiles for the operand reuse.
-    static const int max_t = [] { const char* e = getenv("BBBP_GEMM_DIRECT_T"); return e ? atoi(e) : 2; }();
+    static const int max_t = bbbp_env_int("BBBP_GEMM_DIRECT_T", 2);
     d.t = (wt * d.ks <= 4096 || max_t < 2) ? 1 : 2;
     // many heads with a tiny head dimension (F = 2048: 256 heads of 8) are hundreds of thousands of nearly empty wave
     // tiles: those stay on the LDS-tiled kernel
@@ -1412,19 +1412,13 @@ void launch_tile(const GemmParams& p, int layout, dim3 grid, hipStream_t st) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-int g_gemm_b3 = -1;
-int gemm_b3_on() {
-    if (g_gemm_b3 < 0) { const char* e = getenv("BBBP_GEMM_SPLIT_BF16"); g_gemm_b3 = e ? (atoi(e) != 0) : 1; }
-    return g_gemm_b3;
-}
+Knob g_gemm_b3{"BBBP_GEMM_SPLIT_BF16", 1, knob_bool};
+int gemm_b3_on() { return g_gemm_b3.get(); }
 // Arrival counters of the split-bf16 kernel's in-kernel split-K reduction: one zeroed region per (device, stream) -- launches on one
 // stream run one after another and every launch leaves its counters at zero, launches on different streams never share a region.
 constexpr int ARRIVAL_REGION = 8192, ARRIVAL_REGIONS = 32;
-int g_gemm_fold_reduce = -1;
-int gemm_fold_reduce_on() {
-    if (g_gemm_fold_reduce < 0) { const char* e = getenv("BBBP_GEMM_FOLD_REDUCE"); g_gemm_fold_reduce = e ? (atoi(e) != 0) : 0; }      // default off: measured slower, see DESIGN.md section 3
-    return g_gemm_fold_reduce;
-}
+Knob g_gemm_fold_reduce{"BBBP_GEMM_FOLD_REDUCE", 0, knob_bool};      // default off: measured slower, see DESIGN.md section 3
+int gemm_fold_reduce_on() { return g_gemm_fold_reduce.get(); }
 unsigned* arrival_counters(hipStream_t st, long tiles) {
     if (!gemm_fold_reduce_on() || tiles > ARRIVAL_REGION) return nullptr;
     static std::mutex mu;
@@ -1461,7 +1455,7 @@ bool b3_eligible(const GemmParams& p, int layout) {
 // the 64 x 64 split-bf16 tile: the 128-tile grid would leave CUs idle (or split K) while 64-tiles fill the chip, and K is deep enough to
 // amortise the tile's prologue.  BBBP_GEMM_B3_SMALL=0 keeps the 128-tile plans.
 bool b3_small_tile(int M, int N, int K, int batch) {
-    static const int on = [] { const char* e = getenv("BBBP_GEMM_B3_SMALL"); return e ? atoi(e) : 1; }();
+    static const int on = bbbp_env_int("BBBP_GEMM_B3_SMALL", 1);
     if (!on || K < 512) return false;
     const long t128 = (long)cdiv(M, 128) * cdiv(N, 128) * batch, t64 = (long)cdiv(M, 64) * cdiv(N, 64) * batch;
     const int ncu = bbbp_num_cus();
@@ -1470,7 +1464,7 @@ bool b3_small_tile(int M, int N, int K, int batch) {
 template <int LAYOUT>
 int launch_b3_one(const GemmParams& p, dim3 grid, hipStream_t st) {
     { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_b3_kernel<LAYOUT>), (size_t)B3_LDS); if (rc_) return rc_; }
-    static const bool probe = [] { const char* e = getenv("BBBP_GEMM_B3_PROBE"); return e && atoi(e) != 0; }();
+    static const bool probe = bbbp_env_int("BBBP_GEMM_B3_PROBE", 0) != 0;
     if (probe) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_b3_probe_kernel<LAYOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)B3_LDS);
         hipLaunchKernelGGL((gemm_b3_probe_kernel<LAYOUT>), grid, dim3(256), B3_LDS, st, p);
@@ -1501,7 +1495,7 @@ static void gemm_plan(int M, int N, int K, int batch, int* tile, int* splits, in
     // plan runs it at 49 TFLOP/s (66 us); on the bf16 pipe the padded columns (167 -> 256) cost less than the pipe gains.
     // BBBP_GEMM_TALL_B3=0 keeps the old plan.
     {
-        static const int tall = [] { const char* e = getenv("BBBP_GEMM_TALL_B3"); return e ? atoi(e) : 1; }();
+        static const int tall = bbbp_env_int("BBBP_GEMM_TALL_B3", 1);
         const long covered = (long)cdiv(M, 128) * 128 * (long)cdiv(N, 128) * 128;
         if (tall && K >= 1024 && M >= 1024 && N >= 128 && covered * 10 <= (long)M * N * 16) *tile = 128;
     }
@@ -1510,10 +1504,10 @@ static void gemm_plan(int M, int N, int K, int batch, int* tile, int* splits, in
     // launches are latency-bound at one work-group per tile, so spread K over ~2 work-groups per CU.
     int s = 1;
     // BBBP_GEMM_SPLIT_X10: target work-groups per CU x 10 when K is split (default 20 = two per CU)
-    static const int split_x10 = [] { const char* e = getenv("BBBP_GEMM_SPLIT_X10"); return e ? atoi(e) : 20; }();
+    static const int split_x10 = bbbp_env_int("BBBP_GEMM_SPLIT_X10", 20);
     // BBBP_GEMM_SPLIT_FULL: also split when the tiles already cover the chip once but not twice (one work-group per CU leaves
     // every barrier stall of its single wave per SIMD exposed)
-    static const int split_full = [] { const char* e = getenv("BBBP_GEMM_SPLIT_FULL"); return e ? atoi(e) : 0; }();
+    static const int split_full = bbbp_env_int("BBBP_GEMM_SPLIT_FULL", 0);
     if ((tiles < ncu || (split_full && tiles < 2 * ncu && K >= 512)) && K >= 256) {
         s = (int)(((long)split_x10 * ncu / 10 + tiles - 1) / tiles);
         int maxs = K / 64;
@@ -1614,8 +1608,8 @@ int gemm_run(hipStream_t st, const bbbp_gemm_desc& g, void* workspace, size_t wo
         }
     }
     if (K == 0) { p.splits = 1; p.kchunk = bk_of(tile); }
-    static const int short_k_max = [] { const char* e = getenv("BBBP_GEMM_SHORT_K"); return e ? atoi(e) : 256; }();
-    static const int short_k_tiles = [] { const char* e = getenv("BBBP_GEMM_SHORT_TILES"); return e ? atoi(e) : 4; }();
+    static const int short_k_max = bbbp_env_int("BBBP_GEMM_SHORT_K", 256);
+    static const int short_k_tiles = bbbp_env_int("BBBP_GEMM_SHORT_TILES", 4);
     p.short_k = (tile == 128 && p.splits == 1 && K <= short_k_max &&
                  (long)cdiv(M, 128) * cdiv(N, 128) * batch >= (long)short_k_tiles * bbbp_num_cus()) ? 1 : 0;
     dim3 grid(cdiv(N, tile), cdiv(M, tile), batch * p.splits);
@@ -1647,7 +1641,7 @@ int gemm_run(hipStream_t st, const bbbp_gemm_desc& g, void* workspace, size_t wo
         int gx = (int)((mn + 255) / 256);
         if (gx > 4096) gx = 4096;
         auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        static const int vec4_on = [] { const char* e = getenv("BBBP_GEMM_REDUCE_VEC4"); return e ? atoi(e) : 1; }();
+        static const int vec4_on = bbbp_env_int("BBBP_GEMM_REDUCE_VEC4", 1);
         const bool vec4 = vec4_on && N % 4 == 0 && p.ldc % 4 == 0 && p.sC % 4 == 0 && al16(p.C) && al16(p.slab) && (!p.bias || al16(p.bias)) &&
                           (!p.R || (p.ldr % 4 == 0 && p.sR % 4 == 0 && al16(p.R))) && (!p.gate || (p.ldg % 4 == 0 && p.sG % 4 == 0 && al16(p.gate)));
         if (vec4) {
@@ -1702,17 +1696,9 @@ extern "C" int bbbp_gemm_f32_grouped(void* stream, const bbbp_gemm_desc* problem
     return BBBP_OK;
 }
 
-extern "C" int bbbp_set_gemm_fold_reduce(int on) {
-    const int prev = gemm_fold_reduce_on();
-    g_gemm_fold_reduce = on ? 1 : 0;
-    return prev;
-}
+extern "C" int bbbp_set_gemm_fold_reduce(int on) { return g_gemm_fold_reduce.set(on); }
 
-extern "C" int bbbp_set_gemm_split_bf16(int on) {
-    const int prev = gemm_b3_on();
-    g_gemm_b3 = on ? 1 : 0;
-    return prev;
-}
+extern "C" int bbbp_set_gemm_split_bf16(int on) { return g_gemm_b3.set(on); }
 
 extern "C" int bbbp_gemm_split_bf16_phases(unsigned long long* phases7) {
     BBBP_CHECK_ARG(phases7 != nullptr, "gemm_split_bf16_phases: null output");

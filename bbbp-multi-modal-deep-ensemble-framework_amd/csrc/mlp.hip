@@ -514,8 +514,8 @@ extern "C" int bbbp_mlp_train_epochs(void* stream, bbbp_mlp_model* models_dev, i
     if (n_models == 0 || epochs == 0) return BBBP_OK;
     BBBP_CHECK_ARG(models_dev && X && y, "mlp_train: null pointer");
     // round 4: the float64-MFMA trainer; BBBP_MLP_SCALAR=1 selects the scalar kernel of rounds 1-3 (the cross-check in tests/test_gpu_mlp.py)
-    const char* e = getenv("BBBP_MLP_SCALAR");
-    if (e && atoi(e) != 0)
+    const int scalar = bbbp_env_int("BBBP_MLP_SCALAR", 0);          // (read at every call, not once)
+    if (scalar != 0)
         hipLaunchKernelGGL(mlp_train_scalar_kernel, dim3(n_models), dim3(NT), 0, static_cast<hipStream_t>(stream), models_dev, X, y, n_features, epochs);
     else if (g_mlp_profile_on)
         hipLaunchKernelGGL(mlp_train_mfma_kernel<true>, dim3(n_models), dim3(MT), 0, static_cast<hipStream_t>(stream), models_dev, X, y, n_features, epochs);

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_wide_kernel(const float* dy
 }
 // the wide form serves rows of 1024..4096 columns in whole float4s (gfx950 global loads need 4-byte alignment only)
 inline int ln_wide_nv(int cols) {
-    static const int on = [] { const char* e = getenv("BBBP_LN_WIDE"); return e ? atoi(e) : 1; }();
+    static const int on = bbbp_env_int("BBBP_LN_WIDE", 1);
     return (on && cols >= 1024 && cols <= 4096 && cols % 4 == 0) ? (cols + 1023) / 1024 : 0;
 }
 
@@ -565,7 +565,7 @@ __device__ __forceinline__ void adamw_element(float& p, float g, float& m, float
 // BBBP_ADAMW_BACKGROUND=n (experiment, default 0 = off): launches of the step use at most n work-groups and no raised wave priority -- an
 // update that runs BESIDE compute (the optimizer pipelined into the backward pass) should trickle through HBM, not evict the GEMMs.
 int adamw_background() {
-    static const int v = [] { const char* e = getenv("BBBP_ADAMW_BACKGROUND"); return e ? atoi(e) : 0; }();
+    static const int v = bbbp_env_int("BBBP_ADAMW_BACKGROUND", 0);
     return v;
 }
 

@@ -13,10 +13,6 @@ static thread_local char g_err[512] = "";
 thread_local int g_bbbp_reserved_cus = 0;
 thread_local size_t g_bbbp_small_lds_pad = 0;
 thread_local int g_bbbp_wino_side_cus = 0;
-thread_local int g_bbbp_conv1_fwd_f32 = 0;
-thread_local int g_bbbp_conv1_fwd_per_cu = 0;
-thread_local int g_bbbp_conv_wgrad_beside_encoder = 0;
-thread_local int g_bbbp_conv2_fwd_pipe = 0;
 thread_local const unsigned long long* g_bbbp_seed_base = nullptr;
 
 // More than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize per (kernel, DEVICE): code objects are loaded
@@ -50,15 +46,14 @@ void bbbp_set_error(const char* fmt, ...) {
 
 extern "C" const char* bbbp_last_error(void) { return g_err; }
 
+const char* bbbp_env(const char* name) { return getenv(name); }
+int bbbp_env_int(const char* name, int dflt) { const char* e = bbbp_env(name); return e ? atoi(e) : dflt; }
+
 // CUs kept out of every persistent grid (they are all sized from bbbp_num_cus()): room for RCCL's ring kernels beside the conv work-groups
 // in a multi-GPU run.  Initial value BBBP_COMM_CUS (default 0); bench.py's N-rank diagnostic pass measures 0 against 8 and keeps the
 // faster one (bbbp_set_comm_cus).  Never measured on a multi-GPU node before that pass runs there.
-static int g_comm_cus = -1;
-static int comm_cus() {
-    if (g_comm_cus < 0) { const char* e = getenv("BBBP_COMM_CUS"); const int v = e ? atoi(e) : 0; g_comm_cus = v < 0 ? 0 : v; }
-    return g_comm_cus;
-}
-extern "C" int bbbp_set_comm_cus(int n) { const int prev = comm_cus(); g_comm_cus = n < 0 ? 0 : n; return prev; }
+static Knob g_comm_cus{"BBBP_COMM_CUS", 0, [](int v) { return v < 0 ? 0 : v; }};
+extern "C" int bbbp_set_comm_cus(int n) { return g_comm_cus.set(n); }
 
 int bbbp_num_cus() {
     static int cached[64] = {0};                  // per device: the hardware's count (benign race: every thread computes the same value)
@@ -69,7 +64,7 @@ int bbbp_num_cus() {
         int n = (hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 0;
         cached[dev] = n > 0 ? n : 256;
     }
-    const int n = cached[dev], c = comm_cus();
+    const int n = cached[dev], c = g_comm_cus.get();
     return (c > 0 && n - c >= 64) ? n - c : n;
 }
 
@@ -90,24 +85,4 @@ extern "C" int bbbp_set_partition(int reserved_cus, size_t small_lds_pad) {
 extern "C" int bbbp_set_seed_base(const void* base_dev) {
     g_bbbp_seed_base = static_cast<const unsigned long long*>(base_dev);
     return BBBP_OK;
-}
-
-// The conv2-family weight gradient has two structured-sparse forms (conv_b3.hip): 8 waves (fastest alone) and 4 waves (one wave per SIMD: the
-// form to run while ANOTHER branch's small kernels share the GPU).  bbbp_mixed_backward picks by itself; a caller that composes the model
-// op by op and overlaps its branches on two streams says so for the calling thread around its bbbp_conv3x3_relu_pool_bwd_weight call.
-// Returns the previous setting.
-extern "C" int bbbp_set_conv_wgrad_beside_encoder(int on) {
-    const int prev = g_bbbp_conv_wgrad_beside_encoder;
-    g_bbbp_conv_wgrad_beside_encoder = on ? 1 : 0;
-    return prev;
-}
-
-// Forward of the 32 -> 64 / 64 -> 128 stages on 64 x 64 maps: 1 selects, for the calling thread, the software-pipelined kernel that runs ONE
-// work-group per CU (conv_b3.hip: conv_b3p_kernel) -- 3 % slower alone, but beside an encoder chain the step is 2.8 % faster
-// (bbbp_mixed_forward sets it by itself for training plans with an encoder).  Same arithmetic in the same order: bit-identical outputs
-// and decisions.  Returns the previous setting.  BBBP_C2_PIPE=0 / 1 overrides every caller.
-extern "C" int bbbp_set_conv2_fwd_pipe(int on) {
-    const int prev = g_bbbp_conv2_fwd_pipe;
-    g_bbbp_conv2_fwd_pipe = on ? 1 : 0;
-    return prev;
 }

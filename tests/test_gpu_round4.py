@@ -366,3 +366,26 @@ def test_pipelined_conv2_forward_is_bit_identical_to_the_two_work_group_kernel(d
         assert torch.equal(y0, y1), B
         if keep_mask:
             assert torch.equal(m0, m1), B
+
+
+def test_conv_form_setters_survive_a_whole_model_forward_and_backward(dev):
+    """bbbp_set_conv2_fwd_pipe / bbbp_set_conv_wgrad_beside_encoder hold "for the calling thread" and return the previous setting
+    (include/bbbp_hip.h).  The engine passes its own conv form choices as arguments, so what a caller set is still there after a
+    bbbp_mixed_forward / bbbp_mixed_backward on the same thread."""
+    L = _lib.lib()
+    F, B = 167, 8
+    fp, img, y = (t.to(dev) for t in synth_inputs(41, B, F, 49152))
+    old_pipe = L.bbbp_set_conv2_fwd_pipe(1)
+    old_wgrad = L.bbbp_set_conv_wgrad_beside_encoder(1)
+    try:
+        torch.manual_seed(7)
+        model = bbbp_amd.MixedInputModel(F, 128).to(dev).train()
+        loss = bbbp_amd.MSELoss()(model(fp, img).squeeze(), y)
+        loss.backward()
+        torch.cuda.synchronize()
+        assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in model.parameters())
+    finally:
+        seen_pipe = L.bbbp_set_conv2_fwd_pipe(old_pipe)
+        seen_wgrad = L.bbbp_set_conv_wgrad_beside_encoder(old_wgrad)
+    assert seen_pipe == 1
+    assert seen_wgrad == 1
