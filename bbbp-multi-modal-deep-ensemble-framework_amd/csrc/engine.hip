@@ -88,6 +88,29 @@ struct Plan {
     size_t total;
 };
 
+// Every choice a whole-model call makes from knobs, environment variables and the plan, beyond the workspace layout (Plan: fold, flash,
+// attn_b3): decided once per call by make_schedule (below, with the measurements behind each default), read by the enqueue functions,
+// compared by the graph cache.  A forward call fills the forward half, a backward call the backward half; the other half stays zero.
+enum { ENC_OPS = 0, ENC_ROWS, ENC_SLICED };      // encoder schedules: launch-per-op, row-fused launches, one sliced persistent launch
+struct Schedule {
+    bool overlap;                       // the branches on streams of their own; false: everything on the caller's stream
+    int enc_fwd, enc_bwd;               // ENC_*
+    // launch-per-op encoder forward: norm1 absorbed by linear1 / norm2 by the next in_proj or fingerprint_fc; out_proj -> norm1 as one
+    // launch; the FFN dropout in linear1's epilogue
+    bool absorb1, absorb2, ln_fused, drop_in_gemm;
+    bool head_fwd_fused, head_bwd_fused;
+    bool fold_bias_grad;                // backward: a bias gradient rides in its weight-gradient GEMM (linear_bwd_weight_bias)
+    ConvPrefs conv1_fwd, conv2_fwd, conv2_wgrad;
+    bool operator==(const Schedule& o) const {          // field by field: the structs have padding
+        auto same = [](const ConvPrefs& a, const ConvPrefs& b) {
+            return a.conv1_fwd_f32 == b.conv1_fwd_f32 && a.conv1_fwd_per_cu == b.conv1_fwd_per_cu && a.conv2_fwd_pipe == b.conv2_fwd_pipe && a.wgrad_beside_encoder == b.wgrad_beside_encoder;
+        };
+        return overlap == o.overlap && enc_fwd == o.enc_fwd && enc_bwd == o.enc_bwd && absorb1 == o.absorb1 && absorb2 == o.absorb2 && ln_fused == o.ln_fused &&
+               drop_in_gemm == o.drop_in_gemm && head_fwd_fused == o.head_fwd_fused && head_bwd_fused == o.head_bwd_fused && fold_bias_grad == o.fold_bias_grad &&
+               same(conv1_fwd, o.conv1_fwd) && same(conv2_fwd, o.conv2_fwd) && same(conv2_wgrad, o.conv2_wgrad);
+    }
+};
+
 // Fused attention for many small heads (attention.hip); 0 selects the GEMM + softmax schedule with materialised probabilities.
 Knob g_flash_attention{"BBBP_FLASH_ATTENTION", 13, [](int v) { return v & 31; }};
 
@@ -240,7 +263,8 @@ struct Ctx {
     hipStream_t st;
     char* ws;
     const Plan* p;
-    int side = 0;          // 0 main stream, 1 fingerprint-branch chain, 2 weight-gradient leaves: own scratch each
+    const Schedule* s;
+    int side = 0;         // 0 main stream, 1 fingerprint-branch chain, 2 weight-gradient leaves: own scratch each
     float* f(size_t off) const { return reinterpret_cast<float*>(ws + off); }
     uint8_t* u8(size_t off) const { return reinterpret_cast<uint8_t*>(ws + off); }
     void* scratch() const { return ws + (side == 0 ? p->scratch : side == 1 ? p->scratch2 : p->scratch3); }
@@ -331,6 +355,65 @@ struct Partition {
         if (side) g_bbbp_wino_side_cus = 0;
     }
 };
+// An environment-only knob is read once per process, at the first call of its direction; a knob with a setter again at every call.
+Schedule make_schedule(const Plan& p, bool backward) {
+    Schedule s{};
+    const int B = p.B, F = p.F, DFF = p.DFF;
+    if (backward) {
+        s.overlap = overlap_enabled();          // (a training plan is never a screening plan)
+        // (the backward kernel takes bit 2 of the mode and its own share of the workspace)
+        s.enc_bwd = (sliced_encoder(p, 4) && p.sl_sync && p.sl_kvpart) ? ENC_SLICED : fused_encoder(p) ? ENC_ROWS : ENC_OPS;
+        // default ON since round 2 (bbbp_set_fused_head_bwd / BBBP_FUSED_HEAD_BWD=0 select the launch-per-op chain): with the bias
+        // gradients folded into the weight-gradient GEMMs the leaves it feeds are short enough that the shorter chain shows --
+        // B = 512 3.32 -> 3.27 ms, B = 256 2.12 -> 2.08, B = 128 2.36 -> 2.23 (round 1, with 38 separate column-sum leaves: neutral)
+        s.head_bwd_fused = g_fused_head_bwd.get() && !p.concat;
+        static const int fold_bias = bbbp_env_int("BBBP_FOLD_BIAS_GRAD", 1);
+        s.fold_bias_grad = fold_bias != 0;
+        // beside the encoder's backward chain the sparse weight-gradient kernel runs one wave per SIMD (common.h); the rule looks at the
+        // plan only, not at the stream mode: one stream or three give bit-identical steps
+        s.conv2_wgrad.wgrad_beside_encoder = p.L > 0 ? 1 : 0;
+        return s;
+    }
+    // Screening plans (forward-only, 2048+ rows on the bf16 attention kernel) run on ONE stream: there both branches are bound by the matrix
+    // pipe, so the second stream only time-shares it -- measured equal on one box (6.66 / 6.83 ms overlapped, 6.59 / 6.85 one stream) and
+    // WORSE than the sum of the branches on others (7.6 ms against 5.29 + 1.85 + 0.06; profiles/r03_config5_streams.txt); alone, the
+    // encoder also takes the out_proj fold's gain (fold mask bit 1).  BBBP_SCREEN_OVERLAP=1 restores the two-stream schedule.
+    static const bool screen_overlap = bbbp_env_int("BBBP_SCREEN_OVERLAP", 0) != 0;
+    s.overlap = overlap_enabled() && (screen_overlap || !p.attn_b3);
+    s.enc_fwd = (sliced_encoder(p) && p.sl_sync) ? ENC_SLICED : fused_encoder(p) ? ENC_ROWS : ENC_OPS;
+    const bool beside_chain = !p.inference && p.L > 0;
+    // conv1: beside a training step's encoder chain the f32 form stays (common.h: ConvPrefs::conv1_fwd_f32); screening batches, eval loops and
+    // the encoder-less two-branch model take the split-bf16 form when the conv mask selects it (bit 6, default)
+    // (the rule looks at the plan only, not at the stream mode: one stream or three give bit-identical steps)
+    // round 4: training steps run the software-pipelined split-bf16 kernel (conv_b3c1.hip) too, ONE work-group per CU beside the chain
+    // (BBBP_C1_TRAIN=0: the f32 kernel of rounds 1-3 there; 2: two work-groups per CU, measured slower for the step)
+    static const int c1_train = bbbp_env_int("BBBP_C1_TRAIN", 1);      // default 1: step 2.517 -> 2.487 ms (profiles/r04_c1_pipe.txt)
+    s.conv1_fwd.conv1_fwd_f32 = (beside_chain && !c1_train) ? 1 : 0;
+    s.conv1_fwd.conv1_fwd_per_cu = (beside_chain && c1_train) ? (c1_train >= 2 ? 2 : 1) : 0;      // BBBP_C1_TRAIN=2: two work-groups per CU there too
+    // conv2, round 4: beside a training step's encoder chain the software-pipelined one-work-group-per-CU kernel (conv_b3.hip): 0.40 instead of
+    // 0.387 ms alone, but the chain -- the forward half's critical path -- keeps three quarters of every SIMD: step 2.41 -> 2.34 ms
+    // (profiles/r04_conv2_pipe.txt).  BBBP_C2_TRAIN=0: the two-work-group kernel there too.  Bit-identical outputs either way.
+    static const int c2_train = bbbp_env_int("BBBP_C2_TRAIN", 1);
+    s.conv2_fwd.conv2_fwd_pipe = (beside_chain && c2_train) ? 1 : 0;
+    // LayerNorm absorbed by the Linear that consumes it (BBBP_LN_ABSORB=0 keeps the stand-alone launches; Step::encoder_layer_fwd_ops)
+    const bool lna_ok = ln_absorb_on() && s.enc_fwd == ENC_OPS && !p.exact && p.L > 0 && bbbp_layernorm_linear_preferred(B, DFF, F) &&
+                        bbbp_layernorm_linear_preferred(B, 3 * F, F) && bbbp_layernorm_linear_preferred(B, FC, F) &&
+                        // training: the producers' dropout rides in the small-product GEMM's epilogue only
+                        (!p.drop || (bbbp_gemm_folds_asum(B, F, DFF, 1) && bbbp_gemm_folds_asum(B, F, p.fold ? (int)p.Bg : F, 1)));
+    s.absorb1 = lna_ok && !(p.attn_b3 && p.fold);      // (that attention kernel writes z1 itself: no epilogue for the residual)
+    s.absorb2 = lna_ok;
+    // out_proj -> (dropout) + residual -> norm1 as one launch (gemm.hip: gemm_direct_ln_kernel).
+    // OPT-IN (BBBP_FUSED_LINEAR_LN=1), measured slower at B = 512: the 11-wave work-groups need three wave slots on three SIMDs of a CU
+    // beside the resident conv work-groups (encoder forward 0.98 -> 1.15 ms in the step, 0.58 -> 0.60 alone); linear2 -> norm2 is never
+    // fused (one wave per tile walking K = 2048 alone: 90 us against 22 + 4)
+    static const bool ln_opt_in = bbbp_env_int("BBBP_FUSED_LINEAR_LN", 0) != 0;
+    s.ln_fused = s.enc_fwd == ENC_OPS && !p.fold && ln_opt_in && bbbp_linear_layernorm_supported(B, F, F) && F <= 512;
+    s.drop_in_gemm = s.enc_fwd == ENC_OPS && p.drop && bbbp_gemm_folds_asum(B, DFF, F, 1);
+    static const int fused_head = bbbp_env_int("BBBP_FUSED_HEAD", 1);
+    s.head_fwd_fused = fused_head && NHEADS_FUSION == 4;
+    return s;
+}
+
 int get_side(SideStream** out) {
     DeviceState* ds = nullptr; int dev = 0;
     TRY(device_state(&ds, &dev));
@@ -396,8 +479,8 @@ struct ProfState {
 
 struct Section {
     hipStream_t st; int idx;
-    Section(hipStream_t s, int sec) : st(s), idx(-1) {
-        if (!g_prof.on || !((g_prof.mask >> sec) & 1u) || g_prof.n >= PROF_MAX) return;
+    Section(hipStream_t s, int sec) : st(s), idx(-1) {          // sec < 0: no section
+        if (sec < 0 || !g_prof.on || !((g_prof.mask >> sec) & 1u) || g_prof.n >= PROF_MAX) return;
         idx = g_prof.n++;
         if (idx >= g_prof.created) {
             if (hipEventCreate(&g_prof.a[idx]) != hipSuccess || hipEventCreate(&g_prof.b[idx]) != hipSuccess) { idx = -1; --g_prof.n; return; }
@@ -428,22 +511,7 @@ int linear_bwd_weight(const Ctx& c, const float* dy, int lddy, const float* x, i
 }
 
 bbbp_gemm_desc gemm_desc(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
-                         float* C, int ldc, int batch, long sA, long sB, long sC);
-// dW[N,K] = dy[M,N]^T x[M,K] and db[N] = column sums of dy: ONE launch when the product takes the small-GEMM path (the bias
-// gradient rides through the same MFMAs as a virtual all-ones column of x), else the GEMM plus a column-sum kernel
-int linear_bwd_weight_bias(const Ctx& c, const float* dy, int lddy, const float* x, int ldx, float* dW, float* db, int M, int N, int K) {
-    static const int fold = bbbp_env_int("BBBP_FOLD_BIAS_GRAD", 1);
-    if (fold && bbbp_gemm_folds_asum(N, K, M, 1)) {
-        bbbp_gemm_desc g = gemm_desc(1, 0, N, K, M, 1.f, dy, lddy, x, ldx, dW, K, 1, 0, 0, 0);
-        g.asum = db;
-        return bbbp_gemm_f32_grouped(c.st, &g, 1, c.scratch(), c.scratch_bytes());
-    }
-    TRY(linear_bwd_weight(c, dy, lddy, x, ldx, dW, M, N, K));
-    return bbbp_bias_act_bwd(c.st, const_cast<float*>(dy), lddy, nullptr, 0, db, M, N, 0, 1.f);
-}
-
-bbbp_gemm_desc gemm_desc(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
-                         float* C, int ldc, int batch, long sA, long sB, long sC) {
+                         float* C, int ldc, int batch = 1, long sA = 0, long sB = 0, long sC = 0) {
     bbbp_gemm_desc g;
     g.transA = transA; g.transB = transB; g.M = M; g.N = N; g.K = K; g.alpha = alpha;
     g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
@@ -452,14 +520,20 @@ bbbp_gemm_desc gemm_desc(int transA, int transB, int M, int N, int K, float alph
     g.batch = batch; g.strideA = sA; g.strideB = sB; g.strideC = sC; g.strideR = 0; g.strideG = 0;
     return g;
 }
-
-bbbp_gemm_desc gemm_desc(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
-                         float* C, int ldc) {
-    return gemm_desc(transA, transB, M, N, K, alpha, A, lda, B, ldb, C, ldc, 1, 0, 0, 0);
+// dW[N,K] = dy[M,N]^T x[M,K] and db[N] = column sums of dy: ONE launch when the product takes the small-GEMM path (the bias
+// gradient rides through the same MFMAs as a virtual all-ones column of x), else the GEMM plus a column-sum kernel
+int linear_bwd_weight_bias(const Ctx& c, const float* dy, int lddy, const float* x, int ldx, float* dW, float* db, int M, int N, int K) {
+    if (c.s->fold_bias_grad && bbbp_gemm_folds_asum(N, K, M, 1)) {
+        bbbp_gemm_desc g = gemm_desc(1, 0, N, K, M, 1.f, dy, lddy, x, ldx, dW, K, 1, 0, 0, 0);
+        g.asum = db;
+        return bbbp_gemm_f32_grouped(c.st, &g, 1, c.scratch(), c.scratch_bytes());
+    }
+    TRY(linear_bwd_weight(c, dy, lddy, x, ldx, dW, M, N, K));
+    return bbbp_bias_act_bwd(c.st, const_cast<float*>(dy), lddy, nullptr, 0, db, M, N, 0, 1.f);
 }
 
 // per-site salt; the kernels mix it with the call's seed read from device memory (effective_seed)
-uint64_t site_seed(uint64_t /*seed: lives in the workspace*/, int layer, int site) { return (uint64_t)(layer * 8 + site + 1); }
+uint64_t site_seed(int layer, int site) { return (uint64_t)(layer * 8 + site + 1); }
 
 __global__ void set_seed_kernel(unsigned long long* slot, unsigned long long seed) { *slot = seed; }
 
@@ -475,20 +549,23 @@ struct SeedScope {
 // the second time a call arrives with the same arguments its enqueue is captured (all three streams: the fork/join
 // events pull the side streams into the capture) and from then on replayed with one hipGraphLaunch.  Anything that
 // changes an argument (another batch tensor, re-flattened parameters, a different batch size) is a different key;
-// the cache holds a few entries, least recently used first out.  Opt-in (see graphs_mode); section profiling bypasses it.
+// the cache holds a few entries, least recently used first out.  So is a knob set to another value: the key holds what was decided from
+// the knobs (the schedule, and the plan's choices that move workspace offsets).  Opt-in (see graphs_mode); section profiling bypasses it.
 struct GraphKey {
     int kind;                      // 0 forward, 1 backward
-    bbbp_mixed_desc d;             // seed zeroed
+    bbbp_mixed_desc d;             // every field make_plan reads but the seed (collective calls never get here)
     const void* ptr[6];
     uint64_t phash;                // hash of the parameter / gradient / BN pointer arrays
-    int overlap;
+    Schedule s;
+    bool fold, flash, attn_b3; size_t total;      // of the plan
     hipStream_t st;
     bool operator==(const GraphKey& o) const {
         return kind == o.kind && d.batch == o.d.batch && d.fingerprint_size == o.d.fingerprint_size && d.nhead == o.d.nhead &&
                d.num_layers == o.d.num_layers && d.dim_feedforward == o.d.dim_feedforward && d.training == o.d.training &&
-               d.dropout_p == o.d.dropout_p && d.need_input_grad == o.d.need_input_grad && phash == o.phash &&
-               overlap == o.overlap && st == o.st && ptr[0] == o.ptr[0] && ptr[1] == o.ptr[1] && ptr[2] == o.ptr[2] &&
-               ptr[3] == o.ptr[3] && ptr[4] == o.ptr[4] && ptr[5] == o.ptr[5];
+               d.dropout_p == o.d.dropout_p && d.need_input_grad == o.d.need_input_grad && d.inference == o.d.inference &&
+               d.fusion == o.d.fusion && d.world == o.d.world && d.rank == o.d.rank && phash == o.phash && s == o.s && fold == o.fold &&
+               flash == o.flash && attn_b3 == o.attn_b3 && total == o.total && st == o.st && ptr[0] == o.ptr[0] && ptr[1] == o.ptr[1] &&
+               ptr[2] == o.ptr[2] && ptr[3] == o.ptr[3] && ptr[4] == o.ptr[4] && ptr[5] == o.ptr[5];
     }
 };
 struct GraphEntry { GraphKey key; hipGraphExec_t exec = nullptr; unsigned long long stamp = 0; bool seen_only = true; };
@@ -584,78 +661,90 @@ extern "C" size_t bbbp_mixed_workspace_bytes(const bbbp_mixed_desc* d) {
     return p.total;
 }
 
-// `plan`: made from `d` and checked against the arguments and the workspace size by the caller (bbbp_mixed_forward)
-static int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& plan, const float* const* P, float* const* bn_running,
-                           const float* fingerprint, const float* image, float* out, void* workspace) {
-    SeedScope seed_scope(reinterpret_cast<const unsigned long long*>(static_cast<char*>(workspace) + plan.seed_slot));
-    Ctx c{static_cast<hipStream_t>(stream), static_cast<char*>(workspace), &plan};
-    const PIdx ix(d);
-    // a deferred optimizer slice that is NOT this model's image-FC weight (another model's step, another tensor): wait before anything runs
-    if (bbbp_param_pending_elsewhere(P[ix.ifc_w()])) (void)bbbp_param_wait(c.st, nullptr);
-    const int B = plan.B, F = plan.F, NH = plan.NH, D = plan.D, DFF = plan.DFF;
-    const int Bk = (int)plan.Bg;            // attention keys: this rank's rows, or every rank's in exact-global-batch mode
-    const float p_drop = plan.drop ? d->dropout_p : 0.f;
-    const float scale = 1.0f / sqrtf((float)D);
+namespace {
 
-    // ---- fingerprint branch: encoder (R:75-78, 110-111), on the side stream -------------------
-    Ctx ce = c;
-    SideStream* ss = nullptr;
-    // Screening plans (forward-only, 2048+ rows on the bf16 attention kernel) run on ONE stream: there both branches are bound by the matrix
-    // pipe, so the second stream only time-shares it -- measured equal on one box (6.66 / 6.83 ms overlapped, 6.59 / 6.85 one stream) and
-    // WORSE than the sum of the branches on others (7.6 ms against 5.29 + 1.85 + 0.06; profiles/r03_config5_streams.txt); alone, the
-    // encoder also takes the out_proj fold's gain (fold mask bit 1).  BBBP_SCREEN_OVERLAP=1 restores the two-stream schedule.
-    static const bool screen_overlap = bbbp_env_int("BBBP_SCREEN_OVERLAP", 0) != 0;
-    if (overlap_enabled() && (screen_overlap || !plan.attn_b3)) {
+// the absorbed LayerNorm that the next Linear of the launch-per-op forward chain still has to apply (z == nullptr: none)
+struct PendingNorm { const float* z = nullptr; const float* gamma = nullptr; const float* beta = nullptr; float* y = nullptr; float* mean = nullptr; float* rstd = nullptr; };
+
+// One whole-model call: what every part of the step reads.  `c` (the caller's stream) carries the image branch, the fusion block and the
+// head; `ce` the fingerprint branch's dependency chain; `cl` (backward only) the LEAVES -- weight and bias gradients, LayerNorm parameter
+// gradients -- which nothing downstream waits for, so the chain's critical path is half as long.  Without overlap all three are the
+// caller's stream.  `plan`: made from `d` and checked against the arguments and the workspace size by the caller (bbbp_mixed_forward).
+struct Step {
+    const bbbp_mixed_desc* d; const Plan& plan; const Schedule& s; const float* const* P; float* const* G;
+    const float* fingerprint; const float* image;
+    const PIdx ix;
+    Ctx c, ce, cl;
+    SideStream* ss = nullptr; DeviceState* ds = nullptr;          // ds: this device's gradient-bucket events (backward)
+    const int B, F, NH, D, DFF;
+    const int Bk;                       // attention keys: this rank's rows, or every rank's in exact-global-batch mode
+    const float p_drop, inv_keep, scale;
+    float *comb, *hid, *fused, *h, *hb, *h2, *h3;
+    float *dh3 = nullptr, *dh2 = nullptr, *dhb = nullptr, *dh = nullptr, *dfused = nullptr, *dcomb = nullptr, *dlogit = nullptr, *dpre = nullptr;
+
+    Step(void* stream, const bbbp_mixed_desc* desc, const Plan& pl, const Schedule& sc, const float* const* params, float* const* grads,
+         const float* fp, const float* img, void* workspace)
+        : d(desc), plan(pl), s(sc), P(params), G(grads), fingerprint(fp), image(img), ix(desc),
+          c{static_cast<hipStream_t>(stream), static_cast<char*>(workspace), &pl, &sc}, ce(c), cl(c), B(pl.B), F(pl.F), NH(pl.NH), D(pl.D),
+          DFF(pl.DFF), Bk((int)pl.Bg), p_drop(pl.drop ? desc->dropout_p : 0.f), inv_keep(pl.drop ? 1.f / (1.f - p_drop) : 1.f),
+          scale(1.0f / sqrtf((float)pl.D)), comb(c.f(pl.combined)), hid(c.f(pl.hid)), fused(c.f(pl.fused) /* == combined under torch.cat fusion */),
+          h(c.f(pl.h)), hb(c.f(pl.hb)), h2(c.f(pl.h2)), h3(c.f(pl.h3)) {
+        if (!grads || pl.inference) return;
+        dh3 = c.f(pl.dh3); dh2 = c.f(pl.dh2); dhb = c.f(pl.dhb); dh = c.f(pl.dh); dfused = c.f(pl.dfused); dcomb = c.f(pl.dcomb);
+        dlogit = c.f(pl.dlogit); dpre = c.f(pl.dpre);
+    }
+
+    // the chain stream (and, `leaves`, the leaf stream) start after the caller's prior work
+    int fork(bool leaves) {
+        if (!s.overlap) return BBBP_OK;
         TRY(get_side(&ss));
         TRY(fork_side(c.st, ss));
-        ce.st = ss->s;
-        ce.side = 1;
+        ce.st = ss->s; ce.side = 1;
+        if (leaves) { TRY(after(ss, c.st, ss->leaf)); cl.st = ss->leaf; cl.side = 2; }
+        return BBBP_OK;
     }
-    std::optional<Partition> part;           // scoped sections / partitions end early with reset(), or at any return
-    part.emplace(ss != nullptr);
-    float* comb = c.f(plan.combined);
-
-    // ---- image branch (R:84-94, 114-115): enqueued first so the GPU is busy while the host feeds the encoder's launches -------------------------------------------------------
-    float* pool1 = c.f(plan.pool1); float* pool2 = c.f(plan.pool2);
-    {
-        Section s1(c.st, SEC_CONV1_FWD);
-        // beside a training step's encoder chain the f32 form stays (common.h: ConvPrefs::conv1_fwd_f32); screening batches, eval loops and
-        // the encoder-less two-branch model take the split-bf16 form when the conv mask selects it (bit 6, default)
-        // (the rule looks at the plan only, not at the stream mode: one stream or three give bit-identical steps)
-        // round 4: training steps run the software-pipelined split-bf16 kernel (conv_b3c1.hip) too, ONE work-group per CU beside the chain
-        // (BBBP_C1_TRAIN=0: the f32 kernel of rounds 1-3 there; 2: two work-groups per CU, measured slower for the step)
-        static const int c1_train = bbbp_env_int("BBBP_C1_TRAIN", 1);      // default 1: step 2.517 -> 2.487 ms (profiles/r04_c1_pipe.txt)
-        const bool beside_chain = !plan.inference && plan.L > 0;
-        ConvPrefs prefs;
-        prefs.conv1_fwd_f32 = (beside_chain && !c1_train) ? 1 : 0;
-        prefs.conv1_fwd_per_cu = (beside_chain && c1_train) ? (c1_train >= 2 ? 2 : 1) : 0;      // BBBP_C1_TRAIN=2: two work-groups per CU there too
-        TRY(conv3x3_relu_pool_fwd(c.st, image, P[ix.c1_w()], P[ix.c1_b()], pool1, plan.inference ? nullptr : c.u8(plan.mask1), B, 3, C1, IMG, IMG,
-                                  c.scratch(), c.scratch_bytes(), prefs));
+    // parameter tensor k of encoder layer l, and its gradient
+    const float* PL(int l, int k) const { return P[ix.layer(l, k)]; }
+    float* GL(int l, int k) const { return G[ix.layer(l, k)]; }
+    // the fields that the four per-layer argument tables of the fused encoder schedules (row / sliced, forward / backward) share
+    template <typename A> void fill_layer(A& a, int l) const {
+        const LayerOff& o = plan.layer[l];
+        a.wo = PL(l, L_OUTW); a.g1 = PL(l, L_N1W); a.w1 = PL(l, L_W1); a.w2 = PL(l, L_W2); a.g2 = PL(l, L_N2W);
+        a.z1 = c.f(o.z1); a.hff = c.f(o.hff); a.z2 = c.f(o.z2); a.mean1 = c.f(o.mean1); a.rstd1 = c.f(o.rstd1); a.mean2 = c.f(o.mean2); a.rstd2 = c.f(o.rstd2);
+        a.seed1 = site_seed(l, 1); a.seed3 = site_seed(l, 3);
     }
-    {
-        Section s2(c.st, SEC_CONV2_FWD);
-        // round 4: beside a training step's encoder chain the software-pipelined one-work-group-per-CU kernel (conv_b3.hip): 0.40 instead of
-        // 0.387 ms alone, but the chain -- the forward half's critical path -- keeps three quarters of every SIMD: step 2.41 -> 2.34 ms
-        // (profiles/r04_conv2_pipe.txt).  BBBP_C2_TRAIN=0: the two-work-group kernel there too.  Bit-identical outputs either way.
-        static const int c2_train = bbbp_env_int("BBBP_C2_TRAIN", 1);
-        ConvPrefs prefs;
-        prefs.conv2_fwd_pipe = (!plan.inference && plan.L > 0 && c2_train) ? 1 : 0;
-        TRY(conv3x3_relu_pool_fwd(c.st, pool1, P[ix.c2_w()], P[ix.c2_b()], pool2, plan.inference ? nullptr : c.u8(plan.mask2), B, C1, C2, IMG / 2,
-                                  IMG / 2, c.scratch(), c.scratch_bytes(), prefs));
+    // exact-global-batch mode: the blocks of every rank (forward: (mean, M2); backward: the BatchNorm's two sums, which span every rank's
+    // rows) are gathered between the fused head's two launches.  `what`: BBBP_COLL_BN_FWD / BBBP_COLL_BN_BWD
+    bbbp_head_sync head_sync(int what) const {
+        bbbp_head_sync sync;
+        sync.world = plan.world; sync.rank = plan.rank;
+        if (plan.exact)
+            sync.between = [this, what]() -> int {
+                const size_t pcount = (size_t)((B + 15) / 16) * 2 * H1;
+                return run_collective(d, BBBP_COLL_ALLGATHER, what, -1, plan.head_partial + (size_t)plan.rank * pcount * sizeof(float), plan.head_partial, pcount, c.st);
+            };
+        return sync;
     }
-    {
+    // ---- forward: image branch (R:84-94, 114-115), caller's stream ------------------------------------------------
+    int image_fwd() {
+        float* pool1 = c.f(plan.pool1); float* pool2 = c.f(plan.pool2);
+        {
+            Section s1(c.st, SEC_CONV1_FWD);
+            TRY(conv3x3_relu_pool_fwd(c.st, image, P[ix.c1_w()], P[ix.c1_b()], pool1, plan.inference ? nullptr : c.u8(plan.mask1), B, 3, C1, IMG, IMG,
+                                      c.scratch(), c.scratch_bytes(), s.conv1_fwd));
+        }
+        {
+            Section s2(c.st, SEC_CONV2_FWD);
+            TRY(conv3x3_relu_pool_fwd(c.st, pool1, P[ix.c2_w()], P[ix.c2_b()], pool2, plan.inference ? nullptr : c.u8(plan.mask2), B, C1, C2, IMG / 2,
+                                      IMG / 2, c.scratch(), c.scratch_bytes(), s.conv2_fwd));
+        }
         Section s3(c.st, SEC_IMGFC_FWD);
         (void)bbbp_param_wait(c.st, P[ix.ifc_w()]);        // the optimizer's deferred image-FC slice (bbbp_adamw_step_deferred): first read here
-        TRY(linear_fwd(c, pool2, IMG_FLAT, P[ix.ifc_w()], P[ix.ifc_b()], comb + FC, COMB, B, FC, IMG_FLAT, BBBP_ACT_RELU));
+        return linear_fwd(c, pool2, IMG_FLAT, P[ix.ifc_w()], P[ix.ifc_b()], comb + FC, COMB, B, FC, IMG_FLAT, BBBP_ACT_RELU);
     }
-
-
-    // ---- fingerprint branch body (side stream)
-    const float* x = fingerprint;
-    std::optional<Section> sec_enc;
-    sec_enc.emplace(ce.st, SEC_ENCODER_FWD);
-    const bool sliced = sliced_encoder(plan) && plan.sl_sync;
-    if (sliced) {
+    // ---- forward: fingerprint branch = encoder (R:75-78, 110-111) + fingerprint_fc, chain stream; one function per schedule ----
+    // the whole chain of a small batch, fingerprint_fc included, as one persistent launch
+    int encoder_fwd_sliced() {
         bbbp_enc_sliced_fwd_args a;
         memset(&a, 0, sizeof(a));
         a.x0 = fingerprint; a.L = plan.L; a.B = B; a.F = F; a.DFF = DFF; a.p = p_drop; a.scale = scale;
@@ -664,97 +753,72 @@ static int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& p
         for (int l = 0; l < plan.L; ++l) {
             const LayerOff& o = plan.layer[l];
             bbbp_enc_sliced_layer& y = a.lay[l];
-            y.win = P[ix.layer(l, L_INW)]; y.bin = P[ix.layer(l, L_INB)]; y.wo = P[ix.layer(l, L_OUTW)]; y.bo = P[ix.layer(l, L_OUTB)];
-            y.g1 = P[ix.layer(l, L_N1W)]; y.be1 = P[ix.layer(l, L_N1B)]; y.w1 = P[ix.layer(l, L_W1)]; y.b1 = P[ix.layer(l, L_B1)];
-            y.w2 = P[ix.layer(l, L_W2)]; y.b2 = P[ix.layer(l, L_B2)]; y.g2 = P[ix.layer(l, L_N2W)]; y.be2 = P[ix.layer(l, L_N2B)];
-            y.qkv = c.f(o.qkv); y.prob = c.f(o.prob); y.pd = c.f(o.pd); y.ctx = c.f(o.ctx); y.z1 = c.f(o.z1); y.y1 = c.f(o.y1);
-            y.hff = c.f(o.hff); y.z2 = c.f(o.z2); y.y2 = c.f(o.y2); y.mean1 = c.f(o.mean1); y.rstd1 = c.f(o.rstd1);
-            y.mean2 = c.f(o.mean2); y.rstd2 = c.f(o.rstd2);
-            y.seed0 = site_seed(d->seed, l, 0); y.seed1 = site_seed(d->seed, l, 1); y.seed2 = site_seed(d->seed, l, 2); y.seed3 = site_seed(d->seed, l, 3);
+            fill_layer(y, l);
+            y.win = PL(l, L_INW); y.qkv = c.f(o.qkv); y.prob = c.f(o.prob); y.pd = c.f(o.pd); y.seed0 = site_seed(l, 0);
+            y.bin = PL(l, L_INB); y.bo = PL(l, L_OUTB); y.be1 = PL(l, L_N1B); y.b1 = PL(l, L_B1); y.b2 = PL(l, L_B2); y.be2 = PL(l, L_N2B);
+            y.ctx = c.f(o.ctx); y.y1 = c.f(o.y1); y.y2 = c.f(o.y2); y.seed2 = site_seed(l, 2);
         }
-        TRY(bbbp_enc_sliced_fwd(ce.st, &a));
+        return bbbp_enc_sliced_fwd(ce.st, &a);
     }
-    if (plan.fold) {
-        // W' = Wo Wv, b' = Wo bv of every layer in one launch at the head of the chain (the parameters change every step)
-        const float* win[32]; const float* bin[32]; const float* wo[32]; const float* bo[32]; float* wf[32]; float* bf[32]; float* wvt[32];
-        for (int l = 0; l < plan.L; ++l) {
-            win[l] = P[ix.layer(l, L_INW)]; bin[l] = P[ix.layer(l, L_INB)]; wo[l] = P[ix.layer(l, L_OUTW)];
-            // fused attention (forward-only, no dropout): softmax rows sum to one, so out_proj's bias is carried by b' = Wo bv + bo
-            bo[l] = plan.attn_b3 ? P[ix.layer(l, L_OUTB)] : nullptr;
-            wf[l] = c.f(plan.fwf[l]); bf[l] = c.f(plan.fbf[l]); wvt[l] = c.f(plan.fwvt[l]);
-        }
-        TRY(bbbp_outproj_fold(ce.st, plan.L, F, win, bin, wo, bo, wf, bf, wvt));
-    }
-    const bool fused_rows = !sliced && fused_encoder(plan);
-    if (fused_rows) {
+    // attention launch-per-op, the row-local rest of a layer as one launch
+    int encoder_fwd_rows() {
+        const float* x = fingerprint;
         // in_proj of layer 0; every later in_proj (and fingerprint_fc) is the tail of the previous layer's row kernel
-        TRY(linear_fwd(ce, x, F, P[ix.layer(0, L_INW)], P[ix.layer(0, L_INB)], c.f(plan.layer[0].qkv), 3 * F, B, 3 * F, F, 0));
+        TRY(linear_fwd(ce, x, F, PL(0, L_INW), PL(0, L_INB), c.f(plan.layer[0].qkv), 3 * F, B, 3 * F, F, 0));
         for (int l = 0; l < plan.L; ++l) {
             const LayerOff& o = plan.layer[l];
-            float* qkv = c.f(o.qkv); float* prob = c.f(o.prob); float* ctx = c.f(o.ctx); float* pd = c.f(o.pd);
-            TRY(bbbp_gemm_f32(ce.st, 0, 1, B, B, D, scale, qkv, 3 * F, qkv + F, 3 * F, prob, B, nullptr, nullptr, 0, 0, NH, D, D,
-                              (long)B * B, 0, ce.scratch(), ce.scratch_bytes()));
-            TRY(bbbp_softmax_fwd(ce.st, prob, pd, (long)NH * B, B, p_drop, site_seed(d->seed, l, 0)));
-            TRY(bbbp_gemm_f32(ce.st, 0, 0, B, D, B, 1.f, pd, B, qkv + 2 * F, 3 * F, ctx, F, nullptr, nullptr, 0, 0, NH, (long)B * B,
-                              D, D, 0, ce.scratch(), ce.scratch_bytes()));
+            TRY(attention_fwd_gemm(l, x));
             bbbp_enc_row_fwd_args a;
-            a.ctx = ctx; a.xin = x;
-            a.wo = P[ix.layer(l, L_OUTW)]; a.bo = P[ix.layer(l, L_OUTB)]; a.g1 = P[ix.layer(l, L_N1W)]; a.be1 = P[ix.layer(l, L_N1B)];
-            a.w1 = P[ix.layer(l, L_W1)]; a.b1 = P[ix.layer(l, L_B1)]; a.w2 = P[ix.layer(l, L_W2)]; a.b2 = P[ix.layer(l, L_B2)];
-            a.g2 = P[ix.layer(l, L_N2W)]; a.be2 = P[ix.layer(l, L_N2B)];
+            fill_layer(a, l);
+            a.ctx = c.f(o.ctx); a.xin = x;
+            a.bo = PL(l, L_OUTB); a.be1 = PL(l, L_N1B); a.b1 = PL(l, L_B1); a.b2 = PL(l, L_B2); a.be2 = PL(l, L_N2B);
             const bool last = l + 1 == plan.L;
-            a.wn = last ? P[ix.fpfc_w()] : P[ix.layer(l + 1, L_INW)]; a.bn = last ? P[ix.fpfc_b()] : P[ix.layer(l + 1, L_INB)];
+            a.wn = last ? P[ix.fpfc_w()] : PL(l + 1, L_INW); a.bn = last ? P[ix.fpfc_b()] : PL(l + 1, L_INB);
             a.outn = last ? comb : c.f(plan.layer[l + 1].qkv); a.nn = last ? FC : 3 * F; a.ldn = last ? COMB : 3 * F; a.actn = last ? 1 : 0;
-            a.z1 = c.f(o.z1); a.y1 = c.f(o.y1); a.hff = c.f(o.hff); a.z2 = c.f(o.z2); a.y2 = c.f(o.y2);
-            a.mean1 = c.f(o.mean1); a.rstd1 = c.f(o.rstd1); a.mean2 = c.f(o.mean2); a.rstd2 = c.f(o.rstd2);
-            a.B = B; a.F = F; a.DFF = DFF; a.p = p_drop;
-            a.seed1 = site_seed(d->seed, l, 1); a.seed2 = site_seed(d->seed, l, 2); a.seed3 = site_seed(d->seed, l, 3);
+            a.y1 = c.f(o.y1); a.y2 = c.f(o.y2);
+            a.B = B; a.F = F; a.DFF = DFF; a.p = p_drop; a.seed2 = site_seed(l, 2);
             TRY(bbbp_enc_row_fwd(ce.st, &a));
             x = c.f(o.y2);
         }
+        return BBBP_OK;
     }
-    // LayerNorm absorbed by the Linear that consumes it (gemm.hip: gemm_direct_lna_kernel; BBBP_LN_ABSORB=0 keeps the stand-alone launches):
-    // norm1 -> linear1, norm2 -> the next in_proj / fingerprint_fc.  The dropout + residual that the LayerNorm launch applied to its input
-    // move into the epilogue of the GEMM that produces it (same Philox elements), so z1 / z2, y1 / y2 and the row statistics the backward
-    // pass reads are the same tensors as before.
-    struct { const float* z; const float* gamma; const float* beta; float* y; float* mean; float* rstd; } pend = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const bool lna_ok = ln_absorb_on() && !plan.exact && plan.L > 0 && bbbp_layernorm_linear_preferred(B, DFF, F) && bbbp_layernorm_linear_preferred(B, 3 * F, F) &&
-                        bbbp_layernorm_linear_preferred(B, FC, F) &&
-                        // training: the producers' dropout rides in the small-product GEMM's epilogue only
-                        (!plan.drop || (bbbp_gemm_folds_asum(B, F, DFF, 1) && bbbp_gemm_folds_asum(B, F, plan.fold ? Bk : F, 1)));
-    for (int l = 0; l < ((fused_rows || sliced) ? 0 : plan.L); ++l) {
-        const LayerOff& o = plan.layer[l];
-        float* qkv = c.f(o.qkv); float* prob = c.f(o.prob); float* ctx = c.f(o.ctx);
-        const bool absorb1 = lna_ok && !(plan.attn_b3 && plan.fold);      // (that attention kernel writes z1 itself: no epilogue for the residual)
-        const bool absorb2 = lna_ok;
-        {
-            Section sq(ce.st, SEC_QKV_FWD);
-            // folded plan: [Q | K | VW] = x [Wq; Wk; Wo Wv]^T + [bq; bk; Wo bv]
-            const float* w_in = plan.fold ? c.f(plan.fwf[l]) : P[ix.layer(l, L_INW)];
-            const float* b_in = plan.fold ? c.f(plan.fbf[l]) : P[ix.layer(l, L_INB)];
-            if (pend.z) {
-                // the previous layer's norm2 is absorbed here: x = LayerNorm(z2) is written by the same launch (round 4)
-                TRY(bbbp_layernorm_linear_fwd(ce.st, pend.z, F, pend.gamma, pend.beta, 1e-5f, w_in, b_in, qkv, 3 * F, 0, 0.f, 0, pend.y, F, pend.mean,
-                                              pend.rstd, B, 3 * F, F));
-                pend.z = nullptr;
-            } else {
-                TRY(linear_fwd(ce, x, F, w_in, b_in, qkv, 3 * F, B, 3 * F, F, 0));
+    int encoder_fwd_ops() {
+        if (plan.fold) {
+            // W' = Wo Wv, b' = Wo bv of every layer in one launch at the head of the chain (the parameters change every step)
+            const float* win[32]; const float* bin[32]; const float* wo[32]; const float* bo[32]; float* wf[32]; float* bf[32]; float* wvt[32];
+            for (int l = 0; l < plan.L; ++l) {
+                win[l] = PL(l, L_INW); bin[l] = PL(l, L_INB); wo[l] = PL(l, L_OUTW);
+                // fused attention (forward-only, no dropout): softmax rows sum to one, so out_proj's bias is carried by b' = Wo bv + bo
+                bo[l] = plan.attn_b3 ? PL(l, L_OUTB) : nullptr;
+                wf[l] = c.f(plan.fwf[l]); bf[l] = c.f(plan.fbf[l]); wvt[l] = c.f(plan.fwvt[l]);
             }
+            TRY(bbbp_outproj_fold(ce.st, plan.L, F, win, bin, wo, bo, wf, bf, wvt));
         }
-        std::optional<Section> sec_attn;
-        sec_attn.emplace(ce.st, SEC_ATTN_FWD);
-        if (plan.attn_b3) {
-            TRY(bbbp_attn_b3_fwd(ce.st, qkv, plan.fold ? c.f(o.z1) : ctx, B, F, NH, scale, plan.attn_part_bytes ? c.f(plan.attn_part) : nullptr, plan.attn_part_bytes));
-        } else if (plan.flash) {
-            TRY(bbbp_attn_small_fwd(ce.st, qkv, ctx, c.f(o.lse), B, F, NH, scale, p_drop, site_seed(d->seed, l, 0), o.keep ? c.u8(o.keep) : nullptr));
-        } else {
+        const float* x = fingerprint;
+        PendingNorm pend;
+        for (int l = 0; l < plan.L; ++l) TRY(encoder_layer_fwd_ops(l, x, pend));
+        return fingerprint_fc_fwd(x, pend);
+    }
+    // x = LayerNorm(pend.z) (written to pend.y) where a norm2 is pending; y = act(x W^T + b) in the same launch then
+    int linear_after_norm(PendingNorm& pend, const float* x, const float* W, const float* b, float* y, int ldy, int N, int act) {
+        if (!pend.z) return linear_fwd(ce, x, F, W, b, y, ldy, B, N, F, act);
+        const float* z = pend.z;
+        pend.z = nullptr;
+        return bbbp_layernorm_linear_fwd(ce.st, z, F, pend.gamma, pend.beta, 1e-5f, W, b, y, ldy, act, 0.f, 0, pend.y, F, pend.mean, pend.rstd, B, N, F);
+    }
+    // fingerprint_fc (R:79-82, 112) -> combined[:, 0:128]
+    int fingerprint_fc_fwd(const float* x, PendingNorm& pend) { return linear_after_norm(pend, x, P[ix.fpfc_w()], P[ix.fpfc_b()], comb, COMB, FC, BBBP_ACT_RELU); }
+    // scores -> softmax (+ dropout) -> context with materialised probabilities: into ctx, or (folded plan, one head) z1 = Pd VW + bo
+    // (the row-fused schedule's attention too: never folded, absorbed or exact there)
+    int attention_fwd_gemm(int l, const float* x) {
+        const LayerOff& o = plan.layer[l];
+        float* qkv = c.f(o.qkv); float* prob = c.f(o.prob);
         // keys and values: this rank's rows of qkv, or (exact-global-batch mode) the rows of every rank, gathered once per layer
         const float* kmat = qkv + F; const float* vmat = qkv + 2 * F; int ldkv = 3 * F;
         if (plan.exact) {
             float* kvg = c.f(o.kvg);
             const long n = (long)B * 2 * F;
-            hipLaunchKernelGGL(kv_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), g_bbbp_small_lds_pad, ce.st, qkv,
-                               kvg + (size_t)plan.rank * n, n, F);
+            hipLaunchKernelGGL(kv_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), g_bbbp_small_lds_pad, ce.st, qkv, kvg + (size_t)plan.rank * n, n, F);
             BBBP_CHECK_LAUNCH();
             TRY(run_collective(d, BBBP_COLL_ALLGATHER, BBBP_COLL_KV, l, o.kvg + (size_t)plan.rank * n * sizeof(float), o.kvg, (size_t)n, ce.st));
             kmat = kvg; vmat = kvg + F; ldkv = 2 * F;
@@ -763,344 +827,271 @@ static int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& p
         TRY(bbbp_gemm_f32(ce.st, 0, 1, B, Bk, D, scale, qkv, 3 * F, kmat, ldkv, prob, Bk, nullptr, nullptr, 0, 0, NH, D, D,
                           (long)B * Bk, 0, ce.scratch(), ce.scratch_bytes()));
         float* pd = c.f(o.pd);
-        TRY(bbbp_softmax_fwd(ce.st, prob, pd, (long)NH * B, Bk, p_drop, site_seed(d->seed, l, 0)));
+        TRY(bbbp_softmax_fwd(ce.st, prob, pd, (long)NH * B, Bk, p_drop, site_seed(l, 0)));
         // ctx_h = Pd_h V_h; folded plan (one head): z1 = Pd VW + bo, the out_proj output itself
-        if (plan.fold && absorb1) {
-            // ... and with norm1 absorbed by linear1, z1 = dropout(Pd VW + bo) + x: what bbbp_layernorm_fwd would have left in z1
-            bbbp_gemm_desc g = gemm_desc(0, 0, B, D, Bk, 1.f, pd, Bk, vmat, ldkv, c.f(o.z1), F, 1, 0, 0, 0);
-            g.bias = P[ix.layer(l, L_OUTB)]; g.residual = x; g.ldr = F; g.drop_p = p_drop; g.drop_seed = site_seed(d->seed, l, 1);
-            TRY(bbbp_gemm_f32_grouped(ce.st, &g, 1, ce.scratch(), ce.scratch_bytes()));
-        } else {
-        TRY(bbbp_gemm_f32(ce.st, 0, 0, B, D, Bk, 1.f, pd, Bk, vmat, ldkv, plan.fold ? c.f(o.z1) : ctx, F, plan.fold ? P[ix.layer(l, L_OUTB)] : nullptr,
-                          nullptr, 0, 0, NH, (long)B * Bk, D, D, 0, ce.scratch(), ce.scratch_bytes()));
+        if (!(plan.fold && s.absorb1))
+            return bbbp_gemm_f32(ce.st, 0, 0, B, D, Bk, 1.f, pd, Bk, vmat, ldkv, plan.fold ? c.f(o.z1) : c.f(o.ctx), F, plan.fold ? PL(l, L_OUTB) : nullptr,
+                                 nullptr, 0, 0, NH, (long)B * Bk, D, D, 0, ce.scratch(), ce.scratch_bytes());
+        // ... and with norm1 absorbed by linear1, z1 = dropout(Pd VW + bo) + x: what bbbp_layernorm_fwd would have left in z1
+        bbbp_gemm_desc g = gemm_desc(0, 0, B, D, Bk, 1.f, pd, Bk, vmat, ldkv, c.f(o.z1), F, 1, 0, 0, 0);
+        g.bias = PL(l, L_OUTB); g.residual = x; g.ldr = F; g.drop_p = p_drop; g.drop_seed = site_seed(l, 1);
+        return bbbp_gemm_f32_grouped(ce.st, &g, 1, ce.scratch(), ce.scratch_bytes());
+    }
+    // one layer of the launch-per-op schedule; x: the layer's input on entry, its output on return.
+    // LayerNorm absorbed by the Linear that consumes it (s.absorb1 / s.absorb2; gemm.hip: gemm_direct_lna_kernel): norm1 -> linear1, norm2 ->
+    // the next in_proj / fingerprint_fc.  The dropout + residual that the LayerNorm launch applied to its input move into the epilogue of the
+    // GEMM that produces it (same Philox elements), so z1 / z2, y1 / y2 and the row statistics the backward pass reads are the same tensors.
+    int encoder_layer_fwd_ops(int l, const float*& x, PendingNorm& pend) {
+        const LayerOff& o = plan.layer[l];
+        float* qkv = c.f(o.qkv); float* ctx = c.f(o.ctx);
+        {
+            Section sq(ce.st, SEC_QKV_FWD);
+            // folded plan: [Q | K | VW] = x [Wq; Wk; Wo Wv]^T + [bq; bk; Wo bv]; the previous layer's absorbed norm2 is applied by the same launch
+            TRY(linear_after_norm(pend, x, plan.fold ? c.f(plan.fwf[l]) : PL(l, L_INW), plan.fold ? c.f(plan.fbf[l]) : PL(l, L_INB), qkv, 3 * F, 3 * F, 0));
         }
-        }
-        sec_attn.reset();
-        float* z1 = c.f(o.z1); float* y1 = c.f(o.y1);
-        // out_proj -> (dropout) + residual -> norm1: one launch when the output is narrow (gemm.hip: gemm_direct_ln_kernel)
-        // OPT-IN (BBBP_FUSED_LINEAR_LN=1), measured slower at B = 512: the 11-wave work-groups need three wave slots on three SIMDs of a CU
-        // beside the resident conv work-groups (encoder forward 0.98 -> 1.15 ms in the step, 0.58 -> 0.60 alone); linear2 -> norm2 is never
-        // fused (one wave per tile walking K = 2048 alone: 90 us against 22 + 4)
-        static const bool ln_opt_in = bbbp_env_int("BBBP_FUSED_LINEAR_LN", 0) != 0;
-        const bool ln_fused = !plan.fold && ln_opt_in && bbbp_linear_layernorm_supported(B, F, F) && F <= 512;
-        if (ln_fused) {
-            TRY(bbbp_linear_layernorm_fwd(ce.st, ctx, F, P[ix.layer(l, L_OUTW)], P[ix.layer(l, L_OUTB)], x, F, z1, F, y1, F, P[ix.layer(l, L_N1W)],
-                                          P[ix.layer(l, L_N1B)], c.f(o.mean1), c.f(o.rstd1), B, F, F, 1e-5f, p_drop, site_seed(d->seed, l, 1)));
-        } else {
-        if (!plan.fold) {
-            Section so(ce.st, SEC_OUTPROJ_FWD);
-            if (absorb1) {
-                bbbp_gemm_desc g = gemm_desc(0, 1, B, F, F, 1.f, ctx, F, P[ix.layer(l, L_OUTW)], F, z1, F, 1, 0, 0, 0);
-                g.bias = P[ix.layer(l, L_OUTB)]; g.residual = x; g.ldr = F; g.drop_p = p_drop; g.drop_seed = site_seed(d->seed, l, 1);
-                TRY(bbbp_gemm_f32_grouped(ce.st, &g, 1, ce.scratch(), ce.scratch_bytes()));
+        {
+            Section sec_attn(ce.st, SEC_ATTN_FWD);
+            if (plan.attn_b3) {
+                TRY(bbbp_attn_b3_fwd(ce.st, qkv, plan.fold ? c.f(o.z1) : ctx, B, F, NH, scale, plan.attn_part_bytes ? c.f(plan.attn_part) : nullptr, plan.attn_part_bytes));
+            } else if (plan.flash) {
+                TRY(bbbp_attn_small_fwd(ce.st, qkv, ctx, c.f(o.lse), B, F, NH, scale, p_drop, site_seed(l, 0), o.keep ? c.u8(o.keep) : nullptr));
             } else {
-                TRY(linear_fwd(ce, ctx, F, P[ix.layer(l, L_OUTW)], P[ix.layer(l, L_OUTB)], z1, F, B, F, F, 0));
+                TRY(attention_fwd_gemm(l, x));
             }
         }
-        if (!absorb1) {
-        Section sl(ce.st, SEC_LN_FWD);
-        TRY(bbbp_layernorm_fwd(ce.st, z1, x, y1, P[ix.layer(l, L_N1W)], P[ix.layer(l, L_N1B)], c.f(o.mean1), c.f(o.rstd1), B, F,
-                               1e-5f, p_drop, site_seed(d->seed, l, 1)));
-        }
+        float* z1 = c.f(o.z1); float* y1 = c.f(o.y1);
+        if (s.ln_fused) {
+            // out_proj -> (dropout) + residual -> norm1: one launch when the output is narrow (gemm.hip: gemm_direct_ln_kernel)
+            TRY(bbbp_linear_layernorm_fwd(ce.st, ctx, F, PL(l, L_OUTW), PL(l, L_OUTB), x, F, z1, F, y1, F, PL(l, L_N1W),
+                                          PL(l, L_N1B), c.f(o.mean1), c.f(o.rstd1), B, F, F, 1e-5f, p_drop, site_seed(l, 1)));
+        } else {
+            if (!plan.fold) {
+                Section so(ce.st, SEC_OUTPROJ_FWD);
+                if (s.absorb1) {
+                    bbbp_gemm_desc g = gemm_desc(0, 1, B, F, F, 1.f, ctx, F, PL(l, L_OUTW), F, z1, F, 1, 0, 0, 0);
+                    g.bias = PL(l, L_OUTB); g.residual = x; g.ldr = F; g.drop_p = p_drop; g.drop_seed = site_seed(l, 1);
+                    TRY(bbbp_gemm_f32_grouped(ce.st, &g, 1, ce.scratch(), ce.scratch_bytes()));
+                } else {
+                    TRY(linear_fwd(ce, ctx, F, PL(l, L_OUTW), PL(l, L_OUTB), z1, F, B, F, F, 0));
+                }
+            }
+            if (!s.absorb1) {
+                Section sl(ce.st, SEC_LN_FWD);
+                TRY(bbbp_layernorm_fwd(ce.st, z1, x, y1, PL(l, L_N1W), PL(l, L_N1B), c.f(o.mean1), c.f(o.rstd1), B, F, 1e-5f, p_drop, site_seed(l, 1)));
+            }
         }
         float* hff = c.f(o.hff); float* z2 = c.f(o.z2); float* y2 = c.f(o.y2);
         // linear1 + ReLU (+ the FFN dropout in the same epilogue when the product takes the small-GEMM path: same Philox elements as bbbp_dropout)
-        const bool drop_in_gemm = plan.drop && bbbp_gemm_folds_asum(B, DFF, F, 1);
         {
             Section sf(ce.st, SEC_FFN1_FWD);
-            if (absorb1) {
+            if (s.absorb1) {
                 // norm1 absorbed: hff = dropout(ReLU(LayerNorm(z1) W1^T + b1)); y1, mean1, rstd1 written by the same launch
-                TRY(bbbp_layernorm_linear_fwd(ce.st, z1, F, P[ix.layer(l, L_N1W)], P[ix.layer(l, L_N1B)], 1e-5f, P[ix.layer(l, L_W1)], P[ix.layer(l, L_B1)],
-                                              hff, DFF, BBBP_ACT_RELU, p_drop, site_seed(d->seed, l, 2), y1, F, c.f(o.mean1), c.f(o.rstd1), B, DFF, F));
-            } else if (drop_in_gemm) {
-                bbbp_gemm_desc g = gemm_desc(0, 1, B, DFF, F, 1.f, y1, F, P[ix.layer(l, L_W1)], F, hff, DFF, 1, 0, 0, 0);
-                g.bias = P[ix.layer(l, L_B1)]; g.act = BBBP_ACT_RELU; g.drop_p = p_drop; g.drop_seed = site_seed(d->seed, l, 2);
+                TRY(bbbp_layernorm_linear_fwd(ce.st, z1, F, PL(l, L_N1W), PL(l, L_N1B), 1e-5f, PL(l, L_W1), PL(l, L_B1),
+                                              hff, DFF, BBBP_ACT_RELU, p_drop, site_seed(l, 2), y1, F, c.f(o.mean1), c.f(o.rstd1), B, DFF, F));
+            } else if (s.drop_in_gemm) {
+                bbbp_gemm_desc g = gemm_desc(0, 1, B, DFF, F, 1.f, y1, F, PL(l, L_W1), F, hff, DFF, 1, 0, 0, 0);
+                g.bias = PL(l, L_B1); g.act = BBBP_ACT_RELU; g.drop_p = p_drop; g.drop_seed = site_seed(l, 2);
                 TRY(bbbp_gemm_f32_grouped(ce.st, &g, 1, ce.scratch(), ce.scratch_bytes()));
             } else {
-                TRY(linear_fwd(ce, y1, F, P[ix.layer(l, L_W1)], P[ix.layer(l, L_B1)], hff, DFF, B, DFF, F, BBBP_ACT_RELU));
+                TRY(linear_fwd(ce, y1, F, PL(l, L_W1), PL(l, L_B1), hff, DFF, B, DFF, F, BBBP_ACT_RELU));
             }
         }
-        if (plan.drop && !drop_in_gemm && !absorb1) TRY(bbbp_dropout(ce.st, hff, hff, (long)B * DFF, p_drop, site_seed(d->seed, l, 2)));
+        if (plan.drop && !s.drop_in_gemm && !s.absorb1) TRY(bbbp_dropout(ce.st, hff, hff, (long)B * DFF, p_drop, site_seed(l, 2)));
         {
             Section sf(ce.st, SEC_FFN2_FWD);
-            if (absorb2) {
+            if (s.absorb2) {
                 // norm2 is absorbed by the next in_proj (or fingerprint_fc): z2 = dropout(h W2^T + b2) + y1 here, normalised there
-                bbbp_gemm_desc g = gemm_desc(0, 1, B, F, DFF, 1.f, hff, DFF, P[ix.layer(l, L_W2)], DFF, z2, F, 1, 0, 0, 0);
-                g.bias = P[ix.layer(l, L_B2)]; g.residual = y1; g.ldr = F; g.drop_p = p_drop; g.drop_seed = site_seed(d->seed, l, 3);
+                bbbp_gemm_desc g = gemm_desc(0, 1, B, F, DFF, 1.f, hff, DFF, PL(l, L_W2), DFF, z2, F, 1, 0, 0, 0);
+                g.bias = PL(l, L_B2); g.residual = y1; g.ldr = F; g.drop_p = p_drop; g.drop_seed = site_seed(l, 3);
                 TRY(bbbp_gemm_f32_grouped(ce.st, &g, 1, ce.scratch(), ce.scratch_bytes()));
-                pend.z = z2; pend.gamma = P[ix.layer(l, L_N2W)]; pend.beta = P[ix.layer(l, L_N2B)]; pend.y = y2; pend.mean = c.f(o.mean2); pend.rstd = c.f(o.rstd2);
+                pend.z = z2; pend.gamma = PL(l, L_N2W); pend.beta = PL(l, L_N2B); pend.y = y2; pend.mean = c.f(o.mean2); pend.rstd = c.f(o.rstd2);
             } else {
-                TRY(linear_fwd(ce, hff, DFF, P[ix.layer(l, L_W2)], P[ix.layer(l, L_B2)], z2, F, B, F, DFF, 0));
+                TRY(linear_fwd(ce, hff, DFF, PL(l, L_W2), PL(l, L_B2), z2, F, B, F, DFF, 0));
             }
         }
-        if (!absorb2) {
+        if (!s.absorb2) {
             Section sl(ce.st, SEC_LN_FWD);
-            TRY(bbbp_layernorm_fwd(ce.st, z2, y1, y2, P[ix.layer(l, L_N2W)], P[ix.layer(l, L_N2B)], c.f(o.mean2), c.f(o.rstd2), B, F,
-                                   1e-5f, p_drop, site_seed(d->seed, l, 3)));
+            TRY(bbbp_layernorm_fwd(ce.st, z2, y1, y2, PL(l, L_N2W), PL(l, L_N2B), c.f(o.mean2), c.f(o.rstd2), B, F, 1e-5f, p_drop, site_seed(l, 3)));
         }
         x = y2;
+        return BBBP_OK;
     }
-    // fingerprint_fc (R:79-82, 112) -> combined[:, 0:128]
-    if (!fused_rows && !sliced) {
-        if (pend.z) {
-            TRY(bbbp_layernorm_linear_fwd(ce.st, pend.z, F, pend.gamma, pend.beta, 1e-5f, P[ix.fpfc_w()], P[ix.fpfc_b()], comb, COMB, BBBP_ACT_RELU, 0.f, 0,
-                                          pend.y, F, pend.mean, pend.rstd, B, FC, F));
-            pend.z = nullptr;
-        } else {
-            TRY(linear_fwd(ce, x, F, P[ix.fpfc_w()], P[ix.fpfc_b()], comb, COMB, B, FC, F, BBBP_ACT_RELU));
-        }
-    }
-    sec_enc.reset();
-
-    if (ss) TRY(join_side(c.st, ss));        // fusion needs both halves of `combined`
-    part.reset();
-    Section sec_head(c.st, SEC_HEAD_FWD);
-
-    static const int fused_head = bbbp_env_int("BBBP_FUSED_HEAD", 1);
-    BBBP_CHECK_ARG(!plan.exact || (fused_head && NHEADS_FUSION == 4), "the exact-global-batch mode needs the fused head (BBBP_FUSED_HEAD=1)");
-    if (fused_head && NHEADS_FUSION == 4) {
-        // fusion block + head in two launches (head.hip); with torch.cat fusion the first launch starts at fc.0
+    // ---- forward: fusion block (R:60-65, 117) + regression head (R:98-107, 118), caller's stream ----------------------
+    // two launches (head.hip); with torch.cat fusion the first launch starts at fc.0
+    int head_fwd_fused(float* const* bn_running, float* out) {
         const float *fw1[4] = {}, *fb1[4] = {}, *fw2[4] = {}, *fb2[4] = {};
         if (!plan.concat)
-            for (int h = 0; h < 4; ++h) { fw1[h] = P[ix.fus(h, 0)]; fb1[h] = P[ix.fus(h, 1)]; fw2[h] = P[ix.fus(h, 2)]; fb2[h] = P[ix.fus(h, 3)]; }
-        // exact-global-batch mode: the (mean, M2) blocks of every rank are gathered between the two launches
-        bbbp_head_sync sync;
-        sync.world = plan.world; sync.rank = plan.rank;
-        const size_t pcount = (size_t)((B + 15) / 16) * 2 * H1;
-        if (plan.exact)
-            sync.between = [&]() -> int {
-                return run_collective(d, BBBP_COLL_ALLGATHER, BBBP_COLL_BN_FWD, -1, plan.head_partial + (size_t)plan.rank * pcount * sizeof(float),
-                                      plan.head_partial, pcount, c.st);
-            };
+            for (int hh = 0; hh < 4; ++hh) { fw1[hh] = P[ix.fus(hh, 0)]; fb1[hh] = P[ix.fus(hh, 1)]; fw2[hh] = P[ix.fus(hh, 2)]; fb2[hh] = P[ix.fus(hh, 3)]; }
+        const bbbp_head_sync sync = head_sync(BBBP_COLL_BN_FWD);
         return bbbp_head_forward_fused_sync(c.st, comb, fw1, fb1, fw2, fb2, P[ix.fc0_w()], P[ix.fc0_b()], P[ix.bn_w()], P[ix.bn_b()],
                                             bn_running[0], bn_running[1], P[ix.fc3_w()], P[ix.fc3_b()], P[ix.fc5_w()], P[ix.fc5_b()],
-                                            P[ix.fc7_w()], P[ix.fc7_b()], c.f(plan.hid), c.f(plan.attn), c.f(plan.fused), c.f(plan.h),
-                                            c.f(plan.hb), c.f(plan.bn_mean), c.f(plan.bn_rstd), c.f(plan.h2), c.f(plan.h3), out,
+                                            P[ix.fc7_w()], P[ix.fc7_b()], hid, c.f(plan.attn), fused, h, hb, c.f(plan.bn_mean), c.f(plan.bn_rstd), h2, h3, out,
                                             c.f(plan.head_partial), B, d->training, plan.concat ? 1 : 0, plan.exact ? &sync : nullptr);
     }
-    // ---- attention fusion (R:60-65, 117) -------------------------------------------------------
-    float* hid = c.f(plan.hid);
-    float* fused = c.f(plan.fused);              // == combined under torch.cat fusion
-    if (!plan.concat) {
-        const float* w2[NHEADS_FUSION]; const float* b2[NHEADS_FUSION];
-        for (int h = 0; h < NHEADS_FUSION; ++h) {
-            TRY(linear_fwd(c, comb, COMB, P[ix.fus(h, 0)], P[ix.fus(h, 1)], hid + (size_t)h * B * FUS_HID, FUS_HID, B, FUS_HID, COMB,
-                           BBBP_ACT_TANH));
-            w2[h] = P[ix.fus(h, 2)]; b2[h] = P[ix.fus(h, 3)];
+    int head_fwd_ops(float* const* bn_running, float* out) {
+        if (!plan.concat) {
+            const float* w2[NHEADS_FUSION]; const float* b2[NHEADS_FUSION];
+            for (int hh = 0; hh < NHEADS_FUSION; ++hh) {
+                TRY(linear_fwd(c, comb, COMB, P[ix.fus(hh, 0)], P[ix.fus(hh, 1)], hid + (size_t)hh * B * FUS_HID, FUS_HID, B, FUS_HID, COMB, BBBP_ACT_TANH));
+                w2[hh] = P[ix.fus(hh, 2)]; b2[hh] = P[ix.fus(hh, 3)];
+            }
+            TRY(bbbp_fusion_combine_fwd(c.st, comb, hid, w2, b2, fused, c.f(plan.attn), B, COMB, FUS_HID, NHEADS_FUSION));
         }
-        TRY(bbbp_fusion_combine_fwd(c.st, comb, hid, w2, b2, fused, c.f(plan.attn), B, COMB, FUS_HID, NHEADS_FUSION));
+        TRY(linear_fwd(c, fused, COMB, P[ix.fc0_w()], P[ix.fc0_b()], h, H1, B, H1, COMB, BBBP_ACT_RELU));
+        TRY(bbbp_batchnorm1d_fwd(c.st, h, hb, P[ix.bn_w()], P[ix.bn_b()], bn_running[0], bn_running[1], c.f(plan.bn_mean),
+                                 c.f(plan.bn_rstd), B, H1, 1e-5f, 0.1f, d->training));
+        TRY(linear_fwd(c, hb, H1, P[ix.fc3_w()], P[ix.fc3_b()], h2, H2, B, H2, H1, BBBP_ACT_RELU));
+        TRY(linear_fwd(c, h2, H2, P[ix.fc5_w()], P[ix.fc5_b()], h3, H3, B, H3, H2, BBBP_ACT_RELU));
+        return linear_fwd(c, h3, H3, P[ix.fc7_w()], P[ix.fc7_b()], out, 1, B, 1, H3, 0);
     }
-
-    // ---- regression head (R:98-107, 118) -------------------------------------------------------
-    float* h = c.f(plan.h); float* hb = c.f(plan.hb); float* h2 = c.f(plan.h2); float* h3 = c.f(plan.h3);
-    TRY(linear_fwd(c, fused, COMB, P[ix.fc0_w()], P[ix.fc0_b()], h, H1, B, H1, COMB, BBBP_ACT_RELU));
-    TRY(bbbp_batchnorm1d_fwd(c.st, h, hb, P[ix.bn_w()], P[ix.bn_b()], bn_running[0], bn_running[1], c.f(plan.bn_mean),
-                             c.f(plan.bn_rstd), B, H1, 1e-5f, 0.1f, d->training));
-    TRY(linear_fwd(c, hb, H1, P[ix.fc3_w()], P[ix.fc3_b()], h2, H2, B, H2, H1, BBBP_ACT_RELU));
-    TRY(linear_fwd(c, h2, H2, P[ix.fc5_w()], P[ix.fc5_b()], h3, H3, B, H3, H2, BBBP_ACT_RELU));
-    TRY(linear_fwd(c, h3, H3, P[ix.fc7_w()], P[ix.fc7_b()], out, 1, B, 1, H3, 0));
-    return BBBP_OK;
-}
-
-// `plan`: as for forward_enqueue (bbbp_mixed_backward)
-static int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& plan, const float* const* P, float* const* G,
-                            const float* fingerprint, const float* image, const float* dout, void* workspace) {
-    SeedScope seed_scope(reinterpret_cast<const unsigned long long*>(static_cast<char*>(workspace) + plan.seed_slot));
-    BBBP_CHECK_ARG(!plan.inference, "mixed_backward: the forward call used an inference workspace (desc.inference = 1)");
-    (void)bbbp_param_wait(static_cast<hipStream_t>(stream), nullptr);      // (a deferred optimizer slice: normally consumed by the forward pass already)
-    DeviceState* ds = nullptr;          // this device's gradient-bucket events
-    TRY(device_state(&ds));
-    // Three streams: `c` (caller's stream) carries the head, the fusion block and the image branch; `ce` carries the
-    // fingerprint branch's dependency chain (dy -> dx through the encoder layers); `cl` carries the LEAVES -- weight
-    // and bias gradients, LayerNorm parameter gradients -- which nothing downstream waits for, so the chain's
-    // critical path is half as long.  With overlap disabled all three are the caller's stream.
-    Ctx c{static_cast<hipStream_t>(stream), static_cast<char*>(workspace), &plan};
-    Ctx ce = c, cl = c;
-    SideStream* ss = nullptr;
-    if (overlap_enabled()) {
-        TRY(get_side(&ss));
-        TRY(fork_side(c.st, ss));                         // chain stream starts after the caller's prior work
-        ce.st = ss->s; ce.side = 1;
-        TRY(after(ss, c.st, ss->leaf));
-        cl.st = ss->leaf; cl.side = 2;
+    // ---- backward: leaves (leaf stream) -----------------------------------------------------------------------------
+    int leaf_after(const Ctx& producer) { return ss ? after(ss, producer.st, cl.st) : BBBP_OK; }
+    // The head's weight / bias gradients in leaf-stream order: 0..3 fc.7, fc.5, fc.3, fc.0; 4 + h fusion head h; 8 the image FC's bias (column
+    // sums of the masked dcomb).  The fused head enqueues them all after the image branch; the launch-per-op head one by one as its chain
+    // writes what they read.
+    int head_leaf(int k, const float* dout) {
+        switch (k) {
+        case 0: return linear_bwd_weight_bias(cl, dout, 1, h3, H3, G[ix.fc7_w()], G[ix.fc7_b()], B, 1, H3);
+        case 1: return linear_bwd_weight_bias(cl, dh3, H3, h2, H2, G[ix.fc5_w()], G[ix.fc5_b()], B, H3, H2);
+        case 2: return linear_bwd_weight_bias(cl, dh2, H2, hb, H1, G[ix.fc3_w()], G[ix.fc3_b()], B, H2, H1);
+        case 3: return linear_bwd_weight_bias(cl, dh, H1, fused, COMB, G[ix.fc0_w()], G[ix.fc0_b()], B, H1, COMB);
+        case 8: return bbbp_bias_act_bwd(cl.st, dcomb + FC, COMB, nullptr, 0, G[ix.ifc_b()], B, FC, 0, 1.f);
+        }
+        if (plan.concat) return BBBP_OK;
+        const int hh = k - 4;
+        float* dp = dpre + (size_t)hh * B * FUS_HID;
+        TRY(linear_bwd_weight_bias(cl, dlogit + (size_t)hh * B, 1, hid + (size_t)hh * B * FUS_HID, FUS_HID, G[ix.fus(hh, 2)], G[ix.fus(hh, 3)], B, 1, FUS_HID));
+        return linear_bwd_weight_bias(cl, dp, FUS_HID, comb, COMB, G[ix.fus(hh, 0)], G[ix.fus(hh, 1)], B, FUS_HID, COMB);
     }
-    auto leaf_after = [&](const Ctx& producer) -> int { return ss ? after(ss, producer.st, cl.st) : BBBP_OK; };
+    int head_leaves(const float* dout) { for (int k = 0; k <= 8; ++k) TRY(head_leaf(k, dout)); return BBBP_OK; }
+    // A layer's weight / bias gradients: linear2 and linear1, out_proj, in_proj (the schedules put chain work between them); `timed`: the
+    // launch-per-op schedule's profiling sections
+    int ffn_leaves(int l, bool timed) {
+        const LayerOff& o = plan.layer[l]; const LayerGrad& g = plan.lgrad[l];
+        {
+            Section sw(cl.st, timed ? SEC_FFN2_WGRAD : -1);
+            TRY(linear_bwd_weight_bias(cl, c.f(g.dz2d), F, c.f(o.hff), DFF, GL(l, L_W2), GL(l, L_B2), B, F, DFF));
+        }
+        Section sw(cl.st, timed ? SEC_FFN1_WGRAD : -1);
+        return linear_bwd_weight_bias(cl, c.f(g.dhff), DFF, c.f(o.y1), F, GL(l, L_W1), GL(l, L_B1), B, DFF, F);
+    }
+    int outproj_leaf(int l, bool timed) {
+        Section sw(cl.st, timed ? SEC_OUTPROJ_WGRAD : -1);
+        return linear_bwd_weight_bias(cl, c.f(plan.lgrad[l].dz1d), F, c.f(plan.layer[l].ctx), F, GL(l, L_OUTW), GL(l, L_OUTB), B, F, F);
+    }
+    int inproj_leaf(int l, bool timed) {
+        Section sw(cl.st, timed ? SEC_QKV_WGRAD : -1);
+        return linear_bwd_weight_bias(cl, c.f(plan.lgrad[l].dqkv), 3 * F, layer_input(l), F, GL(l, L_INW), GL(l, L_INB), B, 3 * F, F);
+    }
+    const float* layer_input(int l) const { return l > 0 ? c.f(plan.layer[l - 1].y2) : fingerprint; }      // l == L: the encoder's output
+    int fingerprint_fc_leaf() { return linear_bwd_weight_bias(cl, dcomb, COMB, layer_input(plan.L), F, G[ix.fpfc_w()], G[ix.fpfc_b()], B, FC, F); }
     // both LayerNorms' weight / bias gradients of layer l in ONE leaf launch (dgamma = sum_rows dy * xhat, dbeta = sum_rows dy),
     // the last leaf of the layer: its gradient bucket (all twelve tensors, one contiguous slice) is final after it
-    auto layer_norm_grads = [&](int l) -> int {
+    int layer_norm_grads(int l) {
         const LayerOff& o = plan.layer[l]; const LayerGrad& g = plan.lgrad[l];
-        const PIdx ixl(d);
         const float* dy[2] = {c.f(g.dyout), c.f(g.dy1)}; const float* zz[2] = {c.f(o.z2), c.f(o.z1)};
         const float* mm[2] = {c.f(o.mean2), c.f(o.mean1)}; const float* rr[2] = {c.f(o.rstd2), c.f(o.rstd1)};
-        float* dg[2] = {G[ixl.layer(l, L_N2W)], G[ixl.layer(l, L_N1W)]}; float* db[2] = {G[ixl.layer(l, L_N2B)], G[ixl.layer(l, L_N1B)]};
-        return bbbp_ln_param_grad_multi(cl.st, 2, dy, zz, mm, rr, dg, db, plan.B, plan.F);
-    };
-    auto record_layer_bucket = [&](int l) -> int { return (ds && l >= 0 && l < 32) ? record_bucket(ds->layer[l], cl.st) : BBBP_OK; };
-    auto layer_norm_leaves = [&](int l) -> int {
-        TRY(layer_norm_grads(l));
-        return record_layer_bucket(l);
-    };
-    const PIdx ix(d);
-    const int B = plan.B, F = plan.F, NH = plan.NH, D = plan.D, DFF = plan.DFF;
-    const int Bk = (int)plan.Bg;            // attention keys: this rank's rows, or every rank's in exact-global-batch mode
-    const float p_drop = plan.drop ? d->dropout_p : 0.f;
-    const float inv_keep = plan.drop ? 1.f / (1.f - p_drop) : 1.f;
-    const float scale = 1.0f / sqrtf((float)D);
-
-    float* comb = c.f(plan.combined); float* hid = c.f(plan.hid); float* fused = c.f(plan.fused);
-    float* h = c.f(plan.h); float* hb = c.f(plan.hb); float* h2 = c.f(plan.h2); float* h3 = c.f(plan.h3);
-    float* dh3 = c.f(plan.dh3); float* dh2 = c.f(plan.dh2); float* dhb = c.f(plan.dhb); float* dh = c.f(plan.dh);
-    float* dfused = c.f(plan.dfused); float* dcomb = c.f(plan.dcomb);
-
-    // ---- head (chain on the caller's stream, leaves on the leaf stream) ---------------------------
-    std::optional<Section> sec;
-    sec.emplace(c.st, SEC_HEAD_BWD);
-    auto next_section = [&](int id) { sec.reset(); sec.emplace(c.st, id); };
-    // default ON since round 2 (bbbp_set_fused_head_bwd / BBBP_FUSED_HEAD_BWD=0 select the launch-per-op chain): with the bias
-    // gradients folded into the weight-gradient GEMMs the leaves it feeds are short enough that the shorter chain shows --
-    // B = 512 3.32 -> 3.27 ms, B = 256 2.12 -> 2.08, B = 128 2.36 -> 2.23 (round 1, with 38 separate column-sum leaves: neutral)
-    const int fused_head_bwd = g_fused_head_bwd.get() && !plan.concat;
-    float* dlogit = c.f(plan.dlogit); float* dpre = c.f(plan.dpre);
-    bool head_leaves_pending = false;
-    auto head_leaves = [&]() -> int {
-        TRY(linear_bwd_weight_bias(cl, dout, 1, h3, H3, G[ix.fc7_w()], G[ix.fc7_b()], B, 1, H3));
-        TRY(linear_bwd_weight_bias(cl, dh3, H3, h2, H2, G[ix.fc5_w()], G[ix.fc5_b()], B, H3, H2));
-        TRY(linear_bwd_weight_bias(cl, dh2, H2, hb, H1, G[ix.fc3_w()], G[ix.fc3_b()], B, H2, H1));
-        TRY(linear_bwd_weight_bias(cl, dh, H1, fused, COMB, G[ix.fc0_w()], G[ix.fc0_b()], B, H1, COMB));
-        for (int hh = 0; hh < (plan.concat ? 0 : NHEADS_FUSION); ++hh) {
-            float* dl = dlogit + (size_t)hh * B;
-            float* dp = dpre + (size_t)hh * B * FUS_HID;
-            const float* hd = hid + (size_t)hh * B * FUS_HID;
-            TRY(linear_bwd_weight_bias(cl, dl, 1, hd, FUS_HID, G[ix.fus(hh, 2)], G[ix.fus(hh, 3)], B, 1, FUS_HID));
-            TRY(linear_bwd_weight_bias(cl, dp, FUS_HID, comb, COMB, G[ix.fus(hh, 0)], G[ix.fus(hh, 1)], B, FUS_HID, COMB));
-        }
-        TRY(bbbp_bias_act_bwd(cl.st, dcomb + FC, COMB, nullptr, 0, G[ix.ifc_b()], B, FC, 0, 1.f));
-        return BBBP_OK;
-    };
-    BBBP_CHECK_ARG(!plan.exact || fused_head_bwd, "the exact-global-batch mode needs the fused head backward (bbbp_set_fused_head_bwd(1))");
-    if (fused_head_bwd) {
-        // the whole input-gradient chain of the head and the fusion block in two launches (head.hip); every weight / bias
-        // gradient below is a leaf that reads what those wrote
+        float* dg[2] = {GL(l, L_N2W), GL(l, L_N1W)}; float* db[2] = {GL(l, L_N2B), GL(l, L_N1B)};
+        return bbbp_ln_param_grad_multi(cl.st, 2, dy, zz, mm, rr, dg, db, B, F);
+    }
+    int record_layer_bucket(int l) { return (ds && l >= 0 && l < 32) ? record_bucket(ds->layer[l], cl.st) : BBBP_OK; }
+    int layer_norm_leaves(int l) { TRY(layer_norm_grads(l)); return record_layer_bucket(l); }
+    // ---- backward: head and fusion block (chain on the caller's stream) ----------------------------------------------
+    // the whole input-gradient chain of the head and the fusion block in two launches (head.hip); every weight / bias
+    // gradient is a leaf that reads what those wrote
+    int head_bwd_fused(const float* dout) {
         const float* fw1[NHEADS_FUSION]; const float* fw2[NHEADS_FUSION];
         for (int hh = 0; hh < NHEADS_FUSION; ++hh) { fw1[hh] = P[ix.fus(hh, 0)]; fw2[hh] = P[ix.fus(hh, 2)]; }
-        // exact-global-batch mode: the BatchNorm's two backward sums span every rank's rows
-        bbbp_head_sync sync;
-        sync.world = plan.world; sync.rank = plan.rank;
-        const size_t pcount = (size_t)((B + 15) / 16) * 2 * H1;
-        if (plan.exact)
-            sync.between = [&]() -> int {
-                return run_collective(d, BBBP_COLL_ALLGATHER, BBBP_COLL_BN_BWD, -1, plan.head_partial + (size_t)plan.rank * pcount * sizeof(float),
-                                      plan.head_partial, pcount, c.st);
-            };
+        const bbbp_head_sync sync = head_sync(BBBP_COLL_BN_BWD);
         TRY(bbbp_head_backward_fused_sync(c.st, dout, comb, hid, c.f(plan.attn), h, h2, h3, c.f(plan.bn_mean), c.f(plan.bn_rstd),
                                           P[ix.bn_w()], fw1, fw2, P[ix.fc0_w()], P[ix.fc3_w()], P[ix.fc5_w()], P[ix.fc7_w()], dh3, dh2, dhb,
                                           dh, dlogit, dpre, dcomb, G[ix.bn_w()], G[ix.bn_b()], c.f(plan.head_partial), B, d->training,
                                           plan.exact ? &sync : nullptr));
+        return leaf_after(c);          // (the leaves themselves: after the image branch's kernels, the host reaches those sooner)
+    }
+    // dx = (dy W) (.) [gate > 0] on the caller's stream: the ReLU masks ride in the input-gradient GEMMs' epilogues
+    int gated_bwd_input(const float* dy, int N, const float* W, float* dx, int K, const float* gate) {
+        bbbp_gemm_desc g = gemm_desc(0, 0, B, K, N, 1.f, dy, N, W, K, dx, K);
+        g.gate = gate; g.ldg = K;
+        return bbbp_gemm_f32_grouped(c.st, &g, 1, c.scratch(), c.scratch_bytes());
+    }
+    int head_bwd_ops(const float* dout) {
+        // fc.7: out = h3 W7^T + b7
+        TRY(head_leaf(0, dout));
+        TRY(gated_bwd_input(dout, 1, P[ix.fc7_w()], dh3, H3, h3));
         TRY(leaf_after(c));
-        head_leaves_pending = true;          // enqueued after the image branch's kernels: the host reaches those sooner
-    } else {
-    // fc.7: out = h3 W7^T + b7
-    TRY(linear_bwd_weight_bias(cl, dout, 1, h3, H3, G[ix.fc7_w()], G[ix.fc7_b()], B, 1, H3));
-    // the ReLU masks ride in the input-gradient GEMMs' epilogues; the bias gradients (column sums) are leaves
-    {
-        bbbp_gemm_desc g = gemm_desc(0, 0, B, H3, 1, 1.f, dout, 1, P[ix.fc7_w()], H3, dh3, H3);
-        g.gate = h3; g.ldg = H3;
-        TRY(bbbp_gemm_f32_grouped(c.st, &g, 1, c.scratch(), c.scratch_bytes()));
-    }
-    TRY(leaf_after(c));
-    TRY(linear_bwd_weight_bias(cl, dh3, H3, h2, H2, G[ix.fc5_w()], G[ix.fc5_b()], B, H3, H2));
-    {
-        bbbp_gemm_desc g = gemm_desc(0, 0, B, H2, H3, 1.f, dh3, H3, P[ix.fc5_w()], H2, dh2, H2);
-        g.gate = h2; g.ldg = H2;
-        TRY(bbbp_gemm_f32_grouped(c.st, &g, 1, c.scratch(), c.scratch_bytes()));
-    }
-    TRY(leaf_after(c));
-    TRY(linear_bwd_weight_bias(cl, dh2, H2, hb, H1, G[ix.fc3_w()], G[ix.fc3_b()], B, H2, H1));
-    TRY(linear_bwd_input(c, dh2, H2, P[ix.fc3_w()], dhb, H1, B, H2, H1));
-    TRY(bbbp_batchnorm1d_bwd_relu(c.st, dhb, h, P[ix.bn_w()], c.f(plan.bn_mean), c.f(plan.bn_rstd), dh, G[ix.bn_w()], G[ix.bn_b()],
-                                  B, H1, d->training));
-    TRY(leaf_after(c));
-    TRY(linear_bwd_weight_bias(cl, dh, H1, fused, COMB, G[ix.fc0_w()], G[ix.fc0_b()], B, H1, COMB));
-    if (plan.concat) {
-        // torch.cat fusion: dcomb = dh W0, masked by the ReLUs that produced combined = [fp_out | img_out]
-        bbbp_gemm_desc g = gemm_desc(0, 0, B, COMB, H1, 1.f, dh, H1, P[ix.fc0_w()], COMB, dcomb, COMB);
-        g.gate = comb; g.ldg = COMB;
-        TRY(bbbp_gemm_f32_grouped(c.st, &g, 1, c.scratch(), c.scratch_bytes()));
-    } else {
-    TRY(linear_bwd_input(c, dh, H1, P[ix.fc0_w()], dfused, COMB, B, H1, COMB));
-
-    // ---- attention fusion ------------------------------------------------------------------------
-    const float* w2[NHEADS_FUSION];
-    for (int hh = 0; hh < NHEADS_FUSION; ++hh) w2[hh] = P[ix.fus(hh, 2)];
-    TRY(bbbp_fusion_combine_bwd(c.st, dfused, comb, hid, c.f(plan.attn), w2, dcomb, dlogit, dpre, B, COMB, FUS_HID, NHEADS_FUSION));
-    TRY(leaf_after(c));
-    for (int hh = 0; hh < NHEADS_FUSION; ++hh) {
-        float* dl = dlogit + (size_t)hh * B;
-        float* dp = dpre + (size_t)hh * B * FUS_HID;
-        const float* hd = hid + (size_t)hh * B * FUS_HID;
-        TRY(linear_bwd_weight_bias(cl, dl, 1, hd, FUS_HID, G[ix.fus(hh, 2)], G[ix.fus(hh, 3)], B, 1, FUS_HID));
-        TRY(linear_bwd_weight_bias(cl, dp, FUS_HID, comb, COMB, G[ix.fus(hh, 0)], G[ix.fus(hh, 1)], B, FUS_HID, COMB));
-        // dcomb += dp W1_h; the last of the four also applies the ReLU mask of both branch outputs (combined = [fp_out | img_out])
-        bbbp_gemm_desc g = gemm_desc(0, 0, B, COMB, FUS_HID, 1.f, dp, FUS_HID, P[ix.fus(hh, 0)], COMB, dcomb, COMB);
-        g.residual = dcomb; g.ldr = COMB;
-        if (hh == NHEADS_FUSION - 1) { g.gate = comb; g.ldg = COMB; g.gate_after_residual = 1; }
-        TRY(bbbp_gemm_f32_grouped(c.st, &g, 1, c.scratch(), c.scratch_bytes()));
-    }
-    }
-    // bias gradients of the two branch outputs: column sums of the masked dcomb, leaves
-    TRY(leaf_after(c));
-    TRY(bbbp_bias_act_bwd(cl.st, dcomb + FC, COMB, nullptr, 0, G[ix.ifc_b()], B, FC, 0, 1.f));
-
-    }
-
-    // both branches only READ dcomb from here on
-    if (ss) { TRY(after(ss, c.st, ce.st)); TRY(after(ss, c.st, cl.st)); }
-    Partition part(ss != nullptr);
-
-    // ---- image branch (caller's stream): enqueued first, five long MFMA-bound kernels -------------------
-    float* pool1 = c.f(plan.pool1); float* pool2 = c.f(plan.pool2);
-    float* dpool2 = c.f(plan.dpool2); float* dpool1 = c.f(plan.dpool1);
-    next_section(SEC_IMGFC_BWD);
-    TRY(linear_bwd_weight(c, dcomb + FC, COMB, pool2, IMG_FLAT, G[ix.ifc_w()], B, FC, IMG_FLAT));
-    if (ds) TRY(record_bucket(ds->bucket0, c.st));
-    TRY(linear_bwd_input(c, dcomb + FC, COMB, P[ix.ifc_w()], dpool2, IMG_FLAT, B, FC, IMG_FLAT));
-    if (ds) {
-        // ... and from here on the image-FC weight itself is no longer read by this pass (bbbp_mixed_backward_wait_released, bucket 0)
-        BucketEvent& rel = ds->bucket0_released;
-        rel.recorded = g_release_events && ds->bucket0.recorded;
-        if (rel.recorded) {
-            if (!rel.ev) BBBP_CHECK_HIP(hipEventCreateWithFlags(&rel.ev, hipEventDisableTiming));
-            BBBP_CHECK_HIP(hipEventRecord(rel.ev, c.st));
+        TRY(head_leaf(1, dout));
+        TRY(gated_bwd_input(dh3, H3, P[ix.fc5_w()], dh2, H2, h2));
+        TRY(leaf_after(c));
+        TRY(head_leaf(2, dout));
+        TRY(linear_bwd_input(c, dh2, H2, P[ix.fc3_w()], dhb, H1, B, H2, H1));
+        TRY(bbbp_batchnorm1d_bwd_relu(c.st, dhb, h, P[ix.bn_w()], c.f(plan.bn_mean), c.f(plan.bn_rstd), dh, G[ix.bn_w()], G[ix.bn_b()], B, H1, d->training));
+        TRY(leaf_after(c));
+        TRY(head_leaf(3, dout));
+        if (plan.concat) {
+            // torch.cat fusion: dcomb = dh W0, masked by the ReLUs that produced combined = [fp_out | img_out]
+            TRY(gated_bwd_input(dh, H1, P[ix.fc0_w()], dcomb, COMB, comb));
+        } else {
+            TRY(linear_bwd_input(c, dh, H1, P[ix.fc0_w()], dfused, COMB, B, H1, COMB));
+            // attention fusion
+            const float* w2[NHEADS_FUSION];
+            for (int hh = 0; hh < NHEADS_FUSION; ++hh) w2[hh] = P[ix.fus(hh, 2)];
+            TRY(bbbp_fusion_combine_bwd(c.st, dfused, comb, hid, c.f(plan.attn), w2, dcomb, dlogit, dpre, B, COMB, FUS_HID, NHEADS_FUSION));
+            TRY(leaf_after(c));
+            for (int hh = 0; hh < NHEADS_FUSION; ++hh) {
+                TRY(head_leaf(4 + hh, dout));
+                // dcomb += dp W1_h; the last of the four also applies the ReLU mask of both branch outputs (combined = [fp_out | img_out])
+                bbbp_gemm_desc g = gemm_desc(0, 0, B, COMB, FUS_HID, 1.f, dpre + (size_t)hh * B * FUS_HID, FUS_HID, P[ix.fus(hh, 0)], COMB, dcomb, COMB);
+                g.residual = dcomb; g.ldr = COMB;
+                if (hh == NHEADS_FUSION - 1) { g.gate = comb; g.ldg = COMB; g.gate_after_residual = 1; }
+                TRY(bbbp_gemm_f32_grouped(c.st, &g, 1, c.scratch(), c.scratch_bytes()));
+            }
         }
+        // bias gradients of the two branch outputs: leaves of the masked dcomb
+        TRY(leaf_after(c));
+        return head_leaf(8, dout);
     }
-    next_section(SEC_CONV2_WGRAD);
-    {
-        // beside the encoder's backward chain the sparse weight-gradient kernel runs one wave per SIMD (common.h); the rule looks at the
-        // plan only, not at the stream mode: one stream or three give bit-identical steps
-        ConvPrefs prefs;
-        prefs.wgrad_beside_encoder = plan.L > 0 ? 1 : 0;
+    // ---- backward: image branch (caller's stream), five long MFMA-bound kernels; `sec`: the open section of that stream ----
+    int image_bwd(std::optional<Section>& sec) {
+        auto next_section = [&](int id) { sec.reset(); sec.emplace(c.st, id); };
+        float* pool1 = c.f(plan.pool1); float* pool2 = c.f(plan.pool2);
+        float* dpool2 = c.f(plan.dpool2); float* dpool1 = c.f(plan.dpool1);
+        next_section(SEC_IMGFC_BWD);
+        TRY(linear_bwd_weight(c, dcomb + FC, COMB, pool2, IMG_FLAT, G[ix.ifc_w()], B, FC, IMG_FLAT));
+        if (ds) TRY(record_bucket(ds->bucket0, c.st));
+        TRY(linear_bwd_input(c, dcomb + FC, COMB, P[ix.ifc_w()], dpool2, IMG_FLAT, B, FC, IMG_FLAT));
+        if (ds) {
+            // ... and from here on the image-FC weight itself is no longer read by this pass (bbbp_mixed_backward_wait_released, bucket 0)
+            BucketEvent& rel = ds->bucket0_released;
+            rel.recorded = g_release_events && ds->bucket0.recorded;
+            if (rel.recorded) {
+                if (!rel.ev) BBBP_CHECK_HIP(hipEventCreateWithFlags(&rel.ev, hipEventDisableTiming));
+                BBBP_CHECK_HIP(hipEventRecord(rel.ev, c.st));
+            }
+        }
+        next_section(SEC_CONV2_WGRAD);
         TRY(conv3x3_relu_pool_bwd_weight(c.st, pool1, dpool2, c.u8(plan.mask2), G[ix.c2_w()], G[ix.c2_b()], B, C1, C2, IMG / 2, IMG / 2,
-                                         c.scratch(), c.scratch_bytes(), prefs));
+                                         c.scratch(), c.scratch_bytes(), s.conv2_wgrad));
+        next_section(SEC_CONV2_DGRAD);
+        TRY(bbbp_conv3x3_relu_pool_bwd_data(c.st, dpool2, c.u8(plan.mask2), P[ix.c2_w()], dpool1, B, C1, C2, IMG / 2, IMG / 2, c.scratch(), c.scratch_bytes()));
+        next_section(SEC_CONV1_WGRAD);
+        TRY(bbbp_conv3x3_relu_pool_bwd_weight(c.st, image, dpool1, c.u8(plan.mask1), G[ix.c1_w()], G[ix.c1_b()], B, 3, C1, IMG, IMG, c.scratch(), c.scratch_bytes()));
+        sec.reset();
+        return BBBP_OK;
     }
-    next_section(SEC_CONV2_DGRAD);
-    TRY(bbbp_conv3x3_relu_pool_bwd_data(c.st, dpool2, c.u8(plan.mask2), P[ix.c2_w()], dpool1, B, C1, C2, IMG / 2, IMG / 2,
-                                        c.scratch(), c.scratch_bytes()));
-    next_section(SEC_CONV1_WGRAD);
-    TRY(bbbp_conv3x3_relu_pool_bwd_weight(c.st, image, dpool1, c.u8(plan.mask1), G[ix.c1_w()], G[ix.c1_b()], B, 3, C1, IMG, IMG,
-                                          c.scratch(), c.scratch_bytes()));
-    sec.reset();
-    if (head_leaves_pending) TRY(head_leaves());
-
-    // ---- fingerprint branch: chain on `ce`, leaves on `cl` --------------------------------------------
-    Section sec_encb(ce.st, SEC_ENCODER_BWD);
-    const float* enc_out = plan.L > 0 ? c.f(plan.layer[plan.L - 1].y2) : fingerprint;
-    TRY(linear_bwd_weight_bias(cl, dcomb, COMB, enc_out, F, G[ix.fpfc_w()], G[ix.fpfc_b()], B, FC, F));
-    float* dy = plan.L > 0 ? c.f(plan.lgrad[plan.L - 1].dyout) : c.f(plan.dA);
-    const bool sliced = sliced_encoder(plan, 4) && plan.sl_sync && plan.sl_kvpart;
-    if (!sliced && (plan.L > 0 || d->need_input_grad)) TRY(linear_bwd_input(ce, dcomb, COMB, P[ix.fpfc_w()], dy, F, B, FC, F));
-    float* dprob = c.f(plan.dprob); float* dctx = c.f(plan.dctx);
-    if (sliced) {
-        // the whole input-gradient chain in one persistent launch; every weight gradient is a leaf of its buffers afterwards
+    // ---- backward: fingerprint branch, chain on `ce`, leaves on `cl`; one function per schedule ------------------------
+    // gradient of the encoder's output (of the fingerprint, on request, when there are no layers)
+    int fingerprint_fc_bwd_input() {
+        if (plan.L == 0 && !d->need_input_grad) return BBBP_OK;
+        return linear_bwd_input(ce, dcomb, COMB, P[ix.fpfc_w()], plan.L > 0 ? c.f(plan.lgrad[plan.L - 1].dyout) : c.f(plan.dA), F, B, FC, F);
+    }
+    // in_proj input gradient of layer 0 of the fused schedules, on request
+    int fingerprint_grad_fused() {
+        if (!d->need_input_grad) return BBBP_OK;
+        return linear_bwd_input(ce, c.f(plan.lgrad[0].dqkv), 3 * F, PL(0, L_INW), c.f(plan.dA), F, B, 3 * F, F, c.f(plan.lgrad[0].dz1), F);
+    }
+    // the whole input-gradient chain (fingerprint_fc's included) in one persistent launch; every weight gradient is a leaf of its buffers afterwards
+    int encoder_bwd_sliced() {
         bbbp_enc_sliced_bwd_args a;
         memset(&a, 0, sizeof(a));
         a.dcomb = dcomb; a.ldcomb = COMB; a.nfc = FC; a.wfc = P[ix.fpfc_w()];
@@ -1109,134 +1100,53 @@ static int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& 
         for (int l = 0; l < plan.L; ++l) {
             const LayerOff& o = plan.layer[l]; const LayerGrad& g = plan.lgrad[l];
             bbbp_enc_sliced_bwd_layer& y = a.lay[l];
-            y.win = P[ix.layer(l, L_INW)]; y.wo = P[ix.layer(l, L_OUTW)]; y.g1 = P[ix.layer(l, L_N1W)];
-            y.w1 = P[ix.layer(l, L_W1)]; y.w2 = P[ix.layer(l, L_W2)]; y.g2 = P[ix.layer(l, L_N2W)];
-            y.qkv = c.f(o.qkv); y.prob = c.f(o.prob); y.pd = c.f(o.pd); y.z1 = c.f(o.z1); y.hff = c.f(o.hff); y.z2 = c.f(o.z2);
-            y.mean1 = c.f(o.mean1); y.rstd1 = c.f(o.rstd1); y.mean2 = c.f(o.mean2); y.rstd2 = c.f(o.rstd2);
+            fill_layer(y, l);
+            y.win = PL(l, L_INW); y.qkv = c.f(o.qkv); y.prob = c.f(o.prob); y.pd = c.f(o.pd); y.seed0 = site_seed(l, 0);
             y.dyout = c.f(g.dyout); y.dz2 = c.f(g.dz2); y.dff = c.f(g.dz2d); y.dhff = c.f(g.dhff); y.dy1 = c.f(g.dy1);
             y.dz1 = c.f(g.dz1); y.dsa = c.f(g.dz1d); y.dqkv = c.f(g.dqkv);
-            y.seed0 = site_seed(d->seed, l, 0); y.seed1 = site_seed(d->seed, l, 1); y.seed3 = site_seed(d->seed, l, 3);
         }
         TRY(bbbp_enc_sliced_bwd(ce.st, &a));
-        if (d->need_input_grad)
-            TRY(linear_bwd_input(ce, c.f(plan.lgrad[0].dqkv), 3 * F, P[ix.layer(0, L_INW)], c.f(plan.dA), F, B, 3 * F, F, c.f(plan.lgrad[0].dz1), F));
+        TRY(fingerprint_grad_fused());
         TRY(leaf_after(ce));
         for (int l = plan.L - 1; l >= 0; --l) {
-            const LayerOff& o = plan.layer[l]; const LayerGrad& g = plan.lgrad[l];
-            const float* xin = l > 0 ? c.f(plan.layer[l - 1].y2) : fingerprint;
-            TRY(linear_bwd_weight_bias(cl, c.f(g.dz2d), F, c.f(o.hff), DFF, G[ix.layer(l, L_W2)], G[ix.layer(l, L_B2)], B, F, DFF));
-            TRY(linear_bwd_weight_bias(cl, c.f(g.dhff), DFF, c.f(o.y1), F, G[ix.layer(l, L_W1)], G[ix.layer(l, L_B1)], B, DFF, F));
-            TRY(linear_bwd_weight_bias(cl, c.f(g.dz1d), F, c.f(o.ctx), F, G[ix.layer(l, L_OUTW)], G[ix.layer(l, L_OUTB)], B, F, F));
-            TRY(linear_bwd_weight_bias(cl, c.f(g.dqkv), 3 * F, xin, F, G[ix.layer(l, L_INW)], G[ix.layer(l, L_INB)], B, 3 * F, F));
+            TRY(ffn_leaves(l, false));
+            TRY(outproj_leaf(l, false));
+            TRY(inproj_leaf(l, false));
             TRY(layer_norm_leaves(l));
         }
+        return BBBP_OK;
     }
-    const bool fused_rows = !sliced && fused_encoder(plan);
-    for (int l = fused_rows ? plan.L - 1 : -1; l >= 0; --l) {
-        const LayerOff& o = plan.layer[l];
-        const LayerGrad& g = plan.lgrad[l];
-        const float* xin = l > 0 ? c.f(plan.layer[l - 1].y2) : fingerprint;
-        float* qkv = c.f(o.qkv); float* prob = c.f(o.prob); float* ctx = c.f(o.ctx);
-        float* dff = c.f(g.dz2d); float* dhff = c.f(g.dhff); float* dsa = c.f(g.dz1d); float* dqkv = c.f(g.dqkv);
-        // one launch: (in_proj input gradient of the layer above + residual ->) norm2 bwd -> linear2 dgrad (.) gate -> linear1
-        // dgrad + residual -> norm1 bwd -> out_proj dgrad
-        bbbp_enc_row_bwd_args a;
-        const bool top = l + 1 == plan.L;
-        a.dqkv_up = top ? nullptr : c.f(plan.lgrad[l + 1].dqkv); a.win_up = top ? nullptr : P[ix.layer(l + 1, L_INW)];
-        a.dz1_up = top ? nullptr : c.f(plan.lgrad[l + 1].dz1); a.dyout = c.f(g.dyout);
-        a.z2 = c.f(o.z2); a.mean2 = c.f(o.mean2); a.rstd2 = c.f(o.rstd2); a.g2 = P[ix.layer(l, L_N2W)]; a.w2 = P[ix.layer(l, L_W2)];
-        a.hff = c.f(o.hff); a.w1 = P[ix.layer(l, L_W1)]; a.z1 = c.f(o.z1); a.mean1 = c.f(o.mean1); a.rstd1 = c.f(o.rstd1);
-        a.g1 = P[ix.layer(l, L_N1W)]; a.wo = P[ix.layer(l, L_OUTW)];
-        a.dz2 = c.f(g.dz2); a.dff = dff; a.dhff = dhff; a.dy1 = c.f(g.dy1); a.dz1 = c.f(g.dz1); a.dsa = dsa; a.dctx = dctx;
-        a.B = B; a.F = F; a.DFF = DFF; a.p = p_drop; a.seed1 = site_seed(d->seed, l, 1); a.seed3 = site_seed(d->seed, l, 3);
-        TRY(bbbp_enc_row_bwd(ce.st, &a));
-        TRY(leaf_after(ce));
-        TRY(linear_bwd_weight_bias(cl, dff, F, c.f(o.hff), DFF, G[ix.layer(l, L_W2)], G[ix.layer(l, L_B2)], B, F, DFF));
-        TRY(linear_bwd_weight_bias(cl, dhff, DFF, c.f(o.y1), F, G[ix.layer(l, L_W1)], G[ix.layer(l, L_B1)], B, DFF, F));
-        TRY(linear_bwd_weight_bias(cl, dsa, F, ctx, F, G[ix.layer(l, L_OUTW)], G[ix.layer(l, L_OUTB)], B, F, F));
-        // attention backward (products that become ready together share a launch)
-        const float* pdp = c.f(o.pd);
-        {
-            bbbp_gemm_desc gg[2] = {
-                gemm_desc(1, 0, B, D, B, 1.f, pdp, B, dctx, F, dqkv + 2 * F, 3 * F, NH, (long)B * B, D, D),
-                gemm_desc(0, 1, B, B, D, 1.f, dctx, F, qkv + 2 * F, 3 * F, dprob, B, NH, D, D, (long)B * B)};
-            TRY(bbbp_gemm_f32_grouped(ce.st, gg, 2, ce.scratch(), ce.scratch_bytes()));
+    int encoder_bwd_rows() {
+        TRY(fingerprint_fc_bwd_input());
+        float* dctx = c.f(plan.dctx);
+        for (int l = plan.L - 1; l >= 0; --l) {
+            const LayerGrad& g = plan.lgrad[l];
+            // one launch: (in_proj input gradient of the layer above + residual ->) norm2 bwd -> linear2 dgrad (.) gate -> linear1
+            // dgrad + residual -> norm1 bwd -> out_proj dgrad
+            bbbp_enc_row_bwd_args a;
+            fill_layer(a, l);
+            const bool top = l + 1 == plan.L;
+            a.dqkv_up = top ? nullptr : c.f(plan.lgrad[l + 1].dqkv); a.win_up = top ? nullptr : PL(l + 1, L_INW);
+            a.dz1_up = top ? nullptr : c.f(plan.lgrad[l + 1].dz1); a.dyout = c.f(g.dyout);
+            a.dz2 = c.f(g.dz2); a.dff = c.f(g.dz2d); a.dhff = c.f(g.dhff); a.dy1 = c.f(g.dy1); a.dz1 = c.f(g.dz1); a.dsa = c.f(g.dz1d); a.dctx = dctx;
+            a.B = B; a.F = F; a.DFF = DFF; a.p = p_drop;
+            TRY(bbbp_enc_row_bwd(ce.st, &a));
+            TRY(leaf_after(ce));
+            TRY(ffn_leaves(l, false));
+            TRY(outproj_leaf(l, false));
+            TRY(attention_bwd_gemm(l, dctx));
+            TRY(leaf_after(ce));
+            TRY(inproj_leaf(l, false));
+            TRY(layer_norm_leaves(l));
         }
-        TRY(bbbp_softmax_bwd(ce.st, dprob, prob, (long)NH * B, B, p_drop, site_seed(d->seed, l, 0)));
-        {
-            bbbp_gemm_desc gg[2] = {
-                gemm_desc(0, 0, B, D, B, scale, dprob, B, qkv + F, 3 * F, dqkv, 3 * F, NH, (long)B * B, D, D),
-                gemm_desc(1, 0, B, D, B, scale, dprob, B, qkv, 3 * F, dqkv + F, 3 * F, NH, (long)B * B, D, D)};
-            TRY(bbbp_gemm_f32_grouped(ce.st, gg, 2, ce.scratch(), ce.scratch_bytes()));
-        }
-        TRY(leaf_after(ce));
-        TRY(linear_bwd_weight_bias(cl, dqkv, 3 * F, xin, F, G[ix.layer(l, L_INW)], G[ix.layer(l, L_INB)], B, 3 * F, F));
-        TRY(layer_norm_leaves(l));
-        if (l == 0 && d->need_input_grad)
-            TRY(linear_bwd_input(ce, dqkv, 3 * F, P[ix.layer(0, L_INW)], c.f(plan.dA), F, B, 3 * F, F, c.f(g.dz1), F));
+        return fingerprint_grad_fused();
     }
-    for (int l = (fused_rows || sliced) ? -1 : plan.L - 1; l >= 0; --l) {
+    int encoder_bwd_ops() { TRY(fingerprint_fc_bwd_input()); for (int l = plan.L - 1; l >= 0; --l) TRY(encoder_layer_bwd_ops(l)); return BBBP_OK; }
+    // attention backward with materialised probabilities (both launch-per-op and row-fused schedules).  Products that become ready together share a launch (bbbp_gemm_f32_grouped):
+    //   dV_h = Pd_h^T dctx_h -> dqkv[:, 2F + hD]   |   dPd_h = dctx_h V_h^T
+    int attention_bwd_gemm(int l, const float* dattn) {
         const LayerOff& o = plan.layer[l];
-        const LayerGrad& g = plan.lgrad[l];
-        const float* xin = l > 0 ? c.f(plan.layer[l - 1].y2) : fingerprint;
-        float* qkv = c.f(o.qkv); float* prob = c.f(o.prob); float* ctx = c.f(o.ctx);
-        float* z1 = c.f(o.z1); float* y1 = c.f(o.y1); float* hff = c.f(o.hff); float* z2 = c.f(o.z2);
-        float* dyout = c.f(g.dyout); float* dz2 = c.f(g.dz2); float* dff = c.f(g.dz2d); float* dhff = c.f(g.dhff);
-        float* dy1 = c.f(g.dy1); float* dz1 = c.f(g.dz1); float* dsa = c.f(g.dz1d); float* dqkv = c.f(g.dqkv);
-        // norm2: dz2 (residual gradient, flows to y1) and its dropped copy dff (gradient of the FFN output)
-        {
-            Section sl(ce.st, SEC_LN_BWD);
-            TRY(bbbp_layernorm_bwd(ce.st, dyout, z2, P[ix.layer(l, L_N2W)], c.f(o.mean2), c.f(o.rstd2), dz2, plan.drop ? dff : nullptr,
-                                   nullptr, nullptr, B, F, p_drop, site_seed(d->seed, l, 3)));
-        }
-        // linear2 input gradient, then ReLU (+ dropout: hff is the post-dropout value, hff > 0 <=> active and kept)
-        // the ReLU / dropout mask rides in the GEMM epilogue; the bias gradient (a column sum) is a leaf
-        {
-            Section sg(ce.st, SEC_FFN2_DGRAD);
-            bbbp_gemm_desc g = gemm_desc(0, 0, B, DFF, F, 1.f, dff, F, P[ix.layer(l, L_W2)], DFF, dhff, DFF);
-            g.gate = hff; g.ldg = DFF; g.gate_scale = inv_keep;
-            TRY(bbbp_gemm_f32_grouped(ce.st, &g, 1, ce.scratch(), ce.scratch_bytes()));
-        }
-        // leaves of this half layer (they only read per-layer buffers, so ONE event per half layer orders them all)
-        TRY(leaf_after(ce));
-        {
-            Section sw(cl.st, SEC_FFN2_WGRAD);
-            TRY(linear_bwd_weight_bias(cl, dff, F, hff, DFF, G[ix.layer(l, L_W2)], G[ix.layer(l, L_B2)], B, F, DFF));
-        }
-        {
-            Section sw(cl.st, SEC_FFN1_WGRAD);
-            TRY(linear_bwd_weight_bias(cl, dhff, DFF, y1, F, G[ix.layer(l, L_W1)], G[ix.layer(l, L_B1)], B, DFF, F));
-        }
-        // dy1 = dhff W1 + dz2
-        {
-            Section sg(ce.st, SEC_FFN1_DGRAD);
-            TRY(linear_bwd_input(ce, dhff, DFF, P[ix.layer(l, L_W1)], dy1, F, B, DFF, F, dz2, F));
-        }
-        // Layer 0 is the end of the pass: whatever its leaves still hold after the chain's last kernel is the step's tail.  Its LayerNorm
-        // parameter gradients only need dyout and dy1, so they start here (one more event) instead of after the attention block.
-        const bool ln_grads_early = l == 0 && ss != nullptr;
-        if (ln_grads_early) { TRY(leaf_after(ce)); TRY(layer_norm_grads(l)); }
-        // norm1
-        {
-            Section sl(ce.st, SEC_LN_BWD);
-            TRY(bbbp_layernorm_bwd(ce.st, dy1, z1, P[ix.layer(l, L_N1W)], c.f(o.mean1), c.f(o.rstd1), dz1, plan.drop ? dsa : nullptr,
-                                   nullptr, nullptr, B, F, p_drop, site_seed(d->seed, l, 1)));
-        }
-        // out_proj input gradient (folded plan: dVW = Pd^T dsa and dPd = dsa VW^T take the out_proj output's gradient itself)
-        if (!plan.fold) {
-            Section sg(ce.st, SEC_OUTPROJ_DGRAD);
-            TRY(linear_bwd_input(ce, dsa, F, P[ix.layer(l, L_OUTW)], dctx, F, B, F, F));
-        }
-        const float* dattn = plan.fold ? dsa : dctx;
-        // attention backward.  Products that become ready together share a launch (bbbp_gemm_f32_grouped):
-        //   dV_h = Pd_h^T dctx_h -> dqkv[:, 2F + hD]   |   dPd_h = dctx_h V_h^T
-        const float* pdp = c.f(o.pd);
-        std::optional<Section> sec_attn;
-        sec_attn.emplace(ce.st, SEC_ATTN_BWD);
-        if (plan.flash) {
-            TRY(bbbp_attn_small_bwd(ce.st, qkv, ctx, c.f(o.lse), dctx, dqkv, B, F, NH, scale, p_drop, site_seed(d->seed, l, 0),
-                                    o.keep ? c.u8(o.keep) : nullptr));
-        } else {
+        float* qkv = c.f(o.qkv); float* dqkv = c.f(plan.lgrad[l].dqkv); float* dprob = c.f(plan.dprob);
         // exact-global-batch mode: keys / values are the gathered rows of every rank; dK | dV of ALL keys (this rank's queries' share)
         // go to dkvg and come back reduce-scattered
         const float* kmat = plan.exact ? c.f(o.kvg) : qkv + F; const float* vmat = plan.exact ? c.f(o.kvg) + F : qkv + 2 * F;
@@ -1244,11 +1154,11 @@ static int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& 
         float* dkmat = plan.exact ? c.f(plan.dkvg) : dqkv + F; float* dvmat = plan.exact ? c.f(plan.dkvg) + F : dqkv + 2 * F;
         {
             bbbp_gemm_desc g[2] = {
-                gemm_desc(1, 0, Bk, D, B, 1.f, pdp, Bk, dattn, F, dvmat, ldkv, NH, (long)B * Bk, D, D),
+                gemm_desc(1, 0, Bk, D, B, 1.f, c.f(o.pd), Bk, dattn, F, dvmat, ldkv, NH, (long)B * Bk, D, D),
                 gemm_desc(0, 1, B, Bk, D, 1.f, dattn, F, vmat, ldkv, dprob, Bk, NH, D, D, (long)B * Bk)};
             TRY(bbbp_gemm_f32_grouped(ce.st, g, 2, ce.scratch(), ce.scratch_bytes()));
         }
-        TRY(bbbp_softmax_bwd(ce.st, dprob, prob, (long)NH * B, Bk, p_drop, site_seed(d->seed, l, 0)));
+        TRY(bbbp_softmax_bwd(ce.st, dprob, c.f(o.prob), (long)NH * B, Bk, p_drop, site_seed(l, 0)));
         //   dQ_h = scale dS_h K_h   |   dK_h = scale dS_h^T Q_h
         {
             bbbp_gemm_desc g[2] = {
@@ -1262,54 +1172,152 @@ static int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& 
             hipLaunchKernelGGL(kv_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), g_bbbp_small_lds_pad, ce.st, c.f(plan.dkvl), dqkv, n, F);
             BBBP_CHECK_LAUNCH();
         }
-        }
-        sec_attn.reset();
-        TRY(leaf_after(ce));
-        if (!plan.fold) {
-            Section sw(cl.st, SEC_OUTPROJ_WGRAD);
-            TRY(linear_bwd_weight_bias(cl, dsa, F, ctx, F, G[ix.layer(l, L_OUTW)], G[ix.layer(l, L_OUTB)], B, F, F));
-        }
-        if (plan.fold) {
-            // [dWq; dWk | dbq; dbk] straight into the gradient, the folded block dW' | db' = dVW^T [x | 1] into its scratch (one launch), then
-            // dWo = dW' Wv^T + db' bv^T, d[Wv | bv] = Wo^T [dW' | db'] and dbo = column sums of dsa in one more (fold.hip)
-            Section sw(cl.st, SEC_QKV_WGRAD);
-            float* tdw = c.f(plan.ftdw[l]); float* tdb = c.f(plan.ftdb[l]);
-            if (bbbp_gemm_folds_asum(2 * F, F, B, 1) && bbbp_gemm_folds_asum(F, F, B, 1)) {
-                bbbp_gemm_desc gg[2] = {gemm_desc(1, 0, 2 * F, F, B, 1.f, dqkv, 3 * F, xin, F, G[ix.layer(l, L_INW)], F, 1, 0, 0, 0),
-                                        gemm_desc(1, 0, F, F, B, 1.f, dqkv + 2 * F, 3 * F, xin, F, tdw, F, 1, 0, 0, 0)};
-                gg[0].asum = G[ix.layer(l, L_INB)]; gg[1].asum = tdb;
-                TRY(bbbp_gemm_f32_grouped(cl.st, gg, 2, cl.scratch(), cl.scratch_bytes()));
-            } else {
-                TRY(linear_bwd_weight_bias(cl, dqkv, 3 * F, xin, F, G[ix.layer(l, L_INW)], G[ix.layer(l, L_INB)], B, 2 * F, F));
-                TRY(linear_bwd_weight_bias(cl, dqkv + 2 * F, 3 * F, xin, F, tdw, tdb, B, F, F));
-            }
-            TRY(bbbp_outproj_unfold(cl.st, F, B, tdw, tdb, P[ix.layer(l, L_OUTW)], c.f(plan.fwvt[l]), dsa, F, G[ix.layer(l, L_OUTW)],
-                                    G[ix.layer(l, L_OUTB)], G[ix.layer(l, L_INW)] + (size_t)2 * F * F, G[ix.layer(l, L_INB)] + 2 * F));
+        return BBBP_OK;
+    }
+    // folded plan: [dWq; dWk | dbq; dbk] straight into the gradient, the folded block dW' | db' = dVW^T [x | 1] into its scratch (one launch), then
+    // dWo = dW' Wv^T + db' bv^T, d[Wv | bv] = Wo^T [dW' | db'] and dbo = column sums of dsa in one more (fold.hip)
+    int folded_attn_leaves(int l) {
+        Section sw(cl.st, SEC_QKV_WGRAD);
+        const float* xin = layer_input(l);
+        float* dqkv = c.f(plan.lgrad[l].dqkv); float* tdw = c.f(plan.ftdw[l]); float* tdb = c.f(plan.ftdb[l]);
+        if (bbbp_gemm_folds_asum(2 * F, F, B, 1) && bbbp_gemm_folds_asum(F, F, B, 1)) {
+            bbbp_gemm_desc gg[2] = {gemm_desc(1, 0, 2 * F, F, B, 1.f, dqkv, 3 * F, xin, F, GL(l, L_INW), F, 1, 0, 0, 0),
+                                    gemm_desc(1, 0, F, F, B, 1.f, dqkv + 2 * F, 3 * F, xin, F, tdw, F, 1, 0, 0, 0)};
+            gg[0].asum = GL(l, L_INB); gg[1].asum = tdb;
+            TRY(bbbp_gemm_f32_grouped(cl.st, gg, 2, cl.scratch(), cl.scratch_bytes()));
         } else {
-            Section sw(cl.st, SEC_QKV_WGRAD);
-            TRY(linear_bwd_weight_bias(cl, dqkv, 3 * F, xin, F, G[ix.layer(l, L_INW)], G[ix.layer(l, L_INB)], B, 3 * F, F));
+            TRY(linear_bwd_weight_bias(cl, dqkv, 3 * F, xin, F, GL(l, L_INW), GL(l, L_INB), B, 2 * F, F));
+            TRY(linear_bwd_weight_bias(cl, dqkv + 2 * F, 3 * F, xin, F, tdw, tdb, B, F, F));
+        }
+        return bbbp_outproj_unfold(cl.st, F, B, tdw, tdb, PL(l, L_OUTW), c.f(plan.fwvt[l]), c.f(plan.lgrad[l].dz1d), F, GL(l, L_OUTW),
+                                   GL(l, L_OUTB), GL(l, L_INW) + (size_t)2 * F * F, GL(l, L_INB) + 2 * F);
+    }
+    int encoder_layer_bwd_ops(int l) {
+        const LayerOff& o = plan.layer[l];
+        const LayerGrad& g = plan.lgrad[l];
+        float* qkv = c.f(o.qkv); float* ctx = c.f(o.ctx); float* z1 = c.f(o.z1); float* hff = c.f(o.hff); float* z2 = c.f(o.z2);
+        float* dyout = c.f(g.dyout); float* dz2 = c.f(g.dz2); float* dff = c.f(g.dz2d); float* dhff = c.f(g.dhff);
+        float* dy1 = c.f(g.dy1); float* dz1 = c.f(g.dz1); float* dsa = c.f(g.dz1d); float* dqkv = c.f(g.dqkv); float* dctx = c.f(plan.dctx);
+        // norm2: dz2 (residual gradient, flows to y1) and its dropped copy dff (gradient of the FFN output)
+        {
+            Section sl(ce.st, SEC_LN_BWD);
+            TRY(bbbp_layernorm_bwd(ce.st, dyout, z2, PL(l, L_N2W), c.f(o.mean2), c.f(o.rstd2), dz2, plan.drop ? dff : nullptr,
+                                   nullptr, nullptr, B, F, p_drop, site_seed(l, 3)));
+        }
+        // linear2 input gradient, then ReLU (+ dropout: hff is the post-dropout value, hff > 0 <=> active and kept)
+        // the ReLU / dropout mask rides in the GEMM epilogue; the bias gradient (a column sum) is a leaf
+        {
+            Section sg(ce.st, SEC_FFN2_DGRAD);
+            bbbp_gemm_desc gd = gemm_desc(0, 0, B, DFF, F, 1.f, dff, F, PL(l, L_W2), DFF, dhff, DFF);
+            gd.gate = hff; gd.ldg = DFF; gd.gate_scale = inv_keep;
+            TRY(bbbp_gemm_f32_grouped(ce.st, &gd, 1, ce.scratch(), ce.scratch_bytes()));
+        }
+        // leaves of this half layer (they only read per-layer buffers, so ONE event per half layer orders them all)
+        TRY(leaf_after(ce));
+        TRY(ffn_leaves(l, true));
+        // dy1 = dhff W1 + dz2
+        {
+            Section sg(ce.st, SEC_FFN1_DGRAD);
+            TRY(linear_bwd_input(ce, dhff, DFF, PL(l, L_W1), dy1, F, B, DFF, F, dz2, F));
+        }
+        // Layer 0 is the end of the pass: whatever its leaves still hold after the chain's last kernel is the step's tail.  Its LayerNorm
+        // parameter gradients only need dyout and dy1, so they start here (one more event) instead of after the attention block.
+        const bool ln_grads_early = l == 0 && ss != nullptr;
+        if (ln_grads_early) { TRY(leaf_after(ce)); TRY(layer_norm_grads(l)); }
+        // norm1
+        {
+            Section sl(ce.st, SEC_LN_BWD);
+            TRY(bbbp_layernorm_bwd(ce.st, dy1, z1, PL(l, L_N1W), c.f(o.mean1), c.f(o.rstd1), dz1, plan.drop ? dsa : nullptr,
+                                   nullptr, nullptr, B, F, p_drop, site_seed(l, 1)));
+        }
+        // out_proj input gradient (folded plan: dVW = Pd^T dsa and dPd = dsa VW^T take the out_proj output's gradient itself)
+        if (!plan.fold) {
+            Section sg(ce.st, SEC_OUTPROJ_DGRAD);
+            TRY(linear_bwd_input(ce, dsa, F, PL(l, L_OUTW), dctx, F, B, F, F));
+        }
+        {
+            Section sec_attn(ce.st, SEC_ATTN_BWD);
+            if (plan.flash) {
+                TRY(bbbp_attn_small_bwd(ce.st, qkv, ctx, c.f(o.lse), dctx, dqkv, B, F, NH, scale, p_drop, site_seed(l, 0), o.keep ? c.u8(o.keep) : nullptr));
+            } else {
+                TRY(attention_bwd_gemm(l, plan.fold ? dsa : dctx));
+            }
+        }
+        TRY(leaf_after(ce));
+        if (plan.fold) {
+            TRY(folded_attn_leaves(l));
+        } else {
+            TRY(outproj_leaf(l, true));
+            TRY(inproj_leaf(l, true));
         }
         if (ln_grads_early) TRY(record_layer_bucket(l));
         else TRY(layer_norm_leaves(l));
         if (l > 0 || d->need_input_grad) {
             Section sg(ce.st, SEC_QKV_DGRAD);
-            TRY(linear_bwd_input(ce, dqkv, 3 * F, plan.fold ? c.f(plan.fwf[l]) : P[ix.layer(l, L_INW)], l > 0 ? c.f(plan.lgrad[l - 1].dyout) : c.f(plan.dA), F, B, 3 * F, F, dz1, F));
+            TRY(linear_bwd_input(ce, dqkv, 3 * F, plan.fold ? c.f(plan.fwf[l]) : PL(l, L_INW), l > 0 ? c.f(plan.lgrad[l - 1].dyout) : c.f(plan.dA), F, B, 3 * F, F, dz1, F));
         }
+        return BBBP_OK;
     }
-    if (ds) {
+};
+
+// The forward step: fork; image branch; fingerprint branch; join; fusion block and head.
+int forward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& plan, const Schedule& s, const float* const* P, float* const* bn_running,
+                    const float* fingerprint, const float* image, float* out, void* workspace) {
+    SeedScope seed_scope(reinterpret_cast<const unsigned long long*>(static_cast<char*>(workspace) + plan.seed_slot));
+    Step t(stream, d, plan, s, P, nullptr, fingerprint, image, workspace);
+    // a deferred optimizer slice that is NOT this model's image-FC weight (another model's step, another tensor): wait before anything runs
+    if (bbbp_param_pending_elsewhere(P[t.ix.ifc_w()])) (void)bbbp_param_wait(t.c.st, nullptr);
+    TRY(t.fork(false));
+    std::optional<Partition> part(std::in_place, t.ss != nullptr);           // ends early with reset(), or at any return
+    TRY(t.image_fwd());          // enqueued first so the GPU is busy while the host feeds the encoder's launches
+    {
+        Section sec_enc(t.ce.st, SEC_ENCODER_FWD);
+        if (s.enc_fwd == ENC_SLICED) TRY(t.encoder_fwd_sliced());
+        else if (s.enc_fwd == ENC_ROWS) TRY(t.encoder_fwd_rows());
+        else TRY(t.encoder_fwd_ops());
+    }
+    if (t.ss) TRY(join_side(t.c.st, t.ss));        // fusion needs both halves of `combined`
+    part.reset();
+    Section sec_head(t.c.st, SEC_HEAD_FWD);
+    BBBP_CHECK_ARG(!plan.exact || s.head_fwd_fused, "the exact-global-batch mode needs the fused head (BBBP_FUSED_HEAD=1)");
+    return s.head_fwd_fused ? t.head_fwd_fused(bn_running, out) : t.head_fwd_ops(bn_running, out);
+}
+
+// The backward step: fork; head and fusion block; image branch; fingerprint branch; join.  `plan`, `s`: as for forward_enqueue
+int backward_enqueue(void* stream, const bbbp_mixed_desc* d, const Plan& plan, const Schedule& s, const float* const* P, float* const* G,
+                     const float* fingerprint, const float* image, const float* dout, void* workspace) {
+    SeedScope seed_scope(reinterpret_cast<const unsigned long long*>(static_cast<char*>(workspace) + plan.seed_slot));
+    BBBP_CHECK_ARG(!plan.inference, "mixed_backward: the forward call used an inference workspace (desc.inference = 1)");
+    (void)bbbp_param_wait(static_cast<hipStream_t>(stream), nullptr);      // (a deferred optimizer slice: normally consumed by the forward pass already)
+    Step t(stream, d, plan, s, P, G, fingerprint, image, workspace);
+    TRY(device_state(&t.ds));
+    TRY(t.fork(true));
+    std::optional<Section> sec;          // the caller's stream: head, then one section per kernel of the image branch
+    sec.emplace(t.c.st, SEC_HEAD_BWD);
+    BBBP_CHECK_ARG(!plan.exact || s.head_bwd_fused, "the exact-global-batch mode needs the fused head backward (bbbp_set_fused_head_bwd(1))");
+    TRY(s.head_bwd_fused ? t.head_bwd_fused(dout) : t.head_bwd_ops(dout));
+    // both branches only READ dcomb from here on
+    if (t.ss) { TRY(after(t.ss, t.c.st, t.ce.st)); TRY(after(t.ss, t.c.st, t.cl.st)); }
+    Partition part(t.ss != nullptr);
+    TRY(t.image_bwd(sec));          // enqueued first: the host reaches its long kernels sooner
+    if (s.head_bwd_fused) TRY(t.head_leaves(dout));
+    Section sec_encb(t.ce.st, SEC_ENCODER_BWD);
+    TRY(t.fingerprint_fc_leaf());
+    if (s.enc_bwd == ENC_SLICED) TRY(t.encoder_bwd_sliced());
+    else if (s.enc_bwd == ENC_ROWS) TRY(t.encoder_bwd_rows());
+    else TRY(t.encoder_bwd_ops());
+    if (t.ds) {
         // bucket 1 is final when the chain AND the leaves are: make the leaf stream wait for the chain's tail, record there
-        if (ss) TRY(after(ss, ce.st, cl.st));
-        TRY(record_bucket(ds->bucket1, cl.st));
+        if (t.ss) TRY(after(t.ss, t.ce.st, t.cl.st));
+        TRY(record_bucket(t.ds->bucket1, t.cl.st));
     }
-    if (ss) {
-        TRY(join_side(c.st, ss));
-        BBBP_CHECK_HIP(hipEventRecord(ss->join2, ss->leaf));
-        BBBP_CHECK_HIP(hipStreamWaitEvent(c.st, ss->join2, 0));
+    if (t.ss) {
+        TRY(join_side(t.c.st, t.ss));
+        BBBP_CHECK_HIP(hipEventRecord(t.ss->join2, t.ss->leaf));
+        BBBP_CHECK_HIP(hipStreamWaitEvent(t.c.st, t.ss->join2, 0));
     }
     return BBBP_OK;
 }
-
-namespace {
 
 hipStream_t capture_stream() {
     static hipStream_t cs = nullptr;       // captures never run on the caller's stream: the legacy default stream cannot be captured
@@ -1348,11 +1356,12 @@ int run_or_replay(const GraphKey& key, hipStream_t st, F&& enqueue) {
     return enqueue(st);
 }
 
-GraphKey make_key(int kind, const bbbp_mixed_desc* d, const void* a, const void* b, const void* c, const void* ws, uint64_t phash) {
+GraphKey make_key(int kind, const bbbp_mixed_desc* d, const Plan& plan, const Schedule& s, const void* a, const void* b, const void* c,
+                  const void* ws, uint64_t phash) {
     GraphKey k{};
     k.kind = kind; k.d = *d; k.d.seed = 0;
     k.ptr[0] = a; k.ptr[1] = b; k.ptr[2] = c; k.ptr[3] = ws;
-    k.phash = phash; k.overlap = overlap_enabled() ? 1 : 0; k.st = nullptr;
+    k.phash = phash; k.s = s; k.fold = plan.fold; k.flash = plan.flash; k.attn_b3 = plan.attn_b3; k.total = plan.total; k.st = nullptr;
     return k;
 }
 
@@ -1455,11 +1464,9 @@ extern "C" int bbbp_mixed_forward(void* stream, const bbbp_mixed_desc* d, const 
     std::lock_guard<std::mutex> engine_lock(g_engine_mutex);
     Plan plan;
     TRY(make_plan(d, &plan));
+    const Schedule sched = make_schedule(plan, false);
     BBBP_CHECK_ARG(P && fingerprint && image && out && workspace && bn_running, "mixed_forward: null pointer");
-    if (workspace_bytes < plan.total) {
-        bbbp_set_error("mixed_forward: workspace %zu < %zu bytes", workspace_bytes, plan.total);
-        return BBBP_ERR_WORKSPACE;
-    }
+    if (workspace_bytes < plan.total) { bbbp_set_error("mixed_forward: workspace %zu < %zu bytes", workspace_bytes, plan.total); return BBBP_ERR_WORKSPACE; }
     hipStream_t st = static_cast<hipStream_t>(stream);
     // the call's dropout seed goes to device memory first (never part of a graph: it changes every call)
     if (plan.drop) {
@@ -1470,12 +1477,9 @@ extern "C" int bbbp_mixed_forward(void* stream, const bbbp_mixed_desc* d, const 
     const int np = PIdx(d).count();
     uint64_t h = hash_ptrs(reinterpret_cast<const void* const*>(P), np);
     h = hash_ptrs(reinterpret_cast<const void* const*>(bn_running), 2, h);
-    const GraphKey key = make_key(0, d, fingerprint, image, out, workspace, h);
-    if (d->collective)              // host callbacks between the launches: nothing to capture
-        return forward_enqueue(st, d, plan, P, bn_running, fingerprint, image, out, workspace);
-    return run_or_replay(key, st, [&](hipStream_t s) {
-        return forward_enqueue(s, d, plan, P, bn_running, fingerprint, image, out, workspace);
-    });
+    const GraphKey key = make_key(0, d, plan, sched, fingerprint, image, out, workspace, h);
+    auto enqueue = [&](hipStream_t s) { return forward_enqueue(s, d, plan, sched, P, bn_running, fingerprint, image, out, workspace); };
+    return d->collective ? enqueue(st) : run_or_replay(key, st, enqueue);      // (host callbacks between the launches: nothing to capture)
 }
 
 extern "C" int bbbp_mixed_backward(void* stream, const bbbp_mixed_desc* d, const float* const* P, float* const* G,
@@ -1484,19 +1488,14 @@ extern "C" int bbbp_mixed_backward(void* stream, const bbbp_mixed_desc* d, const
     std::lock_guard<std::mutex> engine_lock(g_engine_mutex);
     Plan plan;
     TRY(make_plan(d, &plan));
+    const Schedule sched = make_schedule(plan, true);
     BBBP_CHECK_ARG(P && G && fingerprint && image && dout && workspace, "mixed_backward: null pointer");
-    if (workspace_bytes < plan.total) {
-        bbbp_set_error("mixed_backward: workspace %zu < %zu bytes", workspace_bytes, plan.total);
-        return BBBP_ERR_WORKSPACE;
-    }
+    if (workspace_bytes < plan.total) { bbbp_set_error("mixed_backward: workspace %zu < %zu bytes", workspace_bytes, plan.total); return BBBP_ERR_WORKSPACE; }
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int np = PIdx(d).count();
     uint64_t h = hash_ptrs(reinterpret_cast<const void* const*>(P), np);
     h = hash_ptrs(reinterpret_cast<const void* const*>(G), np, h);
-    const GraphKey key = make_key(1, d, fingerprint, image, dout, workspace, h);
-    if (d->collective)
-        return backward_enqueue(st, d, plan, P, G, fingerprint, image, dout, workspace);
-    return run_or_replay(key, st, [&](hipStream_t s) {
-        return backward_enqueue(s, d, plan, P, G, fingerprint, image, dout, workspace);
-    });
+    const GraphKey key = make_key(1, d, plan, sched, fingerprint, image, dout, workspace, h);
+    auto enqueue = [&](hipStream_t s) { return backward_enqueue(s, d, plan, sched, P, G, fingerprint, image, dout, workspace); };
+    return d->collective ? enqueue(st) : run_or_replay(key, st, enqueue);
 }

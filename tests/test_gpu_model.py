@@ -268,6 +268,47 @@ def test_graph_replay_is_bit_identical_to_eager(dev):
     assert cap2.value > cap1.value and rep2.value > rep1.value, "no graph was captured/replayed: check the cache key"
 
 
+def test_graph_is_not_replayed_after_a_knob_changed_the_schedule(dev):
+    """The graph cache's key holds what a call decided from its knobs.  With graphs on, a forward call with fixed arguments is
+    replayed from its third sighting on; after bbbp_set_fold_outproj(0) (at F = 167 the out_proj fold moves workspace offsets and
+    removes launches) the same arguments are a first sighting again: no replay, and the output of the schedule now in force."""
+    import ctypes
+    from bbbp_amd import _lib
+    L = _lib.lib()
+    m = build(167, 11, dev).eval()
+    fp, img, _ = synth_inputs(78, 24, 167, 49152)
+    fp, img = fp.to(dev), img.to(dev)
+
+    def replays():
+        r = ctypes.c_long(0)
+        L.bbbp_graph_stats(None, ctypes.byref(r))
+        return r.value
+
+    def call():          # the output is copied to the host and freed, so the next call gets the same device addresses
+        with torch.no_grad():
+            return m(fp, img).cpu()
+
+    old_graphs, old_fold = L.bbbp_set_graphs(1), None
+    try:
+        r0 = replays()
+        for _ in range(8):
+            out_folded = call()
+            if replays() > r0:
+                break
+        assert replays() == r0 + 1, "the forward call was never replayed: same arguments, same key expected"
+        old_fold = L.bbbp_set_fold_outproj(0)
+        out_after = call()
+        assert replays() == r0 + 1, "a graph captured under another fold setting was replayed"
+        L.bbbp_set_graphs(0)
+        out_eager = call()
+        assert torch.equal(out_after, out_eager)
+        assert torch.isfinite(out_folded).all()
+    finally:
+        if old_fold is not None:
+            L.bbbp_set_fold_outproj(old_fold)
+        L.bbbp_set_graphs(old_graphs)
+
+
 @pytest.mark.parametrize("B,steps", [(64, 12), (512, 40)])
 def test_stream_overlap_is_bit_identical_to_one_stream(dev, B, steps):
     """The three-stream schedule (image branch | encoder chain | weight-gradient leaves) only reorders independent work:

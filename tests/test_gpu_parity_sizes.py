@@ -105,9 +105,9 @@ def check_b512_step_against_float64(dev, F, seed, conv_mask, max_flips=8):
 def test_headline_batch_fwd_bwd_against_oracle(dev, conv_mask):
     """BASELINE config 3 exactly as bench.py runs it: B = 512, F = 167, the library's DEFAULT conv mask 252 (conv2 forward / data
     gradient / weight gradient AND conv1's weight gradient in the split-bf16 form -- conv_b3_wgrad3_kernel at its B = 512 slab
-    count; bit 6, conv1's split-bf16 forward, is held back by the engine beside a training step's encoder chain and runs in the
-    B = 4096 screening test below and in test_gpu_config2.py), and the two all-float32 alternatives (Winograd on the 192-CU
-    partition, direct)."""
+    count; bit 6, conv1's split-bf16 forward, runs here too: beside a training step's encoder chain the engine takes its
+    software-pipelined one-work-group-per-CU form, BBBP_C1_TRAIN's default), and the two all-float32 alternatives (Winograd on the
+    192-CU partition, direct)."""
     assert _lib.lib().bbbp_get_conv_winograd() == 252, "the library default changed: run the B = 512 step under the new default too"
     assert check_b512_step_against_float64(dev, 167, 20250113, conv_mask) == 90
 
