@@ -40,8 +40,24 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 int bbbp_num_cus();   // cached multiProcessorCount of the current device
+// Grid of a persistent kernel over `nwork` items in runs of `nmb`: `want` work-groups, rounded down to a multiple of 8 * nmb (whole XCD
+// rounds, see xcd_adjacent) and capped by the work
+static inline int persistent_grid(int want, int nmb, int nwork) {
+    int grid = want;
+    if (grid >= 8 * nmb) grid -= grid % (8 * nmb);
+    if (grid > nwork) grid = nwork - nwork % nmb;
+    return grid < nmb ? nmb : grid;
+}
 int bbbp_ensure_dyn_lds(const void* kernel, size_t bytes);   // hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device)
-
+// Opt the kernel in to `lds` bytes of dynamic LDS and launch it.  (hipLaunchKernel, not <<<>>>: a triple-chevron launch inside a header
+// template changes the order in which every including file's device variables are emitted.)
+template <class P>
+int launch_lds(void (*kernel)(P), dim3 grid, int threads, size_t lds, hipStream_t st, const P& p) {
+    if (int rc = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(kernel), lds)) return rc;
+    void* args[] = {const_cast<P*>(&p)};
+    BBBP_CHECK_HIP(hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, dim3(threads), args, lds, st));
+    return BBBP_OK;
+}
 // Knobs.  Every BBBP_* environment variable is an integer read through bbbp_env_int (`dflt` when unset); call sites keep the value in a
 // `static const`, so it is read once.  bbbp_env is the raw string (NULL when unset) for the one knob that is not parsed as a number.
 const char* bbbp_env(const char* name);
@@ -63,26 +79,25 @@ static inline int knob_bool(int v) { return v != 0; }
 // grids left free.  Measured without it: a 5 us kernel sharing CUs with a conv kernel takes 35-85 us.
 extern thread_local int g_bbbp_reserved_cus;
 extern thread_local size_t g_bbbp_small_lds_pad;
-// Which form of a conv stage's kernels a caller wants: chosen by the engine from its plan (engine.hip), or from the calling thread's two
-// settable values by the C entry points (conv.hip); passed down to the launch functions below as arguments.
+// What a caller wants of a conv stage's kernels: set by the engine from its plan (engine.hip), or from the calling thread's two settable
+// values by the C entry points (conv.hip).  conv_choice (conv.hip) weighs them against the BBBP_CONV_WINOGRAD mask and the knobs; the
+// measurements behind each field stand there.
 struct ConvPrefs {
-    // keep the first conv stage's forward on the f32 kernel for this call even when bit 6 of the conv mask selects the split-bf16
-    // form.  Set while a training step's encoder chain runs beside the image branch: the split-bf16 kernel is faster alone (0.19 vs 0.26 ms
-    // at B = 512) but holds 2 x 248 registers per lane slot on every SIMD, and the forward pass of that step is bound by the encoder's
-    // latency chain, which then finds no wave slots (measured: conv1 0.31 -> 0.20 ms in-step, encoder forward 1.21 -> 1.33, step 2.61 -> 2.70)
-    int conv1_fwd_f32 = 0;
-    // work-groups per CU for the split-bf16 conv1 forward (0 = the kernel's own default).  The software-pipelined form keeps the
-    // matrix pipe busy with ONE wave per SIMD, so beside an encoder chain the engine asks for one work-group per CU (half the register file and
-    // 100 KB of LDS stay free for the chain's kernels)
-    int conv1_fwd_per_cu = 0;
-    // conv_b3.hip, forward of the 64 x 64-map stages: 1 = the software-pipelined one-work-group-per-CU kernel (what the engine asks for while an encoder
-    // chain runs beside the image branch: slower alone, but it leaves the chain three quarters of every SIMD), 0 = two work-groups per CU
-    int conv2_fwd_pipe = 0;
-    // conv2's weight gradient on the structured-sparse MFMA (conv_b3.hip: conv_b3_wgrad_sp_kernel) has an 8-wave form (fastest alone: two waves
-    // of 256 registers per SIMD) and a 4-wave form that leaves ~200 registers per lane slot to the fingerprint branch's kernels; the engine
-    // asks for the latter while an encoder chain runs beside the image branch (0 = no preference: 8 waves)
-    int wgrad_beside_encoder = 0;
+    int conv1_fwd_f32 = 0;         // keep the first stage's forward on the f32 kernel although the mask selects its split-bf16 form
+    int conv1_fwd_per_cu = 0;      // work-groups per CU for the split-bf16 conv1 forward (0 = BBBP_C1_PER_CU)
+    int conv2_fwd_pipe = 0;        // forward of the 64 x 64-map stages: the software-pipelined one-work-group-per-CU kernel
+    int wgrad_beside_encoder = 0;  // conv2's structured-sparse weight gradient in its 4-wave form (0 = no preference: 8 waves)
 };
+// Bits of the BBBP_CONV_WINOGRAD mask (bbbp_set_conv_winograd): which stages leave the f32 direct kernels, and for what
+enum ConvMaskBit {
+    CONV_WINO_FWD = 1, CONV_WINO_DGRAD = 2,                        // conv2 forward / data gradient as Winograd F(2x2,3x3) (conv_wino.hip)
+    CONV_B3_FWD = 4, CONV_B3_DGRAD = 8, CONV_B3_WGRAD = 16,        // conv2-family stages as split-bf16 (conv_b3.hip; before the Winograd bits)
+    CONV_B3_C1_WGRAD = 32, CONV_B3_C1_FWD = 64,                    // conv1's split-bf16 weight gradient (conv_b3.hip) / forward (conv_b3c1.hip)
+    CONV_B3_WGRAD_SPARSE = 128, CONV_B3_WGRAD_SPARSE4 = 256,       // the weight gradient on the 2:4 structured-sparse MFMA / (test hook) its 4-wave form
+    CONV_MASK_ALL = 511
+};
+// The kernel form conv_choice picks for one call; the launchers below receive it decided and decide nothing
+enum class ConvForm { F32Direct, Winograd, SplitBf16, SplitBf16Pipe, Conv1SplitBf16, Conv1SplitBf16Pipe, WgradDense, WgradSparse8, WgradSparse4 };
 // conv.hip: the C entry points bbbp_conv3x3_relu_pool_fwd / _bwd_weight with the form choices as an argument
 int conv3x3_relu_pool_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int cin, int cout,
                           int H, int W, void* workspace, size_t workspace_bytes, const ConvPrefs& prefs);
@@ -138,24 +153,25 @@ int bbbp_wino_conv2_fwd(hipStream_t st, const float* x, const float* w, const fl
 int bbbp_wino_conv2_dgrad(hipStream_t st, const float* gy, const uint8_t* gmask, const float* w, float* dx, int B, float* workspace);
 int bbbp_wino_last_clock(unsigned long long* shader_cycles, unsigned long long* ticks_100mhz);
 // conv_b3.hip: the same stage as a direct implicit GEMM on the bf16 matrix pipe with every float32 operand split into three bf16
-// pieces (six products per float32 product, float32 accumulate); workspace = bbbp_b3_workspace_bytes() of pre-split filters
-size_t bbbp_b3_workspace_bytes();
-// round 4: the same kernels for the two large stages of the wide / deep variant (64 -> 128 @ 64 x 64, 128 -> 256 @ 32 x 32)
+// pieces (six products per float32 product, float32 accumulate); workspace = bbbp_b3_workspace_bytes(cin, cout) of pre-split filters.
+// Round 4: the same kernels for the two large stages of the wide / deep variant (64 -> 128 @ 64 x 64, 128 -> 256 @ 32 x 32)
 bool bbbp_b3_conv_supported(int cin, int cout, int hw);
 size_t bbbp_b3_workspace_bytes(int cin, int cout);
+// form: SplitBf16 (per_cu work-groups per CU; probe: the phase-stamping build of the flagship kernel) or SplitBf16Pipe (64 x 64 maps)
 int bbbp_b3_conv_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int cin, int cout, void* workspace,
-                     int pipe);      // pipe: ConvPrefs::conv2_fwd_pipe (64 x 64 maps)
-int bbbp_b3_conv_dgrad(hipStream_t st, const float* gy, const uint8_t* gmask, const float* w, float* dx, int B, int cin, int cout, void* workspace);
-// form: 0 dense split-bf16, 1 structured-sparse MFMA (8 waves, or 4 with beside_encoder: ConvPrefs::wgrad_beside_encoder), 2 structured-sparse, 4 waves
-// (cin_total, cout_total, groups: the stage's channel counts and the work-groups per (32 ci, 64 co) block pair; grid = pairs * groups;
-//  map: 64 x 64 maps, or 32 x 32 for the sparse forms)
-int bbbp_b3_conv2_wgrad(hipStream_t st, const float* x, const float* gy, const uint8_t* mask, float* slab, float* bslab, int B, int grid, int form,
-                        int beside_encoder, int cin_total = 32, int cout_total = 64, int groups = 0, int map = 64);
+                     ConvForm form, int per_cu, bool probe);
+int bbbp_b3_conv_dgrad(hipStream_t st, const float* gy, const uint8_t* gmask, const float* w, float* dx, int B, int cin, int cout, void* workspace,
+                       ConvForm form, int per_cu, bool probe);
+// form: WgradDense (64 x 64 maps), WgradSparse8 or WgradSparse4 (64 x 64 or 32 x 32 maps).  cin_total, cout_total: the stage's channel
+// counts; groups: work-groups per (32 ci, 64 co) block pair, grid = pairs * groups; map: the stage's map size
+int bbbp_b3_conv2_wgrad(hipStream_t st, const float* x, const float* gy, const uint8_t* mask, float* slab, float* bslab, int B, int grid, ConvForm form,
+                        int cin_total, int cout_total, int groups, int map);
 int bbbp_b3_last_clock(unsigned long long* shader_cycles, unsigned long long* ticks_100mhz);
-// conv_b3c1.hip: forward of the first stage (3 -> 32 @ 128x128) in the same arithmetic, channel-innermost LDS strip, no operand assembly
+// conv_b3c1.hip: forward of the first stage (3 -> 32 @ 128x128) in the same arithmetic, channel-innermost LDS strip, no operand assembly.
+// form: Conv1SplitBf16Pipe (software-pipelined) or Conv1SplitBf16 (phase by phase), per_cu work-groups per CU
 size_t bbbp_b3_conv1_fwd_workspace_bytes();
 int bbbp_b3_conv1_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, void* workspace,
-                      int want_per_cu);      // ConvPrefs::conv1_fwd_per_cu
+                      ConvForm form, int per_cu);
 int bbbp_b3_conv1_wgrad(hipStream_t st, const float* x, const float* gy, const uint8_t* mask, float* slab, float* bslab, int B, int grid);
 int bbbp_wino_last_phases(unsigned long long* phases4);     // BBBP_WINO_PROBE=1 builds of the kernel only
 // rowops.hip: a slice of the optimizer step deferred to a side stream (bbbp_adamw_step_deferred).  Entry points that read parameters

@@ -25,6 +25,8 @@
 //   second kernel sums the slabs in a fixed order (bit-reproducible; no float atomics).
 #include "common.h"
 #include "bbbp_hip.h"
+#include <limits.h>
+#include <algorithm>
 #include <stdlib.h>
 
 namespace {
@@ -752,9 +754,6 @@ __global__ __launch_bounds__(1024) void conv_wgrad3_reduce_kernel(const float* s
     }
 }
 
-template <typename K>
-int set_lds(K kernel, size_t bytes) { return bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(kernel), bytes); }
-
 template <int CIN, int COUT, int W, int MODE>
 int launch_conv(const ConvParams& p, hipStream_t st) {
     using C = ConvCfg<CIN, COUT, W, MODE>;
@@ -764,8 +763,6 @@ int launch_conv(const ConvParams& p, hipStream_t st) {
     const bool part = g_bbbp_reserved_cus > 0;
     size_t lds = C::LDS_BYTES;
     if (part && lds < BBBP_CONV_MIN_LDS) lds = BBBP_CONV_MIN_LDS;
-    int rc = set_lds(conv3x3_kernel<CIN, COUT, W, MODE>, lds);
-    if (rc) return rc;
     int nstrips = p.B * (p.H / C::TH);
     int per_cu = (int)((160 * 1024) / lds);
     if (per_cu > 2) per_cu = 2;      // measured: more than 2 groups per CU buys nothing and crowds out the side-stream kernels
@@ -776,9 +773,7 @@ int launch_conv(const ConvParams& p, hipStream_t st) {
     if (cus < 1) cus = 1;
     int grid = cus * per_cu;
     if (grid > nstrips) grid = nstrips;
-    hipLaunchKernelGGL((conv3x3_kernel<CIN, COUT, W, MODE>), dim3(grid), dim3(C::NT), lds, st, p);
-    BBBP_CHECK_LAUNCH();
-    return BBBP_OK;
+    return launch_lds(conv3x3_kernel<CIN, COUT, W, MODE>, grid, C::NT, lds, st, p);
 }
 
 // shapes on the reference's paths: the flagship CNN (3->32 @128, 32->64 @64; ...20250113.py:84-90) and the wide/deep
@@ -789,73 +784,130 @@ inline bool supported(int cin, int cout, int h, int w) {
            (cin == 64 && cout == 128 && w == 64) || (cin == 128 && cout == 256 && w == 32);
 }
 
-// Algorithm of the 32 -> 64 @ 64x64 stage.  bit 0 / 1: forward / data gradient as Winograd F(2x2,3x3) (conv_wino.hip);
-// bit 2 / 3 / 4: forward / data gradient / weight gradient as the split-bf16 direct form (conv_b3.hip; takes precedence over
-// the Winograd bit).
-// default since round 2: all three as split-bf16 (28; the weight gradient alone 0.63 -> 0.42 ms, and beside it the encoder's
-// backward chain runs 1.93 -> 1.45 ms: 4 waves x 180 registers instead of conv_wgrad32's 8 x 224) -- alone as fast as the Winograd form (0.42 / 0.41 vs 0.42 / 0.44 ms at B = 512), and in
-// the training step 0.47 / 0.42 vs 0.57 / 0.61 ms: 66 KB of LDS and 160 registers per wave leave room for the other branch's
-// kernels on every CU (the Winograd work-groups take whole CUs and give 64 of them up), and a bf16 MFMA holds the vector issue
-// for 8 of its 32 cycles where the f32 MFMA blocks it for all 64
-// round 3: + bit 7, conv2's weight gradient on the 2:4 structured-sparse MFMA (conv_b3.hip: conv_b3_wgrad_sp_kernel; 0.54 -> 0.33 ms in
-// the step); bit 8 (test hook) forces its 4-wave form
-Knob g_winograd{"BBBP_CONV_WINOGRAD", 252, [](int v) { return v & 511; }};
-inline int winograd_mask() { return g_winograd.get(); }
-int g_last_clock_wino = 0;
+// BBBP_CONV_WINOGRAD (bbbp_set_conv_winograd): the ConvMaskBit set (common.h).  Default since round 2: conv2's three ops as split-bf16 (28; the
+// weight gradient alone 0.63 -> 0.42 ms, and beside it the encoder's backward chain runs 1.93 -> 1.45 ms: 4 waves x 180 registers instead of
+// conv_wgrad32's 8 x 224) -- alone as fast as the Winograd form (0.42 / 0.41 vs 0.42 / 0.44 ms at B = 512), and in the training step 0.47 / 0.42
+// vs 0.57 / 0.61 ms: 66 KB of LDS and 160 registers per wave leave room for the other branch's kernels on every CU (the Winograd work-groups
+// take whole CUs and give 64 of them up), and a bf16 MFMA holds the vector issue for 8 of its 32 cycles where the f32 MFMA blocks it for all 64.
+// Round 3: + conv1's split-bf16 forms and conv2's weight gradient on the structured-sparse MFMA (0.54 -> 0.33 ms in the step).
+Knob g_winograd{"BBBP_CONV_WINOGRAD", 252, [](int v) { return v & CONV_MASK_ALL; }};
 // the calling thread's two settable form choices (bbbp_set_conv2_fwd_pipe, bbbp_set_conv_wgrad_beside_encoder): read by the C entry points only
 thread_local int g_bbbp_conv2_fwd_pipe = 0;
 thread_local int g_bbbp_conv_wgrad_beside_encoder = 0;
 
+// The environment's say in the choice below, read once per process
+struct ConvKnobs {
+    int c2_pipe;               // BBBP_C2_PIPE: set (any integer), it wins over every caller's ConvPrefs::conv2_fwd_pipe; INT_MIN = unset
+    int c2_dgrad_pipe;         // BBBP_C2_DGRAD_PIPE: the pipelined kernel for the data gradient of the 64 x 64-map stages (default off)
+    int b3_probe;              // BBBP_B3_PROBE: the phase-stamping build of the flagship split-bf16 kernel (bbbp_conv_b3_phases); never pipelined
+    int b3_per_cu;             // BBBP_B3_PER_CU: work-groups per CU of the split-bf16 conv2-family kernels, 1 or 2 (default 2)
+    int wgrad_sparse_waves;    // BBBP_C2_WGRAD_SPARSE_WAVES: 8 or 4 forces that structured-sparse form (0: by mask and preference)
+    int c1_pipe;               // BBBP_C1_PIPE: round 4's software-pipelined conv1 forward (0: round 3's phase-by-phase kernel)
+    int c1_per_cu;             // BBBP_C1_PER_CU: its work-groups per CU, 1..4 (default 2), where the caller has no preference
+};
+const ConvKnobs& conv_knobs() {
+    static const ConvKnobs k{bbbp_env_int("BBBP_C2_PIPE", INT_MIN), bbbp_env_int("BBBP_C2_DGRAD_PIPE", 0), bbbp_env_int("BBBP_B3_PROBE", 0),
+                             clampi(bbbp_env_int("BBBP_B3_PER_CU", 2), 1, 2), bbbp_env_int("BBBP_C2_WGRAD_SPARSE_WAVES", 0),
+                             bbbp_env_int("BBBP_C1_PIPE", 1), clampi(bbbp_env_int("BBBP_C1_PER_CU", 2), 1, 4)};
+    return k;
+}
+
+enum class ConvOp { Fwd, Dgrad, Wgrad };
+enum class ConvClock { Keep, F32, Winograd, SplitBf16 };      // whose stamps bbbp_conv_last_clock reads after the call (Keep: the op leaves none)
+struct ConvChoice {
+    ConvForm form = ConvForm::F32Direct;
+    size_t workspace = 0;      // bytes the call needs: prepared filters (forward, data gradient) or partial slabs (weight gradient)
+    ConvClock clock = ConvClock::F32;
+    int per_cu = 0;            // split-bf16 forward / data gradient: work-groups per CU
+    bool probe = false;        // ConvKnobs::b3_probe
+};
+ConvClock g_last_clock = ConvClock::F32;
+
+// The one place a conv call's kernel form is chosen (shapes: `supported` above; hw = map height = width).
+ConvChoice conv_choice(ConvOp op, int cin, int cout, int hw, int mask, const ConvPrefs& prefs, const ConvKnobs& kn) {
+    ConvChoice c;
+    const bool b3_stage = bbbp_b3_conv_supported(cin, cout, hw), conv2 = cin == 32 && cout == 64, conv1 = cin == 3 && cout == 32 && hw == 128;
+    auto at_least = [&](size_t bytes) { if (c.workspace < bytes) c.workspace = bytes; };
+    if (op == ConvOp::Wgrad) {
+        // slabs of any grid: pairs * groups <= 2 * 256 work-groups (the entry point checks its own grid's share)
+        c.workspace = (size_t)2 * 256 * (cin == 3 ? 1024 + 32 : (size_t)64 * 288 + 64) * sizeof(float);
+        c.clock = ConvClock::Keep;
+        const bool sparse = (mask & CONV_B3_WGRAD_SPARSE) != 0;
+        if (conv1 && (mask & CONV_B3_C1_WGRAD)) c.form = ConvForm::Conv1SplitBf16;
+        // split-bf16 weight gradient, (32 ci, 64 co) block pairs: dense or sparse on 64 x 64 maps (the flagship's second stage, one pair; the
+        // wide / deep variant's 64 -> 128 stage, four pairs), sparse only on the variant's 32 x 32 third stage (16 pairs; a stage = two pooled rows)
+        else if (b3_stage && (mask & CONV_B3_WGRAD) && (sparse || hw == 64)) {
+            // the sparse form has an 8-wave kernel (fastest alone: two waves of 256 registers per SIMD) and a 4-wave one that leaves ~200
+            // registers per lane slot to the fingerprint branch's kernels: the engine asks for that while an encoder chain runs beside
+            const int waves = kn.wgrad_sparse_waves ? kn.wgrad_sparse_waves : (((mask & CONV_B3_WGRAD_SPARSE4) || prefs.wgrad_beside_encoder) ? 4 : 8);
+            c.form = !sparse ? ConvForm::WgradDense : waves == 8 ? ConvForm::WgradSparse8 : ConvForm::WgradSparse4;
+        }
+        return c;
+    }
+    const bool fwd = op == ConvOp::Fwd;
+    c.workspace = (size_t)9 * (fwd && cin < 8 ? 4 : cin) * cout * sizeof(float);      // the f32 kernels' re-laid filters; every form's floor
+    if (b3_stage && (mask & (fwd ? CONV_B3_FWD : CONV_B3_DGRAD))) {
+        // 64 x 64 maps have a software-pipelined one-work-group-per-CU kernel: 3 % slower alone, but it leaves an encoder chain beside it
+        // three quarters of every SIMD (step 2.8 % faster), so the engine asks for it in training plans with an encoder
+        const int pipe = !fwd ? kn.c2_dgrad_pipe : kn.c2_pipe != INT_MIN ? kn.c2_pipe : prefs.conv2_fwd_pipe;
+        c.form = (hw == 64 && pipe && !kn.b3_probe) ? ConvForm::SplitBf16Pipe : ConvForm::SplitBf16;
+        c.per_cu = kn.b3_per_cu; c.probe = kn.b3_probe != 0;
+        c.clock = ConvClock::SplitBf16;
+        at_least(bbbp_b3_workspace_bytes(cin, cout));
+    } else if (conv2 && (mask & (fwd ? CONV_WINO_FWD : CONV_WINO_DGRAD))) {
+        c.form = ConvForm::Winograd;
+        c.clock = ConvClock::Winograd;
+        at_least((size_t)16 * 32 * 64 * sizeof(float));
+    } else if (fwd && conv1 && (mask & CONV_B3_C1_FWD) && !prefs.conv1_fwd_f32) {
+        // Faster alone than the f32 kernel (0.19 vs 0.26 ms at B = 512) but it holds 2 x 248 registers per lane slot on every SIMD, and a
+        // training step's forward is bound by the encoder's latency chain, which then finds no wave slots (measured: conv1 0.31 -> 0.20 ms
+        // in-step, encoder forward 1.21 -> 1.33, step 2.61 -> 2.70): the engine sets conv1_fwd_f32 there, or asks the pipelined form -- which
+        // keeps the matrix pipe busy with ONE wave per SIMD -- for one work-group per CU (half the register file and 100 KB of LDS stay free)
+        c.form = kn.c1_pipe ? ConvForm::Conv1SplitBf16Pipe : ConvForm::Conv1SplitBf16;
+        c.per_cu = prefs.conv1_fwd_per_cu > 0 ? prefs.conv1_fwd_per_cu : kn.c1_per_cu;
+        at_least(bbbp_b3_conv1_fwd_workspace_bytes());      // the kernel stamps no clock of its own: bbbp_conv_last_clock keeps reading the f32 pair
+    }
+    return c;
+}
+ConvChoice conv_choice(ConvOp op, int cin, int cout, int hw, const ConvPrefs& prefs) { return conv_choice(op, cin, cout, hw, g_winograd.get(), prefs, conv_knobs()); }
+
 }  // namespace
 
 extern "C" int bbbp_set_conv_winograd(int mask) {
-    BBBP_CHECK_ARG(mask >= 0 && mask <= 511, "set_conv_winograd: mask %d (bits 0/1 Winograd forward / data gradient, bits 2/3/4 split-bf16 forward / data gradient / weight gradient of conv2, bits 5/6 split-bf16 weight gradient / forward of conv1, bit 7 conv2's split-bf16 weight gradient on the structured-sparse MFMA, bit 8 its 4-wave form)", mask);
+    BBBP_CHECK_ARG(mask >= 0 && mask <= CONV_MASK_ALL, "set_conv_winograd: mask %d (bits 0/1 Winograd forward / data gradient, bits 2/3/4 split-bf16 forward / data gradient / weight gradient of conv2, bits 5/6 split-bf16 weight gradient / forward of conv1, bit 7 conv2's split-bf16 weight gradient on the structured-sparse MFMA, bit 8 its 4-wave form)", mask);
     g_winograd.set(mask);
     return BBBP_OK;
 }
 
-extern "C" int bbbp_get_conv_winograd(void) { return winograd_mask(); }
+extern "C" int bbbp_get_conv_winograd(void) { return g_winograd.get(); }
 extern "C" int bbbp_conv_winograd_phases(unsigned long long* phases4) {
     BBBP_CHECK_ARG(phases4, "conv_winograd_phases: null pointer");
     return bbbp_wino_last_phases(phases4);
 }
 
-// workspace: prepped weights (fwd / dgrad) or partial slabs (wgrad)
 extern "C" int bbbp_conv_last_clock(unsigned long long* shader_cycles, unsigned long long* ticks_100mhz) {
     BBBP_CHECK_ARG(shader_cycles && ticks_100mhz, "conv_last_clock: null pointer");
-    if (g_last_clock_wino == 2) return bbbp_b3_last_clock(shader_cycles, ticks_100mhz);
-    if (g_last_clock_wino) return bbbp_wino_last_clock(shader_cycles, ticks_100mhz);
+    if (g_last_clock == ConvClock::SplitBf16) return bbbp_b3_last_clock(shader_cycles, ticks_100mhz);
+    if (g_last_clock == ConvClock::Winograd) return bbbp_wino_last_clock(shader_cycles, ticks_100mhz);
     unsigned long long h[2] = {0, 0};
     BBBP_CHECK_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_conv_clock), sizeof(h)));
     *shader_cycles = h[0]; *ticks_100mhz = h[1];
     return BBBP_OK;
 }
 
+// workspace for any of the three ops on this stage, whatever form the mask, the caller or the knobs select
 extern "C" size_t bbbp_conv3x3_workspace_bytes(int B, int cin, int cout, int H, int W) {
-    (void)B; (void)H; (void)W;
-    size_t prep = (size_t)9 * (cin < 8 ? 4 : cin) * cout * sizeof(float);
-    size_t prep_d = (size_t)9 * cout * cin * sizeof(float);
-    // wgrad: (pairs * groups) slabs with pairs * groups <= 2 * 256 work-groups
-    size_t slab = (size_t)2 * 256 * ((cin == 3 ? 1024 + 32 : (size_t)64 * 288 + 64)) * sizeof(float);
-    size_t m = prep > prep_d ? prep : prep_d;
-    if (bbbp_b3_conv_supported(cin, cout, H) && bbbp_b3_workspace_bytes(cin, cout) > m) m = bbbp_b3_workspace_bytes(cin, cout);      // pre-split filters of the split-bf16 form
-    return align_up(m > slab ? m : slab, 256);
+    (void)B; (void)W;
+    auto need = [&](ConvOp op) { return conv_choice(op, cin, cout, H, ConvPrefs{}).workspace; };
+    return align_up(std::max({need(ConvOp::Fwd), need(ConvOp::Dgrad), need(ConvOp::Wgrad)}), 256);
 }
 
-// The conv2-family weight gradient has two structured-sparse forms (conv_b3.hip): 8 waves (fastest alone) and 4 waves (one wave per SIMD: the
-// form to run while ANOTHER branch's small kernels share the GPU).  bbbp_mixed_backward picks by itself; a caller that composes the model
-// op by op and overlaps its branches on two streams says so for the calling thread around its bbbp_conv3x3_relu_pool_bwd_weight call.
-// Returns the previous setting.
+// The calling thread's two preferences (include/bbbp_hip.h); each returns the previous setting.  BBBP_C2_PIPE=0 / 1 overrides every caller.
 extern "C" int bbbp_set_conv_wgrad_beside_encoder(int on) {
     const int prev = g_bbbp_conv_wgrad_beside_encoder;
     g_bbbp_conv_wgrad_beside_encoder = on ? 1 : 0;
     return prev;
 }
-
-// Forward of the 32 -> 64 / 64 -> 128 stages on 64 x 64 maps: 1 selects, for the calling thread, the software-pipelined kernel that runs ONE
-// work-group per CU (conv_b3.hip: conv_b3p_kernel) -- 3 % slower alone, but beside an encoder chain the step is 2.8 % faster
-// (bbbp_mixed_forward asks for it by itself for training plans with an encoder).  Same arithmetic in the same order: bit-identical outputs
-// and decisions.  Returns the previous setting.  BBBP_C2_PIPE=0 / 1 overrides every caller.
 extern "C" int bbbp_set_conv2_fwd_pipe(int on) {
     const int prev = g_bbbp_conv2_fwd_pipe;
     g_bbbp_conv2_fwd_pipe = on ? 1 : 0;
@@ -875,26 +927,15 @@ int conv3x3_relu_pool_fwd(hipStream_t st, const float* x, const float* w, const 
     BBBP_CHECK_ARG(supported(cin, cout, H, W), "conv fwd: unsupported shape cin=%d cout=%d H=%d W=%d", cin, cout, H, W);
     BBBP_CHECK_ARG(x && w && bias && y && workspace, "conv fwd: null pointer");      // mask may be null: forward-only call, no decisions kept
     if (B == 0) return BBBP_OK;
-    int cinp = cin < 8 ? 4 : cin;
-    size_t need = (size_t)9 * cinp * cout * sizeof(float);
-    BBBP_CHECK_ARG(workspace_bytes >= need, "conv fwd: workspace %zu < %zu", workspace_bytes, need);
+    const ConvChoice c = conv_choice(ConvOp::Fwd, cin, cout, H, prefs);
+    BBBP_CHECK_ARG(workspace_bytes >= c.workspace, "conv fwd: workspace %zu < %zu", workspace_bytes, c.workspace);
     float* wt = static_cast<float*>(workspace);
-    g_last_clock_wino = 0;
-    if (bbbp_b3_conv_supported(cin, cout, H) && H == W && (winograd_mask() & 4)) {
-        BBBP_CHECK_ARG(workspace_bytes >= bbbp_b3_workspace_bytes(cin, cout), "conv fwd: workspace too small");
-        g_last_clock_wino = 2;               // split-bf16 kernel: its own stamps (conv_b3.hip)
-        return bbbp_b3_conv_fwd(st, x, w, bias, y, mask, B, cin, cout, workspace, prefs.conv2_fwd_pipe);
-    }
-    if (cin == 32 && cout == 64 && (winograd_mask() & 1)) {
-        BBBP_CHECK_ARG(workspace_bytes >= (size_t)16 * 32 * 64 * sizeof(float), "conv fwd: workspace too small");
-        g_last_clock_wino = 1;
-        return bbbp_wino_conv2_fwd(st, x, w, bias, y, mask, B, wt);
-    }
-    if (cin == 3 && cout == 32 && W == 128 && (winograd_mask() & 64) && !prefs.conv1_fwd_f32) {          // split-bf16 forward of the first stage (conv_b3c1.hip)
-        BBBP_CHECK_ARG(workspace_bytes >= bbbp_b3_conv1_fwd_workspace_bytes(), "conv fwd: workspace too small");
-        return bbbp_b3_conv1_fwd(st, x, w, bias, y, mask, B, workspace, prefs.conv1_fwd_per_cu);
-    }
-    int total = 9 * cinp * cout;
+    g_last_clock = c.clock;
+    if (c.form == ConvForm::SplitBf16 || c.form == ConvForm::SplitBf16Pipe)
+        return bbbp_b3_conv_fwd(st, x, w, bias, y, mask, B, cin, cout, workspace, c.form, c.per_cu, c.probe);
+    if (c.form == ConvForm::Winograd) return bbbp_wino_conv2_fwd(st, x, w, bias, y, mask, B, wt);
+    if (c.form != ConvForm::F32Direct) return bbbp_b3_conv1_fwd(st, x, w, bias, y, mask, B, workspace, c.form, c.per_cu);
+    const int cinp = cin < 8 ? 4 : cin, total = 9 * cinp * cout;
     hipLaunchKernelGGL(conv_prep_weights_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, w, wt, cin, cout, cinp, MODE_FWD);
     BBBP_CHECK_LAUNCH();
     ConvParams p{x, nullptr, wt, bias, y, mask, B, H, cout};
@@ -914,20 +955,13 @@ extern "C" int bbbp_conv3x3_relu_pool_bwd_data(void* stream, const float* gy, co
     BBBP_CHECK_ARG(gy && mask && w && dx && workspace, "conv bwd_data: null pointer");
     if (B == 0) return BBBP_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    size_t need = (size_t)9 * cout * cin * sizeof(float);
-    BBBP_CHECK_ARG(workspace_bytes >= need, "conv bwd_data: workspace %zu < %zu", workspace_bytes, need);
+    const ConvChoice c = conv_choice(ConvOp::Dgrad, cin, cout, H, ConvPrefs{});
+    BBBP_CHECK_ARG(workspace_bytes >= c.workspace, "conv bwd_data: workspace %zu < %zu", workspace_bytes, c.workspace);
     float* wt = static_cast<float*>(workspace);
-    g_last_clock_wino = 0;
-    if (bbbp_b3_conv_supported(cin, cout, H) && H == W && (winograd_mask() & 8)) {
-        BBBP_CHECK_ARG(workspace_bytes >= bbbp_b3_workspace_bytes(cin, cout), "conv bwd_data: workspace too small");
-        g_last_clock_wino = 2;
-        return bbbp_b3_conv_dgrad(st, gy, mask, w, dx, B, cin, cout, workspace);
-    }
-    if (cin == 32 && cout == 64 && (winograd_mask() & 2)) {
-        BBBP_CHECK_ARG(workspace_bytes >= (size_t)16 * 32 * 64 * sizeof(float), "conv bwd_data: workspace too small");
-        g_last_clock_wino = 1;
-        return bbbp_wino_conv2_dgrad(st, gy, mask, w, dx, B, wt);
-    }
+    g_last_clock = c.clock;
+    if (c.form == ConvForm::SplitBf16 || c.form == ConvForm::SplitBf16Pipe)
+        return bbbp_b3_conv_dgrad(st, gy, mask, w, dx, B, cin, cout, workspace, c.form, c.per_cu, c.probe);
+    if (c.form == ConvForm::Winograd) return bbbp_wino_conv2_dgrad(st, gy, mask, w, dx, B, wt);
     int total = 9 * cout * cin;
     hipLaunchKernelGGL(conv_prep_weights_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, w, wt, cin, cout, 0, MODE_DGRAD);
     BBBP_CHECK_LAUNCH();
@@ -940,12 +974,7 @@ extern "C" int bbbp_conv3x3_relu_pool_bwd_data(void* stream, const float* gy, co
 
 template <int W, int CIN_TOTAL, int COUT_TOTAL>
 static int launch_wgrad32(WgradParams p, int grid, hipStream_t st) {
-    using C = WgCfg<64, W>;
-    int rc = set_lds(conv_wgrad32_kernel<64, W, CIN_TOTAL, COUT_TOTAL>, C::LDS_BYTES);
-    if (rc) return rc;
-    hipLaunchKernelGGL((conv_wgrad32_kernel<64, W, CIN_TOTAL, COUT_TOTAL>), dim3(grid), dim3(512), C::LDS_BYTES, st, p);
-    BBBP_CHECK_LAUNCH();
-    return BBBP_OK;
+    return launch_lds(conv_wgrad32_kernel<64, W, CIN_TOTAL, COUT_TOTAL>, grid, 512, WgCfg<64, W>::LDS_BYTES, st, p);
 }
 
 // dw[cout][cin][3][3], db[cout] from the layer input x, the pooled output gradient and the mask
@@ -966,9 +995,10 @@ int conv3x3_relu_pool_bwd_weight(hipStream_t st, const float* x, const float* gy
         BBBP_CHECK_HIP(hipMemsetAsync(db, 0, (size_t)cout * sizeof(float), st));
         return BBBP_OK;
     }
+    const ConvChoice c = conv_choice(ConvOp::Wgrad, cin, cout, H, prefs);
     int nstrips = B * (H / 2);
     const bool part = g_bbbp_reserved_cus > 0;
-    const int cus = bbbp_num_cus() - (part ? g_bbbp_reserved_cus : 0) > 0 ? bbbp_num_cus() - (part ? g_bbbp_reserved_cus : 0) : 1;
+    const int ncu = bbbp_num_cus(), cus = ncu - (part ? g_bbbp_reserved_cus : 0) > 0 ? ncu - (part ? g_bbbp_reserved_cus : 0) : 1;
     float* slab = static_cast<float*>(workspace);
     WgradParams p{x, gy, mask, slab, nullptr, B, H, cin, cout, 1};
     if (cin == 3) {
@@ -976,42 +1006,25 @@ int conv3x3_relu_pool_bwd_weight(hipStream_t st, const float* x, const float* gy
         const int ncob = cout / 32;
         size_t lds3 = C::LDS_BYTES;
         if (part) lds3 = BBBP_CONV_MIN_LDS;          // one per CU on the unreserved CUs
-        int groups = (part ? cus : bbbp_num_cus() * 2) / ncob;
-        if (groups > nstrips) groups = nstrips;
-        if (groups < 1) groups = 1;
+        const int groups = clampi((part ? cus : ncu * 2) / ncob, 1, nstrips);
         const int grid = groups * ncob;
         BBBP_CHECK_ARG(workspace_bytes >= (size_t)grid * (1024 + 32) * sizeof(float), "conv bwd_weight: workspace too small");
         p.groups = groups;
         p.bslab = slab + (size_t)grid * 1024;
-        if (cout == 32 && (winograd_mask() & 32)) {
-            int rc = bbbp_b3_conv1_wgrad(st, x, gy, mask, slab, p.bslab, B, grid);
-            if (rc) return rc;
-        } else {
-        int rc = set_lds(conv_wgrad3_kernel<128>, lds3);
+        const int rc = c.form == ConvForm::Conv1SplitBf16 ? bbbp_b3_conv1_wgrad(st, x, gy, mask, slab, p.bslab, B, grid)
+                                                          : launch_lds(conv_wgrad3_kernel<128>, grid, 512, lds3, st, p);
         if (rc) return rc;
-        hipLaunchKernelGGL((conv_wgrad3_kernel<128>), dim3(grid), dim3(512), lds3, st, p);
-        BBBP_CHECK_LAUNCH();
-        }
         hipLaunchKernelGGL(conv_wgrad3_reduce_kernel, dim3(33, ncob), dim3(1024), 0, st, slab, p.bslab, dw, db, groups);
         BBBP_CHECK_LAUNCH();
     } else {
         const int pairs = (cin / 32) * (cout / 64);
-        int groups = cus / pairs;
-        if (groups > nstrips) groups = nstrips;
-        if (groups < 1) groups = 1;
+        const int groups = clampi(cus / pairs, 1, nstrips);
         const int grid = groups * pairs;
         BBBP_CHECK_ARG(workspace_bytes >= (size_t)grid * (64 * 288 + 64) * sizeof(float), "conv bwd_weight: workspace too small");
         p.groups = groups;
         p.bslab = slab + (size_t)grid * 64 * 288;
         int rc;
-        // split-bf16 weight gradient (dense or on the structured-sparse MFMA): 64 x 64 maps, (32 ci, 64 co) block pairs -- the flagship's
-        // second stage (one pair) and, round 4, the wide / deep variant's 64 -> 128 stage (four pairs)
-        if (W == 64 && H == 64 && ((cin == 32 && cout == 64) || (cin == 64 && cout == 128)) && (winograd_mask() & 16))
-            rc = bbbp_b3_conv2_wgrad(st, x, gy, mask, slab, p.bslab, B, grid, (winograd_mask() & 128) ? ((winograd_mask() & 256) ? 2 : 1) : 0,
-                                     prefs.wgrad_beside_encoder, cin, cout, groups);
-        else if (W == 32 && H == 32 && cin == 128 && cout == 256 && (winograd_mask() & 16) && (winograd_mask() & 128))
-            // the variant's third stage on the structured-sparse form (16 block pairs; a stage = two pooled rows)
-            rc = bbbp_b3_conv2_wgrad(st, x, gy, mask, slab, p.bslab, B, grid, (winograd_mask() & 256) ? 2 : 1, prefs.wgrad_beside_encoder, cin, cout, groups, 32);
+        if (c.form != ConvForm::F32Direct) rc = bbbp_b3_conv2_wgrad(st, x, gy, mask, slab, p.bslab, B, grid, c.form, cin, cout, groups, W);
         else rc = cin == 32 ? launch_wgrad32<64, 32, 64>(p, grid, st)
                : cin == 64 ? launch_wgrad32<64, 64, 128>(p, grid, st) : launch_wgrad32<32, 128, 256>(p, grid, st);
         if (rc) return rc;

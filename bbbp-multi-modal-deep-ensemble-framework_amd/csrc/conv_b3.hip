@@ -18,7 +18,6 @@
 // filter taps and swaps the channel roles, the epilogue stores full-resolution rows.
 #include "common.h"
 #include "bbbp_hip.h"
-#include <limits.h>
 
 namespace {
 
@@ -1226,43 +1225,27 @@ __global__ __launch_bounds__(256) void conv_b3_wgrad3_kernel(B3Wgrad3Params p) {
 }
 
 template <int MODE, class G>
-int launch_b3(const B3Params& p, hipStream_t st, int fwd_pipe = 0) {
-    static const int probe = bbbp_env_int("BBBP_B3_PROBE", 0);
+int launch_b3(const B3Params& p, hipStream_t st, ConvForm form, int per_cu, bool probe) {
     constexpr bool flagship = G::CIN == 32 && G::COUT == 64 && G::IMGS == 64;
+    constexpr int IMGL = G::IMGS, RL = 256 / IMGL, NMB = (MODE == B3_FWD ? G::COUT : G::CIN) / 32;
+    constexpr size_t lds = (size_t)(3 * (RL + 2) * (IMGL + 2) * CH + WSTAGE) * 2;
+    const int nwork = p.B * (IMGL / RL) * NMB;
     if constexpr (G::IMGS == 64) {
-        static const int pipe_env = bbbp_env_int("BBBP_C2_PIPE", INT_MIN);       // set in the environment (any integer): wins over the caller's choice
-        static const int dpipe_env = bbbp_env_int("BBBP_C2_DGRAD_PIPE", 0);
-        const int pipe = MODE == B3_FWD ? (pipe_env != INT_MIN ? pipe_env : fwd_pipe) : dpipe_env;
-        if (pipe && !probe) {
+        if (form == ConvForm::SplitBf16Pipe) {
             auto pk = MODE == B3_FWD ? (p.ymask ? conv_b3p_kernel<MODE, G, true> : conv_b3p_kernel<MODE, G, false>) : conv_b3p_kernel<MODE, G, false>;
-            constexpr size_t plds = (size_t)2 * (3 * (256 / G::IMGS + 2) * (G::IMGS + 2) * CH + WSTAGE) * 2;
-            { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(pk), plds); if (rc_) return rc_; }
-            constexpr int NMBP = (MODE == B3_FWD ? G::COUT : G::CIN) / 32;
-            const int nworkp = p.B * (G::IMGS / (256 / G::IMGS)) * NMBP;
-            int gridp = bbbp_num_cus();
-            if (gridp >= 8 * NMBP) gridp -= gridp % (8 * NMBP);
-            if (gridp > nworkp) gridp = nworkp - nworkp % NMBP;
-            if (gridp < NMBP) gridp = NMBP;
-            hipLaunchKernelGGL(pk, dim3(gridp), dim3(256), plds, st, p);
-            BBBP_CHECK_LAUNCH();
-            return BBBP_OK;
+            return launch_lds(pk, persistent_grid(bbbp_num_cus(), NMB, nwork), 256, 2 * lds, st, p);
         }
     }
     auto kernel = conv_b3_kernel<MODE, G>;
     if constexpr (flagship) { if (probe) kernel = conv_b3_probe_kernel<MODE>; }
-    constexpr int IMGL = G::IMGS, RL = 256 / IMGL;
-    constexpr size_t lds = (size_t)(3 * (RL + 2) * (IMGL + 2) * CH + WSTAGE) * 2;
-    { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(kernel), lds); if (rc_) return rc_; }
-    constexpr int NMB = (MODE == B3_FWD ? G::COUT : G::CIN) / 32;
-    const int nwork = p.B * (IMGL / RL) * NMB;
-    static const int per_cu = clampi(bbbp_env_int("BBBP_B3_PER_CU", 2), 1, 2);
-    int grid = bbbp_num_cus() * per_cu;
-    if (grid >= 8 * NMB) grid -= grid % (8 * NMB);
-    if (grid > nwork) grid = nwork - nwork % NMB;
-    if (grid < NMB) grid = NMB;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, st, p);
-    BBBP_CHECK_LAUNCH();
-    return BBBP_OK;
+    return launch_lds(kernel, persistent_grid(bbbp_num_cus() * per_cu, NMB, nwork), 256, lds, st, p);
+}
+
+template <int MODE>
+int launch_b3_stage(const B3Params& p, int cin, hipStream_t st, ConvForm form, int per_cu, bool probe) {
+    if (cin == 32) return launch_b3<MODE, GeomFlagship>(p, st, form, per_cu, probe);
+    if (cin == 64) return launch_b3<MODE, B3Geom<64, 128, 64>>(p, st, form, per_cu, probe);
+    return launch_b3<MODE, B3Geom<128, 256, 32>>(p, st, form, per_cu, probe);
 }
 
 }  // namespace
@@ -1272,9 +1255,10 @@ int launch_b3(const B3Params& p, hipStream_t st, int fwd_pipe = 0) {
 bool bbbp_b3_conv_supported(int cin, int cout, int hw) {
     return (cin == 32 && cout == 64 && hw == 64) || (cin == 64 && cout == 128 && hw == 64) || (cin == 128 && cout == 256 && hw == 32);
 }
-size_t bbbp_b3_workspace_bytes(int cin, int cout) { return (size_t)(cin / 16) * (cout / 32) * WSTAGE * 2 > (size_t)(cout / 16) * (cin / 32) * WSTAGE * 2
-                                                             ? (size_t)(cin / 16) * (cout / 32) * WSTAGE * 2 : (size_t)(cout / 16) * (cin / 32) * WSTAGE * 2; }
-size_t bbbp_b3_workspace_bytes() { return bbbp_b3_workspace_bytes(32, 64); }
+size_t bbbp_b3_workspace_bytes(int cin, int cout) {
+    const size_t fwd = (size_t)(cin / 16) * (cout / 32) * WSTAGE * 2, dgrad = (size_t)(cout / 16) * (cin / 32) * WSTAGE * 2;
+    return fwd > dgrad ? fwd : dgrad;
+}
 
 // Wave priority of the BACKWARD conv kernels (BBBP_CONV_BWD_PRIO, default 0).  The encoder chain's small kernels raise themselves to 3 so that
 // they win issue arbitration against the older conv waves; since round 4 the data-gradient kernel leaves the chain a wave slot per SIMD
@@ -1285,22 +1269,20 @@ static int conv_bwd_prio() {
     return v;
 }
 
-int bbbp_b3_conv_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int cin, int cout, void* workspace, int pipe) {
+int bbbp_b3_conv_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int cin, int cout, void* workspace,
+                     ConvForm form, int per_cu, bool probe) {
     hipLaunchKernelGGL(b3_prep_kernel, dim3(cin * cout >= 64 * 128 ? 288 : 72), dim3(256), 0, st, w, static_cast<uint16_t*>(workspace), B3_FWD, cin, cout);
     BBBP_CHECK_LAUNCH();
     B3Params p{x, nullptr, static_cast<const uint16_t*>(workspace), bias, y, mask, B, 0};
-    if (cin == 32) return launch_b3<B3_FWD, GeomFlagship>(p, st, pipe);
-    if (cin == 64) return launch_b3<B3_FWD, B3Geom<64, 128, 64>>(p, st, pipe);
-    return launch_b3<B3_FWD, B3Geom<128, 256, 32>>(p, st, pipe);
+    return launch_b3_stage<B3_FWD>(p, cin, st, form, per_cu, probe);
 }
 
-int bbbp_b3_conv_dgrad(hipStream_t st, const float* gy, const uint8_t* gmask, const float* w, float* dx, int B, int cin, int cout, void* workspace) {
+int bbbp_b3_conv_dgrad(hipStream_t st, const float* gy, const uint8_t* gmask, const float* w, float* dx, int B, int cin, int cout, void* workspace,
+                       ConvForm form, int per_cu, bool probe) {
     hipLaunchKernelGGL(b3_prep_kernel, dim3(cin * cout >= 64 * 128 ? 288 : 72), dim3(256), 0, st, w, static_cast<uint16_t*>(workspace), B3_DGRAD, cin, cout);
     BBBP_CHECK_LAUNCH();
     B3Params p{gy, gmask, static_cast<const uint16_t*>(workspace), nullptr, dx, nullptr, B, conv_bwd_prio()};
-    if (cin == 32) return launch_b3<B3_DGRAD, GeomFlagship>(p, st);
-    if (cin == 64) return launch_b3<B3_DGRAD, B3Geom<64, 128, 64>>(p, st);
-    return launch_b3<B3_DGRAD, B3Geom<128, 256, 32>>(p, st);
+    return launch_b3_stage<B3_DGRAD>(p, cin, st, form, per_cu, probe);
 }
 
 extern "C" int bbbp_conv_b3_phases(unsigned long long* phases4) {
@@ -1310,49 +1292,22 @@ extern "C" int bbbp_conv_b3_phases(unsigned long long* phases4) {
 }
 
 // grid work-groups, each writes slab[g][64][288] and bslab[g][64] (conv.hip: conv_wgrad32_reduce_kernel finishes)
-int bbbp_b3_conv2_wgrad(hipStream_t st, const float* x, const float* gy, const uint8_t* mask, float* slab, float* bslab, int B, int grid, int form,
-                        int beside_encoder, int cin_total, int cout_total, int groups, int map) {
-    B3WgradParams p{x, gy, mask, slab, bslab, B, conv_bwd_prio(), cin_total, cout_total, groups > 0 ? groups : grid};
-    BBBP_CHECK_ARG(map == 64 || (map == 32 && form != 0), "b3 weight gradient: 64 x 64 maps (any form) or 32 x 32 maps (structured-sparse forms), got %d / form %d", map, form);
-    const bool sparse = form != 0;
-    static const int waves_env = bbbp_env_int("BBBP_C2_WGRAD_SPARSE_WAVES", 0);
-    const int waves = waves_env ? waves_env : ((form == 2 || beside_encoder) ? 4 : 8);
-    if (map == 32) {
-        if (waves == 8) {
-            { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(conv_b3_wgrad_sp_kernel<8, 32>), WGS_LDS_BYTES); if (rc_) return rc_; }
-            hipLaunchKernelGGL((conv_b3_wgrad_sp_kernel<8, 32>), dim3(grid), dim3(512), WGS_LDS_BYTES, st, p);
-        } else {
-            { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(conv_b3_wgrad_sp_kernel<4, 32>), WGS_LDS_BYTES); if (rc_) return rc_; }
-            hipLaunchKernelGGL((conv_b3_wgrad_sp_kernel<4, 32>), dim3(grid), dim3(256), WGS_LDS_BYTES, st, p);
-        }
-        BBBP_CHECK_LAUNCH();
-        return BBBP_OK;
-    }
-    if (sparse && waves == 8) {
-        { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(conv_b3_wgrad_sp_kernel<8>), WGS_LDS_BYTES); if (rc_) return rc_; }
-        hipLaunchKernelGGL(conv_b3_wgrad_sp_kernel<8>, dim3(grid), dim3(512), WGS_LDS_BYTES, st, p);
-        BBBP_CHECK_LAUNCH();
-        return BBBP_OK;
-    }
-    if (sparse) {
-        { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(conv_b3_wgrad_sp_kernel<4>), WGS_LDS_BYTES); if (rc_) return rc_; }
-        hipLaunchKernelGGL(conv_b3_wgrad_sp_kernel<4>, dim3(grid), dim3(256), WGS_LDS_BYTES, st, p);
-        BBBP_CHECK_LAUNCH();
-        return BBBP_OK;
-    }
-    { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(conv_b3_wgrad_kernel), (size_t)WG_LDS_BYTES); if (rc_) return rc_; }
-    hipLaunchKernelGGL(conv_b3_wgrad_kernel, dim3(grid), dim3(256), WG_LDS_BYTES, st, p);
-    BBBP_CHECK_LAUNCH();
-    return BBBP_OK;
+int bbbp_b3_conv2_wgrad(hipStream_t st, const float* x, const float* gy, const uint8_t* mask, float* slab, float* bslab, int B, int grid, ConvForm form,
+                        int cin_total, int cout_total, int groups, int map) {
+    B3WgradParams p{x, gy, mask, slab, bslab, B, conv_bwd_prio(), cin_total, cout_total, groups};
+    const bool dense = form == ConvForm::WgradDense, w8 = form == ConvForm::WgradSparse8;
+    BBBP_CHECK_ARG(dense || w8 || form == ConvForm::WgradSparse4, "b3 weight gradient: not a weight-gradient form (%d)", (int)form);
+    BBBP_CHECK_ARG(map == 64 || (map == 32 && !dense), "b3 weight gradient: 64 x 64 maps (any form) or 32 x 32 maps (structured-sparse forms), got %d / form %d", map, (int)form);
+    if (dense) return launch_lds(conv_b3_wgrad_kernel, grid, 256, (size_t)WG_LDS_BYTES, st, p);
+    if (map == 32) return w8 ? launch_lds(conv_b3_wgrad_sp_kernel<8, 32>, grid, 512, WGS_LDS_BYTES, st, p)
+                             : launch_lds(conv_b3_wgrad_sp_kernel<4, 32>, grid, 256, WGS_LDS_BYTES, st, p);
+    return w8 ? launch_lds(conv_b3_wgrad_sp_kernel<8>, grid, 512, WGS_LDS_BYTES, st, p) : launch_lds(conv_b3_wgrad_sp_kernel<4>, grid, 256, WGS_LDS_BYTES, st, p);
 }
 
 // 3 -> 32 @ 128x128 weight gradient: grid work-groups, each writes slab[g][32][32] and bslab[g][32] (conv.hip: conv_wgrad3_reduce_kernel)
 int bbbp_b3_conv1_wgrad(hipStream_t st, const float* x, const float* gy, const uint8_t* mask, float* slab, float* bslab, int B, int grid) {
-    { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(conv_b3_wgrad3_kernel), (size_t)WG3_LDS_BYTES); if (rc_) return rc_; }
     B3Wgrad3Params p{x, gy, mask, slab, bslab, B, conv_bwd_prio()};
-    hipLaunchKernelGGL(conv_b3_wgrad3_kernel, dim3(grid), dim3(256), WG3_LDS_BYTES, st, p);
-    BBBP_CHECK_LAUNCH();
-    return BBBP_OK;
+    return launch_lds(conv_b3_wgrad3_kernel, grid, 256, (size_t)WG3_LDS_BYTES, st, p);
 }
 
 int bbbp_b3_last_clock(unsigned long long* shader_cycles, unsigned long long* ticks_100mhz) {

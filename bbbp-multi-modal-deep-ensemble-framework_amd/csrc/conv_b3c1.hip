@@ -447,20 +447,15 @@ __global__ __launch_bounds__(256, 2) void conv1_b3p_fwd_kernel(C1Params p) {
 // workspace: WFRAG_WORDS uint32 of pre-split filter fragments (9 KB)
 size_t bbbp_b3_conv1_fwd_workspace_bytes() { return (size_t)WFRAG_WORDS * sizeof(uint32_t); }
 
-int bbbp_b3_conv1_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, void* workspace, int want_per_cu) {
+int bbbp_b3_conv1_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, void* workspace,
+                      ConvForm form, int per_cu) {
     uint32_t* wf = static_cast<uint32_t*>(workspace);
-    static const int pipe = bbbp_env_int("BBBP_C1_PIPE", 1);     // round 4: the software-pipelined form (0: round 3's phase-by-phase kernel)
+    const bool pipe = form == ConvForm::Conv1SplitBf16Pipe;
     hipLaunchKernelGGL(c1_prep_kernel, dim3(3), dim3(256), 0, st, w, wf, pipe ? bias : nullptr);
     BBBP_CHECK_LAUNCH();
     static const int exp_bits = bbbp_env_int("BBBP_C1_EXP", 0);
     C1Params p{x, wf, bias, y, mask, B, exp_bits};
-    static const int per_cu_env = clampi(bbbp_env_int("BBBP_C1_PER_CU", 2), 1, 4);
-    const int per_cu = want_per_cu > 0 ? want_per_cu : per_cu_env;
-    const int nstrips = B * (W1 / R1);
-    int grid = bbbp_num_cus() * per_cu;
-    if (grid >= 8) grid -= grid % 8;
-    if (grid > nstrips) grid = nstrips;
-    if (grid < 1) grid = 1;
+    const int grid = persistent_grid(bbbp_num_cus() * per_cu, 1, B * (W1 / R1));
     if (pipe) {
         if (mask) hipLaunchKernelGGL(conv1_b3p_fwd_kernel<true>, dim3(grid), dim3(256), LDS1_BYTES, st, p);
         else hipLaunchKernelGGL(conv1_b3p_fwd_kernel<false>, dim3(grid), dim3(256), LDS1_BYTES, st, p);

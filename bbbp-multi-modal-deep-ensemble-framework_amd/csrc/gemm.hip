@@ -21,6 +21,7 @@
 #include "common.h"
 #include "bbbp_hip.h"
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #define TRY_RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
@@ -1307,120 +1308,59 @@ __global__ __launch_bounds__(256) void gemm_direct_pair_kernel(DirectParams p0, 
     }
 }
 
-struct DirectPlan { bool use; int t, wsm, wsn, ks; };
 
-// The direct path serves launches that cannot fill the chip with 64x64 tiles anyway; big GEMMs keep the LDS tiling.
-DirectPlan direct_plan(int M, int N, int K, int batch) {
-    static const int enabled = bbbp_env_int("BBBP_GEMM_DIRECT", 1);
-    DirectPlan d{false, 1, 1, 1, 1};
-    const double flops = 2.0 * M * N * (double)K * batch;
-    if (!enabled || flops > 1.2e9 || K > 8192) return d;
-    d.use = true;
-    const int nch = cdiv(K, 16);
-    // work-groups stay at 4 waves (one per SIMD, <= 64 VGPRs for the 16x16 variant): a 16-wave group needs 256 free
-    // VGPRs on every SIMD of one CU and cannot start while the persistent conv work-groups of the other stream hold
-    // theirs (measured: the conv beside it slowed from 0.72 to 1.25 ms and the encoder gained nothing).  Whole training
+// ---- host half: knobs -> plan -> launch.  Which kernel a product runs, on what grid and with how much workspace is decided in gemm_plan
+// and nowhere else; the launchers below only instantiate what the plan names. ----
+
+// Every BBBP_GEMM_* variable, read once per process (gemm_knobs); the two with an exported setter are sampled from their Knob per plan.
+struct GemmKnobs {
+    // BBBP_GEMM_DIRECT: the small-product path.  A/B values: 0 off, 3 no K slices, 5 no 32x32 wave tiles
+    int direct;
+    // BBBP_GEMM_DIRECT_KS: cap on the K slices of a direct work-group.  Work-groups stay at 4 waves (one per SIMD, <= 64 VGPRs for the 16x16
+    // variant): a 16-wave group needs 256 free VGPRs on every SIMD of one CU and cannot start while the persistent conv work-groups of the
+    // other stream hold theirs (measured: the conv beside it slowed from 0.72 to 1.25 ms and the encoder gained nothing).  Whole training
     // step, B = 512 (tools/exp_step.py): K slices capped at 1 / 2 / 4 -> 3.95 / 3.75 / 3.78 ms; LDS-tiled path 4.25 ms.
-    static const int max_ks = bbbp_env_int("BBBP_GEMM_DIRECT_KS", 2);
-    d.ks = nch <= 12 ? 1 : (cdiv(nch, 8) < max_ks ? cdiv(nch, 8) : max_ks);
-    if (d.ks == 3) d.ks = 4;
-    const long wt = (long)cdiv(M, 16) * cdiv(N, 16) * batch;
-    // 32x32 wave tiles (t = 2) need ~100 VGPRs: beside conv_wgrad32 (2 x 224 VGPRs per SIMD) such a wave cannot be
-    // placed until the conv kernel ends -- rocprofv3 showed the dhff GEMM of every layer waiting up to 0.65 ms.  The
-    // 16x16 variant fits the 64 VGPRs that are left, so it serves everything up to 4096 wave tiles (all of B = 512,
-    // F = 167: whole step 3.81 -> 3.75 ms); larger outputs (B = 4096 screening) take 32x32 tiles for the operand reuse.
-    static const int max_t = bbbp_env_int("BBBP_GEMM_DIRECT_T", 2);
-    d.t = (wt * d.ks <= 4096 || max_t < 2) ? 1 : 2;
-    // many heads with a tiny head dimension (F = 2048: 256 heads of 8) are hundreds of thousands of nearly empty wave
-    // tiles: those stay on the LDS-tiled kernel
-    const long waves = (long)cdiv(M, 16 * d.t) * cdiv(N, 16 * d.t) * batch * d.ks;
-    const int mind = M < N ? (M < K ? M : K) : (N < K ? N : K);
-    if (waves > 16384 || (batch >= 8 && mind < 16)) d.use = false;
-    if (d.ks >= 4) { d.wsm = 1; d.wsn = 1; }
-    else if (d.ks >= 2) { d.wsm = 2; d.wsn = 1; }
-    else { d.wsm = 2; d.wsn = 2; }
-    if ((enabled & 2) && d.ks > 1) d.use = false;      // A/B knobs: BBBP_GEMM_DIRECT=0 off, 3 no K slices, 5 no 32x32 wave tiles
-    if ((enabled & 4) && d.t > 1) d.use = false;
-    return d;
-}
-
-inline size_t direct_lds(const DirectParams& p, int t) {
-    const int waves = p.wsm * p.wsn * p.ks;
-    size_t lds = p.ks > 1 ? (size_t)waves * t * t * 4 * 64 * sizeof(float) : 0;
-    return lds < g_bbbp_small_lds_pad ? g_bbbp_small_lds_pad : lds;
-}
-
-template <int LAYOUT, int T>
-void launch_direct_one(const DirectParams& p, hipStream_t st) {
-    const int waves = p.wsm * p.wsn * p.ks;
-    hipLaunchKernelGGL((gemm_direct_kernel<LAYOUT, T, T>), dim3(p.gx, p.gy, p.batch), dim3(64 * waves), direct_lds(p, T), st, p);
-}
-
-void launch_direct(const DirectParams& p, int layout, int t, hipStream_t st) {
-    if (t == 1) {
-        if (layout == 0) launch_direct_one<0, 1>(p, st);
-        else if (layout == 1) launch_direct_one<1, 1>(p, st);
-        else launch_direct_one<2, 1>(p, st);
-    } else {
-        if (layout == 0) launch_direct_one<0, 2>(p, st);
-        else if (layout == 1) launch_direct_one<1, 2>(p, st);
-        else launch_direct_one<2, 2>(p, st);
-    }
-}
-
-template <int L0, int T0, int L1, int T1>
-void launch_pair_one(const DirectParams& a, const DirectParams& b, hipStream_t st) {
-    const size_t la = direct_lds(a, T0), lb = direct_lds(b, T1);
-    dim3 grid(a.gx > b.gx ? a.gx : b.gx, a.gy > b.gy ? a.gy : b.gy, a.batch + b.batch);
-    hipLaunchKernelGGL((gemm_direct_pair_kernel<L0, T0, L1, T1>), grid, dim3(256), la > lb ? la : lb, st, a, b);
-}
-
-// the pairs the engine issues; anything else runs as two launches
-bool launch_pair(const DirectParams& a, int la, int ta, const DirectParams& b, int lb, int tb, hipStream_t st) {
-    if (a.wsm * a.wsn * a.ks != 4 || b.wsm * b.wsn * b.ks != 4) return false;
-    if ((long)a.batch + b.batch > 65535) return false;
-    if (ta == 1 && tb == 1) {
-        if (la == 2 && lb == 0) { launch_pair_one<2, 1, 0, 1>(a, b, st); return true; }      // dV = Pd^T dO | dPd = dO V^T
-        if (la == 1 && lb == 2) { launch_pair_one<1, 1, 2, 1>(a, b, st); return true; }      // dQ = dS K   | dK = dS^T Q
-        if (la == 2 && lb == 2) { launch_pair_one<2, 1, 2, 1>(a, b, st); return true; }      // [dWq; dWk] = dQK^T x | dW' = dVW^T x (fold.hip)
-    }
-    return false;
-}
-
-template <int BM, int BN, int LAYOUT, bool VEC, int BKT = 0>
-void launch_one(const GemmParams& p, dim3 grid, hipStream_t st) {
-    constexpr int BK = BKT ? BKT : bk_of(BM);
-    constexpr size_t lds = (size_t)2 * BK * ((BM + (LAYOUT == 2 ? 4 : 1)) + (BN + (LAYOUT != 0 ? 4 : 1))) * sizeof(float);
-    // a refused opt-in makes the launch itself fail, which BBBP_CHECK_LAUNCH reports
-    if (lds > 64 * 1024) (void)bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_f32_kernel<BM, BN, LAYOUT, VEC, BKT>), lds);
-    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, LAYOUT, VEC, BKT>), grid, dim3(256), lds > g_bbbp_small_lds_pad ? lds : g_bbbp_small_lds_pad, st, p);
-}
-
-template <int BM, int BN>
-void launch_tile(const GemmParams& p, int layout, dim3 grid, hipStream_t st) {
-    const bool vec = p.vecA && p.vecB;
-    if (BM == 128 && p.short_k && vec) {           // short K over a large output: four work-groups per CU (see the kernel)
-        if (layout == 0) launch_one<128, 128, 0, true, 16>(p, grid, st);
-        else if (layout == 1) launch_one<128, 128, 1, true, 16>(p, grid, st);
-        else launch_one<128, 128, 2, true, 16>(p, grid, st);
-        return;
-    }
-    if (layout == 0) { if (vec) launch_one<BM, BN, 0, true>(p, grid, st); else launch_one<BM, BN, 0, false>(p, grid, st); }
-    else if (layout == 1) { if (vec) launch_one<BM, BN, 1, true>(p, grid, st); else launch_one<BM, BN, 1, false>(p, grid, st); }
-    else { if (vec) launch_one<BM, BN, 2, true>(p, grid, st); else launch_one<BM, BN, 2, false>(p, grid, st); }
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
+    int direct_ks;
+    // BBBP_GEMM_DIRECT_T: largest wave tile (in 16s) of the direct path.  32x32 wave tiles (t = 2) need ~100 VGPRs: beside conv_wgrad32
+    // (2 x 224 VGPRs per SIMD) such a wave cannot be placed until the conv kernel ends -- rocprofv3 showed the dhff GEMM of every layer
+    // waiting up to 0.65 ms.  The 16x16 variant fits the 64 VGPRs that are left, so it serves everything up to 4096 wave tiles (all of
+    // B = 512, F = 167: whole step 3.81 -> 3.75 ms); larger outputs (B = 4096 screening) take 32x32 tiles for the operand reuse.
+    int direct_t;
+    // BBBP_GEMM_B3_SMALL: the 64 x 64 split-bf16 tile where the 128-tile grid would leave CUs idle (or split K) while 64-tiles fill the
+    // chip and K is deep enough to amortise the tile's prologue; 0 keeps the 128-tile plans
+    int b3_small;
+    // BBBP_GEMM_TALL_B3: a deep K over many rows and one or two column tiles (linear2 of a 4096-row screening batch: N = 167, K = 2048): the
+    // 64 x 64 f32 plan runs it at 49 TFLOP/s (66 us); on the bf16 pipe the padded columns (167 -> 256) cost less than the pipe gains.
+    // 0 keeps the old plan
+    int tall_b3;
+    int split_x10;       // BBBP_GEMM_SPLIT_X10: target work-groups per CU x 10 when K is split (default 20 = two per CU)
+    // BBBP_GEMM_SPLIT_FULL: also split when the tiles already cover the chip once but not twice (one work-group per CU leaves every barrier
+    // stall of its single wave per SIMD exposed)
+    int split_full;
+    int short_k, short_tiles;      // BBBP_GEMM_SHORT_K / _SHORT_TILES: the 16-deep 128 x 128 form serves K <= short_k over >= short_tiles tiles per CU
+    int reduce_vec4;     // BBBP_GEMM_REDUCE_VEC4: the float4 form of the split-K reduce kernel where alignment allows
+    int b3_probe;        // BBBP_GEMM_B3_PROBE: the phase-stamping build of the split-bf16 kernel (bbbp_gemm_split_bf16_phases)
+    int split_bf16;      // BBBP_GEMM_SPLIT_BF16 / bbbp_set_gemm_split_bf16
+    int fold_reduce;     // BBBP_GEMM_FOLD_REDUCE / bbbp_set_gemm_fold_reduce: default off, measured slower, see DESIGN.md section 3
+};
 Knob g_gemm_b3{"BBBP_GEMM_SPLIT_BF16", 1, knob_bool};
-int gemm_b3_on() { return g_gemm_b3.get(); }
-// Arrival counters of the split-bf16 kernel's in-kernel split-K reduction: one zeroed region per (device, stream) -- launches on one
-// stream run one after another and every launch leaves its counters at zero, launches on different streams never share a region.
-constexpr int ARRIVAL_REGION = 8192, ARRIVAL_REGIONS = 32;
-Knob g_gemm_fold_reduce{"BBBP_GEMM_FOLD_REDUCE", 0, knob_bool};      // default off: measured slower, see DESIGN.md section 3
-int gemm_fold_reduce_on() { return g_gemm_fold_reduce.get(); }
-unsigned* arrival_counters(hipStream_t st, long tiles) {
-    if (!gemm_fold_reduce_on() || tiles > ARRIVAL_REGION) return nullptr;
+Knob g_gemm_fold_reduce{"BBBP_GEMM_FOLD_REDUCE", 0, knob_bool};
+GemmKnobs gemm_knobs() {
+    static const GemmKnobs env{bbbp_env_int("BBBP_GEMM_DIRECT", 1), bbbp_env_int("BBBP_GEMM_DIRECT_KS", 2), bbbp_env_int("BBBP_GEMM_DIRECT_T", 2),
+                               bbbp_env_int("BBBP_GEMM_B3_SMALL", 1), bbbp_env_int("BBBP_GEMM_TALL_B3", 1), bbbp_env_int("BBBP_GEMM_SPLIT_X10", 20),
+                               bbbp_env_int("BBBP_GEMM_SPLIT_FULL", 0), bbbp_env_int("BBBP_GEMM_SHORT_K", 256), bbbp_env_int("BBBP_GEMM_SHORT_TILES", 4),
+                               bbbp_env_int("BBBP_GEMM_REDUCE_VEC4", 1), bbbp_env_int("BBBP_GEMM_B3_PROBE", 0), 0, 0};
+    GemmKnobs k = env;
+    k.split_bf16 = g_gemm_b3.get();
+    k.fold_reduce = g_gemm_fold_reduce.get();
+    return k;
+}
+
+// ---- arrival counters of the split-bf16 kernel's opt-in in-kernel split-K reduction (GemmPlan::in_kernel_reduce): one zeroed region per
+// (device, stream) -- launches on one stream run one after another and every launch leaves its counters at zero, launches on different
+// streams never share a region.  nullptr: none available, this launch keeps the reduce kernel. ----
+constexpr int ARRIVAL_REGION = 8192, ARRIVAL_REGIONS = 32;      // counters (= output tiles) per region, regions
+unsigned* arrival_counters(hipStream_t st) {
     static std::mutex mu;
     static unsigned* base[64] = {};
     static std::unordered_map<hipStream_t, int> region[64];
@@ -1430,7 +1370,7 @@ unsigned* arrival_counters(hipStream_t st, long tiles) {
     if (!base[dev]) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(st, &cap);
-        if (cap != hipStreamCaptureStatusNone) return nullptr;          // no allocation inside a capture: this launch keeps the reduce kernel
+        if (cap != hipStreamCaptureStatusNone) return nullptr;          // no allocation inside a capture
         unsigned* ptr = nullptr;
         const size_t bytes = (size_t)ARRIVAL_REGION * ARRIVAL_REGIONS * sizeof(unsigned);
         if (hipMalloc(&ptr, bytes) != hipSuccess) return nullptr;
@@ -1445,98 +1385,171 @@ unsigned* arrival_counters(hipStream_t st, long tiles) {
     return base[dev] + (size_t)it->second * ARRIVAL_REGION;
 }
 
-// the split-bf16 form serves 128 x 128 plans whose operands can be read in aligned-extent quads
-bool b3_eligible(const GemmParams& p, int layout) {
-    if (!gemm_b3_on() || p.K < 32) return false;          // any K >= 32: a partial last stage is handled by B3Loader::load_tail
-    const bool a_ok = layout != 2 || (p.M % 4 == 0 && p.M >= 4);
-    const bool b_ok = layout == 0 || (p.N % 4 == 0 && p.N >= 4);
-    return a_ok && b_ok;
-}
-// the 64 x 64 split-bf16 tile: the 128-tile grid would leave CUs idle (or split K) while 64-tiles fill the chip, and K is deep enough to
-// amortise the tile's prologue.  BBBP_GEMM_B3_SMALL=0 keeps the 128-tile plans.
-bool b3_small_tile(int M, int N, int K, int batch) {
-    static const int on = bbbp_env_int("BBBP_GEMM_B3_SMALL", 1);
-    if (!on || K < 512) return false;
-    const long t128 = (long)cdiv(M, 128) * cdiv(N, 128) * batch, t64 = (long)cdiv(M, 64) * cdiv(N, 64) * batch;
-    const int ncu = bbbp_num_cus();
-    return t128 < ncu && t64 * 2 >= (long)ncu * 5;
-}
-template <int LAYOUT>
-int launch_b3_one(const GemmParams& p, dim3 grid, hipStream_t st) {
-    { int rc_ = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_b3_kernel<LAYOUT>), (size_t)B3_LDS); if (rc_) return rc_; }
-    static const bool probe = bbbp_env_int("BBBP_GEMM_B3_PROBE", 0) != 0;
-    if (probe) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_b3_probe_kernel<LAYOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)B3_LDS);
-        hipLaunchKernelGGL((gemm_b3_probe_kernel<LAYOUT>), grid, dim3(256), B3_LDS, st, p);
-    } else {
-        hipLaunchKernelGGL((gemm_b3_kernel<LAYOUT>), grid, dim3(256), B3_LDS, st, p);
+// layout: NT = (transA 0, transB 1); NN = (0, 0); TN = (1, 0).  LAYOUT_ANY: not known (the workspace and capability queries)
+constexpr int LAYOUT_ANY = -1;
+struct GemmProblem {
+    int M, N, K, batch;
+    int layout = LAYOUT_ANY;
+    bool asum_column = false;      // a TN product whose caller asks for the column sums of A: one more output column on the direct path
+    bool quad_epilogue = false;    // C, bias, residual, gate and the slab are 16-byte aligned with strides that are multiples of 4
+};
+
+enum class GemmKernel {
+    Direct,               // gemm_direct_kernel: no LDS staging, 16x16 / 32x32 wave tiles, K slices reduced inside the work-group
+    B3Small,              // gemm_b3s_kernel: 64 x 64 split-bf16 tile, the whole K in one launch
+    B3,                   // gemm_b3_kernel: 128 x 128 split-bf16 tile
+    F32Tile128,           // gemm_f32_kernel<128, 128>
+    F32Tile128ShortK,     // gemm_f32_kernel<128, 128, ., true, 16>: four work-groups per CU
+    F32Tile64             // gemm_f32_kernel<64, 64>
+};
+struct GemmPlan {
+    GemmKernel kernel = GemmKernel::F32Tile64;
+    int tile = 0, splits = 1, kchunk = 0;       // LDS-tiled families: K range per split (multiple of the stage depth)
+    int t = 1, wsm = 1, wsn = 1, ks = 1;        // Direct: wave tile in 16s, waves along M / N, K slices
+    int gx = 0, gy = 0, gz = 0;                 // the family's grid
+    size_t slab_bytes = 0;                      // split-K slabs [batch][split][M][N]; 0: the launch needs no workspace
+    bool reduce = false, reduce_vec4 = false;   // gemm_splitk_reduce(4)_kernel follows ...
+    bool in_kernel_reduce = false;              // ... unless the opt-in arrival counters are available (B3 only, see arrival_counters)
+    bool asum_dropout = false;                  // desc.asum and output dropout are honoured (Direct only)
+};
+
+// The one place a launch is decided.  Pure: the problem, the CU count (bbbp_num_cus(), read once by the caller) and the knobs in, the plan
+// out.  `split_k` = false plans the same tile as a single pass (a caller without room for the slabs).
+GemmPlan gemm_plan(const GemmProblem& pr, int ncu, const GemmKnobs& kn, bool split_k = true) {
+    const int M = pr.M, N = pr.N, K = pr.K, batch = pr.batch;
+    GemmPlan pl;
+    // ---- the direct path serves launches that cannot fill the chip with 64x64 tiles anyway; big GEMMs keep the LDS tiling ----
+    if (kn.direct && 2.0 * M * N * (double)K * batch <= 1.2e9 && K <= 8192) {
+        const int nch = cdiv(K, 16);
+        pl.ks = nch <= 12 ? 1 : (cdiv(nch, 8) < kn.direct_ks ? cdiv(nch, 8) : kn.direct_ks);
+        if (pl.ks == 3) pl.ks = 4;
+        const long wt = (long)cdiv(M, 16) * cdiv(N, 16) * batch;
+        pl.t = (wt * pl.ks <= 4096 || kn.direct_t < 2) ? 1 : 2;
+        // many heads with a tiny head dimension (F = 2048: 256 heads of 8) are hundreds of thousands of nearly empty wave
+        // tiles: those stay on the LDS-tiled kernel.  (waves <= 16384 also keeps batch and both grid dimensions below 65536.)
+        const long waves = (long)cdiv(M, 16 * pl.t) * cdiv(N, 16 * pl.t) * batch * pl.ks;
+        const int mind = M < N ? (M < K ? M : K) : (N < K ? N : K);
+        if (pl.ks >= 4) { pl.wsm = 1; pl.wsn = 1; }
+        else if (pl.ks >= 2) { pl.wsm = 2; pl.wsn = 1; }
+        else { pl.wsm = 2; pl.wsn = 2; }
+        if (waves <= 16384 && !(batch >= 8 && mind < 16) && !((kn.direct & 2) && pl.ks > 1) && !((kn.direct & 4) && pl.t > 1)) {
+            pl.kernel = GemmKernel::Direct;
+            pl.gx = cdiv(N + (pr.asum_column ? 1 : 0), 16 * pl.t * pl.wsn); pl.gy = cdiv(M, 16 * pl.t * pl.wsm); pl.gz = batch;
+            pl.asum_dropout = true;
+            return pl;
+        }
+        pl = GemmPlan{};
     }
-    return BBBP_OK;
-}
-
-}  // namespace
-
-// Split-K plan shared by the launcher and bbbp_gemm_workspace_bytes.
-static void gemm_plan(int M, int N, int K, int batch, int* tile, int* splits, int* kchunk) {
-    long t128 = (long)cdiv(M, 128) * cdiv(N, 128) * batch;
-    long t64 = (long)cdiv(M, 64) * cdiv(N, 64) * batch;
-    int ncu = bbbp_num_cus();
-    *tile = (t128 >= (long)ncu * 3 / 4) ? 128 : 64;
+    // ---- tile: 128 x 128 when such tiles cover 3/4 of the chip ... ----
+    const long t128 = (long)cdiv(M, 128) * cdiv(N, 128) * batch, t64 = (long)cdiv(M, 64) * cdiv(N, 64) * batch;
+    const long covered = (long)cdiv(M, 128) * 128 * (long)cdiv(N, 128) * 128;
+    pl.tile = (t128 >= (long)ncu * 3 / 4) ? 128 : 64;
     // Very deep K over a small output (the 65536-wide image FC forward): the 128x128 tile does 64 MFMAs per wave per
     // stage, enough to cover the global-load latency of the next stage, and split-K supplies the parallelism; the
     // 64x64 tile (8 MFMAs per stage) is latency-bound there (measured 36 vs ~90 TFLOP/s).
-    if (K >= 8192 && M >= 128 && N >= 128) *tile = 128;
+    if (K >= 8192 && M >= 128 && N >= 128) pl.tile = 128;
     // Deep K with a large, 128-divisible output (the F = 2048 encoder's FFN / projection GEMMs): same argument.
-    {
-        const long covered = (long)cdiv(M, 128) * 128 * (long)cdiv(N, 128) * 128;
-        if (K >= 512 && M >= 256 && N >= 256 && covered * 100 <= (long)M * N * 115) *tile = 128;
-    }
-    // A deep K over many rows and one or two column tiles (linear2 of a 4096-row screening batch: N = 167, K = 2048): the 64 x 64 f32
-    // plan runs it at 49 TFLOP/s (66 us); on the bf16 pipe the padded columns (167 -> 256) cost less than the pipe gains.
-    // BBBP_GEMM_TALL_B3=0 keeps the old plan.
-    {
-        static const int tall = bbbp_env_int("BBBP_GEMM_TALL_B3", 1);
-        const long covered = (long)cdiv(M, 128) * 128 * (long)cdiv(N, 128) * 128;
-        if (tall && K >= 1024 && M >= 1024 && N >= 128 && covered * 10 <= (long)M * N * 16) *tile = 128;
-    }
-    long tiles = (*tile == 128) ? t128 : t64;
-    // Few output tiles and a deep K (weight gradients over the batch, the 65536-wide image FC, FFN2): these
-    // launches are latency-bound at one work-group per tile, so spread K over ~2 work-groups per CU.
+    if (K >= 512 && M >= 256 && N >= 256 && covered * 100 <= (long)M * N * 115) pl.tile = 128;
+    if (kn.tall_b3 && K >= 1024 && M >= 1024 && N >= 128 && covered * 10 <= (long)M * N * 16) pl.tile = 128;      // GemmKnobs::tall_b3
+    // ---- split-K.  Few output tiles and a deep K (weight gradients over the batch, the 65536-wide image FC, FFN2): these
+    // launches are latency-bound at one work-group per tile, so spread K over ~2 work-groups per CU. ----
+    const long tiles = pl.tile == 128 ? t128 : t64;
+    const int BK = bk_of(pl.tile);
     int s = 1;
-    // BBBP_GEMM_SPLIT_X10: target work-groups per CU x 10 when K is split (default 20 = two per CU)
-    static const int split_x10 = bbbp_env_int("BBBP_GEMM_SPLIT_X10", 20);
-    // BBBP_GEMM_SPLIT_FULL: also split when the tiles already cover the chip once but not twice (one work-group per CU leaves
-    // every barrier stall of its single wave per SIMD exposed)
-    static const int split_full = bbbp_env_int("BBBP_GEMM_SPLIT_FULL", 0);
-    if ((tiles < ncu || (split_full && tiles < 2 * ncu && K >= 512)) && K >= 256) {
-        s = (int)(((long)split_x10 * ncu / 10 + tiles - 1) / tiles);
-        int maxs = K / 64;
-        if (s > maxs) s = maxs;
+    if (split_k && (tiles < ncu || (kn.split_full && tiles < 2 * ncu && K >= 512)) && K >= 256) {
+        s = (int)(((long)kn.split_x10 * ncu / 10 + tiles - 1) / tiles);
+        if (s > K / 64) s = K / 64;
         if (s < 1) s = 1;
     }
-    const int BK = bk_of(*tile);
-    int kc = cdiv(cdiv(K, s), BK) * BK;
-    if (kc < BK) kc = BK;
-    s = cdiv(K, kc);
-    if (s < 1) s = 1;
-    *splits = s;
-    *kchunk = kc;
+    pl.kchunk = cdiv(cdiv(K, s), BK) * BK;
+    if (pl.kchunk < BK) pl.kchunk = BK;
+    pl.splits = cdiv(K, pl.kchunk) < 1 ? 1 : cdiv(K, pl.kchunk);
+    pl.gx = cdiv(N, pl.tile); pl.gy = cdiv(M, pl.tile); pl.gz = batch * pl.splits;
+    pl.slab_bytes = pl.splits > 1 ? (size_t)batch * pl.splits * M * N * sizeof(float) : 0;
+    pl.reduce = pl.splits > 1;
+    pl.reduce_vec4 = pl.reduce && kn.reduce_vec4 && N % 4 == 0 && pr.quad_epilogue;
+    // ---- family.  Without a layout no split-bf16 form can be promised: the answer is the 128 / 64 f32 tile with the split-K above, which
+    // is what bbbp_gemm_workspace_bytes has always reported (also for shapes that then run the 64 x 64 split-bf16 tile and leave the slab
+    // untouched). ----
+    pl.kernel = pl.tile == 128 ? GemmKernel::F32Tile128 : GemmKernel::F32Tile64;
+    if (pl.tile != 128 || pr.layout == LAYOUT_ANY) return pl;
+    // the split-bf16 forms serve 128 x 128 plans whose operands can be read in aligned-extent quads (any K >= 32: a partial last stage is
+    // handled by B3Loader::load_tail)
+    const bool b3 = kn.split_bf16 && K >= 32 && (pr.layout != 2 || (M % 4 == 0 && M >= 4)) && (pr.layout == 0 || (N % 4 == 0 && N >= 4));
+    if (b3 && pr.layout != 2 && kn.b3_small && K >= 512 && t128 < ncu && t64 * 2 >= (long)ncu * 5) {      // GemmKnobs::b3_small
+        pl.kernel = GemmKernel::B3Small;
+        pl.splits = 1; pl.kchunk = cdiv(K, B3_BK) * B3_BK;
+        pl.gx = cdiv(N, B3S_T); pl.gy = cdiv(M, B3S_T); pl.gz = batch;
+        pl.slab_bytes = 0; pl.reduce = pl.reduce_vec4 = false;
+    } else if (b3) {
+        pl.kernel = GemmKernel::B3;
+        pl.in_kernel_reduce = kn.fold_reduce && pl.splits > 1 && (long)pl.gx * pl.gy * batch <= ARRIVAL_REGION;
+    } else {
+        // 4-wide loads need a contiguous extent that is a multiple of 4 (see tile_params)
+        const bool vec = (pr.layout == 2 ? M : K) % 4 == 0 && (pr.layout == 0 ? K : N) % 4 == 0;
+        if (vec && pl.splits == 1 && K <= kn.short_k && t128 >= (long)kn.short_tiles * ncu) pl.kernel = GemmKernel::F32Tile128ShortK;
+    }
+    return pl;
 }
 
-extern "C" int bbbp_gemm_folds_asum(int M, int N, int K, int batch) {
-    if (M <= 0 || N <= 0 || K <= 0 || batch < 1) return 0;
-    const DirectPlan dp = direct_plan(M, N, K, batch);
-    return (dp.use && batch <= 65535 && cdiv(M, 16 * dp.t * dp.wsm) <= 65535) ? 1 : 0;
+// ---- launchers: a run-time value -> a template argument, then the plan's family as it stands ----
+template <int... Vs, class F>
+void with_constant(int v, F&& f) { (void)(... || (v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false)); }
+#define CONST_OF(x) decltype(x)::value
+
+inline size_t direct_lds(const DirectParams& p, int t) {
+    const int waves = p.wsm * p.wsn * p.ks;
+    size_t lds = p.ks > 1 ? (size_t)waves * t * t * 4 * 64 * sizeof(float) : 0;
+    return lds < g_bbbp_small_lds_pad ? g_bbbp_small_lds_pad : lds;
 }
 
-extern "C" size_t bbbp_gemm_workspace_bytes(int M, int N, int K, int batch) {
-    if (M <= 0 || N <= 0 || direct_plan(M, N, K, batch).use) return 0;
-    int tile, splits, kchunk;
-    gemm_plan(M, N, K, batch, &tile, &splits, &kchunk);
-    return splits > 1 ? (size_t)batch * splits * M * N * sizeof(float) : 0;
+void launch_direct(const DirectParams& p, int layout, int t, hipStream_t st) {
+    with_constant<1, 2>(t, [&](auto T) { with_constant<0, 1, 2>(layout, [&](auto L) {
+        hipLaunchKernelGGL((gemm_direct_kernel<CONST_OF(L), CONST_OF(T), CONST_OF(T)>), dim3(p.gx, p.gy, p.batch), dim3(64 * p.wsm * p.wsn * p.ks),
+                           direct_lds(p, CONST_OF(T)), st, p);
+    }); });
 }
 
-namespace {
+template <int L0, int T0, int L1, int T1>
+void launch_pair_one(const DirectParams& a, const DirectParams& b, hipStream_t st) {
+    const size_t la = direct_lds(a, T0), lb = direct_lds(b, T1);
+    dim3 grid(a.gx > b.gx ? a.gx : b.gx, a.gy > b.gy ? a.gy : b.gy, a.batch + b.batch);
+    hipLaunchKernelGGL((gemm_direct_pair_kernel<L0, T0, L1, T1>), grid, dim3(256), la > lb ? la : lb, st, a, b);
+}
+
+// the pairs the engine issues; anything else runs as two launches
+bool launch_pair(const DirectParams& a, int la, int ta, const DirectParams& b, int lb, int tb, hipStream_t st) {
+    if (a.wsm * a.wsn * a.ks != 4 || b.wsm * b.wsn * b.ks != 4 || ta != 1 || tb != 1 || (long)a.batch + b.batch > 65535) return false;
+    if (la == 2 && lb == 0) { launch_pair_one<2, 1, 0, 1>(a, b, st); return true; }      // dV = Pd^T dO | dPd = dO V^T
+    if (la == 1 && lb == 2) { launch_pair_one<1, 1, 2, 1>(a, b, st); return true; }      // dQ = dS K   | dK = dS^T Q
+    if (la == 2 && lb == 2) { launch_pair_one<2, 1, 2, 1>(a, b, st); return true; }      // [dWq; dWk] = dQK^T x | dW' = dVW^T x (fold.hip)
+    return false;
+}
+
+template <int BM, int BN, int LAYOUT, bool VEC, int BKT = 0>
+void launch_f32_tile(const GemmParams& p, dim3 grid, hipStream_t st) {
+    constexpr int BK = BKT ? BKT : bk_of(BM);
+    constexpr size_t lds = (size_t)2 * BK * ((BM + (LAYOUT == 2 ? 4 : 1)) + (BN + (LAYOUT != 0 ? 4 : 1))) * sizeof(float);
+    // a refused opt-in makes the launch itself fail, which BBBP_CHECK_LAUNCH reports
+    if (lds > 64 * 1024) (void)bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_f32_kernel<BM, BN, LAYOUT, VEC, BKT>), lds);
+    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, LAYOUT, VEC, BKT>), grid, dim3(256), lds > g_bbbp_small_lds_pad ? lds : g_bbbp_small_lds_pad, st, p);
+}
+
+template <int LAYOUT>
+int launch_b3(const GemmParams& p, dim3 grid, bool probe, hipStream_t st) {
+    if (!probe) return launch_lds(gemm_b3_kernel<LAYOUT>, grid, 256, B3_LDS, st, p);
+    TRY_RC(bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_b3_kernel<LAYOUT>), (size_t)B3_LDS));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_b3_probe_kernel<LAYOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)B3_LDS);
+    hipLaunchKernelGGL((gemm_b3_probe_kernel<LAYOUT>), grid, dim3(256), B3_LDS, st, p);
+    return BBBP_OK;
+}
+
+template <int LAYOUT>
+int launch_b3_small(const GemmParams& p, dim3 grid, hipStream_t st) {
+    return launch_lds(gemm_b3s_kernel<LAYOUT, LAYOUT == 0 ? B3S_DEPTH_NT : B3S_DEPTH_NN>, grid, 256, B3S_LDS, st, p);
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int gemm_validate(const bbbp_gemm_desc& g) {
     BBBP_CHECK_ARG(g.M >= 0 && g.N >= 0 && g.K >= 0 && g.batch >= 1, "gemm: bad sizes M=%d N=%d K=%d batch=%d", g.M, g.N, g.K, g.batch);
@@ -1552,110 +1565,112 @@ int gemm_validate(const bbbp_gemm_desc& g) {
     return BBBP_OK;
 }
 
-// layout: NT = (transA 0, transB 1); NN = (0, 0); TN = (1, 0)
-inline int layout_of(const bbbp_gemm_desc& g) { return g.transA ? 2 : (g.transB ? 0 : 1); }
+GemmProblem problem_of(const bbbp_gemm_desc& g, const void* slab) {
+    GemmProblem pr{g.M, g.N, g.K, g.batch, g.transA ? 2 : (g.transB ? 0 : 1)};
+    pr.asum_column = g.transA && !g.transB && g.asum;
+    pr.quad_epilogue = g.ldc % 4 == 0 && g.strideC % 4 == 0 && aligned16(g.C) && aligned16(slab) && (!g.bias || aligned16(g.bias)) &&
+                       (!g.residual || (g.ldr % 4 == 0 && g.strideR % 4 == 0 && aligned16(g.residual))) &&
+                       (!g.gate || (g.ldg % 4 == 0 && g.strideG % 4 == 0 && aligned16(g.gate)));
+    return pr;
+}
 
-bool direct_params(const bbbp_gemm_desc& g, DirectParams* d, int* t) {
-    const DirectPlan dp = direct_plan(g.M, g.N, g.K, g.batch);
-    if (!dp.use || g.batch > 65535 || cdiv(g.M, 16 * dp.t * dp.wsm) > 65535) return false;
-    d->A = g.A; d->B = g.B; d->C = g.C; d->bias = g.bias; d->R = g.residual;
-    d->M = g.M; d->N = g.N; d->K = g.K; d->lda = g.lda; d->ldb = g.ldb; d->ldc = g.ldc; d->ldr = g.ldr;
-    d->sA = g.strideA; d->sB = g.strideB; d->sC = g.strideC; d->sR = g.strideR;
-    d->alpha = g.alpha; d->act = g.act;
-    d->gate = g.gate; d->ldg = g.ldg; d->sG = g.strideG; d->gate_scale = g.gate_scale; d->gate_after = g.gate_after_residual;
-    d->wsm = dp.wsm; d->wsn = dp.wsn; d->ks = dp.ks;
-    d->asum = (g.transA && !g.transB) ? g.asum : nullptr;
-    d->drop_p = g.drop_p; d->drop_inv_keep = g.drop_p > 0.f ? 1.f / (1.f - g.drop_p) : 1.f; d->drop_seed = g.drop_seed; d->seed_base = g_bbbp_seed_base;
-    d->batch = g.batch; d->gx = cdiv(g.N + (d->asum ? 1 : 0), 16 * dp.t * dp.wsn); d->gy = cdiv(g.M, 16 * dp.t * dp.wsm);
-    *t = dp.t;
-    return true;
+template <class P>      // the fields GemmParams and DirectParams share
+void copy_desc(P& d, const bbbp_gemm_desc& g) {
+    d.A = g.A; d.B = g.B; d.C = g.C; d.bias = g.bias; d.R = g.residual;
+    d.M = g.M; d.N = g.N; d.K = g.K; d.lda = g.lda; d.ldb = g.ldb; d.ldc = g.ldc; d.ldr = g.ldr;
+    d.sA = g.strideA; d.sB = g.strideB; d.sC = g.strideC; d.sR = g.strideR;
+    d.alpha = g.alpha; d.act = g.act;
+    d.gate = g.gate; d.ldg = g.ldg; d.sG = g.strideG; d.gate_scale = g.gate_scale; d.gate_after = g.gate_after_residual;
+}
+
+DirectParams direct_params(const bbbp_gemm_desc& g, const GemmProblem& pr, const GemmPlan& pl) {
+    DirectParams d;
+    copy_desc(d, g);
+    d.wsm = pl.wsm; d.wsn = pl.wsn; d.ks = pl.ks;
+    d.asum = pr.asum_column ? g.asum : nullptr;
+    d.drop_p = g.drop_p; d.drop_inv_keep = g.drop_p > 0.f ? 1.f / (1.f - g.drop_p) : 1.f; d.drop_seed = g.drop_seed; d.seed_base = g_bbbp_seed_base;
+    d.batch = pl.gz; d.gx = pl.gx; d.gy = pl.gy;
+    return d;
+}
+
+GemmParams tile_params(const bbbp_gemm_desc& g, const GemmPlan& pl, void* workspace) {
+    GemmParams p;
+    copy_desc(p, g);
+    // 4-wide loads need a contiguous extent that is a multiple of 4 (so that a quad is either fully inside or fully
+    // outside the matrix): K for an [M][K] / [N][K] operand, M or N for a [K][.] one.  Bases and strides may be odd
+    // (the image-FC weight sits at an odd offset of the flat parameter buffer when F = 167): the loads are unaligned dwordx4.
+    p.vecA = ((g.transA ? g.M : g.K) % 4 == 0);
+    p.vecB = ((g.transB ? g.K : g.N) % 4 == 0);
+    p.splits = pl.splits; p.kchunk = pl.kchunk;
+    p.slab = pl.slab_bytes ? static_cast<float*>(workspace) : nullptr;
+    p.arrivals = nullptr;
+    p.short_k = pl.kernel == GemmKernel::F32Tile128ShortK;
+    return p;
 }
 
 int gemm_run(hipStream_t st, const bbbp_gemm_desc& g, void* workspace, size_t workspace_bytes) {
     TRY_RC(gemm_validate(g));
     if (g.M == 0 || g.N == 0) return BBBP_OK;
-    const int layout = layout_of(g);
-    DirectParams d; int t;
-    if (direct_params(g, &d, &t)) {
-        launch_direct(d, layout, t, st);
+    const int ncu = bbbp_num_cus();
+    const GemmKnobs kn = gemm_knobs();
+    const GemmProblem pr = problem_of(g, workspace);
+    GemmPlan pl = gemm_plan(pr, ncu, kn);
+    if (pl.slab_bytes && (!workspace || workspace_bytes < pl.slab_bytes)) pl = gemm_plan(pr, ncu, kn, false);      // no room: a single pass
+    if (pl.kernel == GemmKernel::Direct) {
+        launch_direct(direct_params(g, pr, pl), pr.layout, pl.t, st);
         BBBP_CHECK_LAUNCH();
         return BBBP_OK;
     }
     BBBP_CHECK_ARG(!g.asum, "gemm: asum is only produced by the small-product path (bbbp_gemm_folds_asum(%d, %d, %d, %d) == 0)", g.M, g.N, g.K, g.batch);
     BBBP_CHECK_ARG(!(g.drop_p > 0.f), "gemm: output dropout is only applied by the small-product path (bbbp_gemm_folds_asum(%d, %d, %d, %d) == 0)", g.M, g.N, g.K, g.batch);
-    const int M = g.M, N = g.N, K = g.K, batch = g.batch;
-    GemmParams p;
-    p.A = g.A; p.B = g.B; p.C = g.C; p.bias = g.bias; p.R = g.residual;
-    p.M = M; p.N = N; p.K = K; p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc; p.ldr = g.ldr;
-    p.sA = g.strideA; p.sB = g.strideB; p.sC = g.strideC; p.sR = g.strideR;
-    p.alpha = g.alpha; p.act = g.act;
-    p.gate = g.gate; p.ldg = g.ldg; p.sG = g.strideG; p.gate_scale = g.gate_scale; p.gate_after = g.gate_after_residual;
-    // 4-wide loads need a contiguous extent that is a multiple of 4 (so that a quad is either fully inside or fully
-    // outside the matrix): K for an [M][K] / [N][K] operand, M or N for a [K][.] one.  Bases and strides may be odd
-    // (the image-FC weight sits at an odd offset of the flat parameter buffer when F = 167): the loads are unaligned dwordx4.
-    p.vecA = ((g.transA ? M : K) % 4 == 0);
-    p.vecB = ((g.transB ? K : N) % 4 == 0);
-    int tile;
-    gemm_plan(M, N, K, batch, &tile, &p.splits, &p.kchunk);
-    p.slab = nullptr;
-    if (p.splits > 1) {
-        size_t need = (size_t)batch * p.splits * M * N * sizeof(float);
-        if (!workspace || workspace_bytes < need) {   // no room: fall back to a single pass
-            p.splits = 1;
-            p.kchunk = cdiv(K, bk_of(tile)) * bk_of(tile);
-        } else {
-            p.slab = static_cast<float*>(workspace);
-        }
+    BBBP_CHECK_ARG(pl.gy <= 65535 && pl.gz <= 65535, "gemm: grid too large");
+    GemmParams p = tile_params(g, pl, workspace);
+    const dim3 grid(pl.gx, pl.gy, pl.gz);
+    const bool vec = p.vecA && p.vecB;
+    int rc = BBBP_OK;
+    switch (pl.kernel) {
+    case GemmKernel::B3Small:
+        with_constant<0, 1>(pr.layout, [&](auto L) { rc = launch_b3_small<CONST_OF(L)>(p, grid, st); });
+        break;
+    case GemmKernel::B3:
+        if (pl.in_kernel_reduce) p.arrivals = arrival_counters(st);
+        with_constant<0, 1, 2>(pr.layout, [&](auto L) { rc = launch_b3<CONST_OF(L)>(p, grid, kn.b3_probe != 0, st); });
+        break;
+    case GemmKernel::F32Tile128ShortK:
+        with_constant<0, 1, 2>(pr.layout, [&](auto L) { launch_f32_tile<128, 128, CONST_OF(L), true, 16>(p, grid, st); });
+        break;
+    case GemmKernel::F32Tile128:
+        with_constant<0, 1, 2>(pr.layout, [&](auto L) { with_constant<1, 0>(vec, [&](auto V) { launch_f32_tile<128, 128, CONST_OF(L), CONST_OF(V) != 0>(p, grid, st); }); });
+        break;
+    default:
+        with_constant<0, 1, 2>(pr.layout, [&](auto L) { with_constant<1, 0>(vec, [&](auto V) { launch_f32_tile<64, 64, CONST_OF(L), CONST_OF(V) != 0>(p, grid, st); }); });
     }
-    if (K == 0) { p.splits = 1; p.kchunk = bk_of(tile); }
-    static const int short_k_max = bbbp_env_int("BBBP_GEMM_SHORT_K", 256);
-    static const int short_k_tiles = bbbp_env_int("BBBP_GEMM_SHORT_TILES", 4);
-    p.short_k = (tile == 128 && p.splits == 1 && K <= short_k_max &&
-                 (long)cdiv(M, 128) * cdiv(N, 128) * batch >= (long)short_k_tiles * bbbp_num_cus()) ? 1 : 0;
-    dim3 grid(cdiv(N, tile), cdiv(M, tile), batch * p.splits);
-    BBBP_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "gemm: grid too large");
-    p.arrivals = nullptr;
-    // few 128 x 128 tiles, many 64 x 64 ones, deep K: the small split-bf16 tile walks the whole K in one launch (gemm_b3s_kernel)
-    if (tile == 128 && layout != 2 && b3_eligible(p, layout) && b3_small_tile(M, N, K, batch)) {
-        p.splits = 1; p.kchunk = cdiv(K, B3_BK) * B3_BK; p.slab = nullptr;
-        dim3 gs(cdiv(N, B3S_T), cdiv(M, B3S_T), batch);
-        BBBP_CHECK_ARG(gs.y <= 65535 && gs.z <= 65535, "gemm: grid too large");
-        if (layout == 0) {
-            TRY_RC(bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_b3s_kernel<0, B3S_DEPTH_NT>), B3S_LDS));
-            hipLaunchKernelGGL((gemm_b3s_kernel<0, B3S_DEPTH_NT>), gs, dim3(256), B3S_LDS, st, p);
-        } else {
-            TRY_RC(bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_b3s_kernel<1, B3S_DEPTH_NN>), B3S_LDS));
-            hipLaunchKernelGGL((gemm_b3s_kernel<1, B3S_DEPTH_NN>), gs, dim3(256), B3S_LDS, st, p);
-        }
-        BBBP_CHECK_LAUNCH();
-        return BBBP_OK;
-    }
-    if (tile == 128 && b3_eligible(p, layout)) {
-        if (p.splits > 1) p.arrivals = arrival_counters(st, (long)grid.x * grid.y * batch);
-        TRY_RC(layout == 0 ? launch_b3_one<0>(p, grid, st) : layout == 1 ? launch_b3_one<1>(p, grid, st) : launch_b3_one<2>(p, grid, st));
-    } else if (tile == 128) launch_tile<128, 128>(p, layout, grid, st);
-    else launch_tile<64, 64>(p, layout, grid, st);
+    TRY_RC(rc);
     BBBP_CHECK_LAUNCH();
-    if (p.splits > 1 && !p.arrivals) {
-        long mn = (long)M * N;
-        int gx = (int)((mn + 255) / 256);
-        if (gx > 4096) gx = 4096;
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        static const int vec4_on = bbbp_env_int("BBBP_GEMM_REDUCE_VEC4", 1);
-        const bool vec4 = vec4_on && N % 4 == 0 && p.ldc % 4 == 0 && p.sC % 4 == 0 && al16(p.C) && al16(p.slab) && (!p.bias || al16(p.bias)) &&
-                          (!p.R || (p.ldr % 4 == 0 && p.sR % 4 == 0 && al16(p.R))) && (!p.gate || (p.ldg % 4 == 0 && p.sG % 4 == 0 && al16(p.gate)));
-        if (vec4) {
-            int g4 = (int)((mn / 4 + 255) / 256);
-            if (g4 > 4096) g4 = 4096;
-            hipLaunchKernelGGL(gemm_splitk_reduce4_kernel, dim3(g4, batch), dim3(256), g_bbbp_small_lds_pad, st, p);
-        } else
-        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(gx, batch), dim3(256), g_bbbp_small_lds_pad, st, p);
+    if (pl.reduce && !p.arrivals) {
+        const long quads = ((long)g.M * g.N / (pl.reduce_vec4 ? 4 : 1) + 255) / 256;
+        const dim3 rgrid((unsigned)(quads > 4096 ? 4096 : quads), g.batch);
+        if (pl.reduce_vec4) hipLaunchKernelGGL(gemm_splitk_reduce4_kernel, rgrid, dim3(256), g_bbbp_small_lds_pad, st, p);
+        else hipLaunchKernelGGL(gemm_splitk_reduce_kernel, rgrid, dim3(256), g_bbbp_small_lds_pad, st, p);
         BBBP_CHECK_LAUNCH();
     }
     return BBBP_OK;
 }
 
+// the layout-free questions (workspace, capabilities) ask the same function
+GemmPlan gemm_plan_any_layout(int M, int N, int K, int batch) { return gemm_plan(GemmProblem{M, N, K, batch}, bbbp_num_cus(), gemm_knobs()); }
+
 }  // namespace
+
+extern "C" int bbbp_gemm_folds_asum(int M, int N, int K, int batch) {
+    return (M > 0 && N > 0 && K > 0 && batch >= 1 && gemm_plan_any_layout(M, N, K, batch).asum_dropout) ? 1 : 0;
+}
+
+// The layout is not known here (GemmProblem::layout = LAYOUT_ANY): the plan then reports the split-K slabs of the 128 / 64 tile, also for
+// shapes that a known NT / NN layout puts on the 64 x 64 split-bf16 tile, which never touches them.  Callers size their scratch by this.
+extern "C" size_t bbbp_gemm_workspace_bytes(int M, int N, int K, int batch) {
+    return (M <= 0 || N <= 0) ? 0 : gemm_plan_any_layout(M, N, K, batch).slab_bytes;
+}
 
 extern "C" int bbbp_gemm_f32(void* stream, int transA, int transB, int M, int N, int K, float alpha,
                              const float* A, int lda, const float* B, int ldb, float* C, int ldc,
@@ -1681,12 +1696,17 @@ extern "C" int bbbp_gemm_f32_grouped(void* stream, const bbbp_gemm_desc* problem
             const bbbp_gemm_desc &a = problems[i], &b = problems[i + 1];
             TRY_RC(gemm_validate(a));
             TRY_RC(gemm_validate(b));
-            DirectParams da, db; int ta, tb;
-            if (a.M > 0 && a.N > 0 && b.M > 0 && b.N > 0 && direct_params(a, &da, &ta) && direct_params(b, &db, &tb) &&
-                launch_pair(da, layout_of(a), ta, db, layout_of(b), tb, st)) {
-                BBBP_CHECK_LAUNCH();
-                i += 2;
-                continue;
+            if (a.M > 0 && a.N > 0 && b.M > 0 && b.N > 0) {
+                const int ncu = bbbp_num_cus();
+                const GemmKnobs kn = gemm_knobs();
+                const GemmProblem pa = problem_of(a, workspace), pb = problem_of(b, workspace);
+                const GemmPlan la = gemm_plan(pa, ncu, kn), lb = gemm_plan(pb, ncu, kn);
+                if (la.kernel == GemmKernel::Direct && lb.kernel == GemmKernel::Direct &&
+                    launch_pair(direct_params(a, pa, la), pa.layout, la.t, direct_params(b, pb, lb), pb.layout, lb.t, st)) {
+                    BBBP_CHECK_LAUNCH();
+                    i += 2;
+                    continue;
+                }
             }
         }
         // the split-K scratch is shared: sequential launches on one stream may reuse it
@@ -1699,6 +1719,7 @@ extern "C" int bbbp_gemm_f32_grouped(void* stream, const bbbp_gemm_desc* problem
 extern "C" int bbbp_set_gemm_fold_reduce(int on) { return g_gemm_fold_reduce.set(on); }
 
 extern "C" int bbbp_set_gemm_split_bf16(int on) { return g_gemm_b3.set(on); }
+
 
 extern "C" int bbbp_gemm_split_bf16_phases(unsigned long long* phases7) {
     BBBP_CHECK_ARG(phases7 != nullptr, "gemm_split_bf16_phases: null output");
@@ -1740,8 +1761,8 @@ extern "C" int bbbp_layernorm_linear_supported(int M, int N, int K) {
 // wave tiles or the split-bf16 kernels, which the absorbing kernel would be slower than)
 bool bbbp_layernorm_linear_preferred(int M, int N, int K) {
     if (!bbbp_layernorm_linear_supported(M, N, K)) return false;
-    const DirectPlan dp = direct_plan(M, N, K, 1);
-    return dp.use && dp.t == 1 && dp.ks == 1;
+    const GemmPlan pl = gemm_plan_any_layout(M, N, K, 1);
+    return pl.kernel == GemmKernel::Direct && pl.t == 1 && pl.ks == 1;
 }
 
 extern "C" int bbbp_layernorm_linear_fwd(void* stream, const float* z, int ldz, const float* gamma, const float* beta, float eps,
