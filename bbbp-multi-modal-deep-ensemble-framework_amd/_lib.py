@@ -50,6 +50,14 @@ class MlpModel(Structure):
                 ("t", c_long), ("best_loss", ctypes.c_double), ("no_improve", c_int), ("n_iter", c_int), ("done", c_int)]
 
 
+class GemmF64cDesc(Structure):
+    """bbbp_gemm_f64c_desc (include/bbbp_hip.h)."""
+    _fields_ = [("layout", c_int), ("M", c_int), ("N", c_int), ("K", c_int),
+                ("A", c_void_p), ("a_dtype", c_int), ("lda", c_long), ("B", c_void_p), ("b_dtype", c_int), ("ldb", c_long),
+                ("a_shift", c_void_p), ("b_shift", c_void_p), ("row_scale", c_void_p),
+                ("C", c_void_p), ("c_dtype", c_int), ("ldc", c_long), ("symmetric", c_int), ("split_k", c_int)]
+
+
 _FP = c_void_p          # device float*
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -91,6 +99,9 @@ _SIGNATURES = {
                                     c_void_p, c_void_p]),
     "bbbp_mlp_train_epochs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int]),
     "bbbp_mlp_predict_proba": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "bbbp_pca_col_mean": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_long, c_void_p]),
+    "bbbp_gemm_f64c_workspace_bytes": (c_size_t, [POINTER(GemmF64cDesc)]),
+    "bbbp_gemm_f64c": (c_int, [c_void_p, POINTER(GemmF64cDesc), c_void_p, c_size_t]),
     "bbbp_graph_stats": (c_int, [POINTER(c_long), POINTER(c_long)]),
     "bbbp_conv_last_clock": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "bbbp_set_conv_winograd": (c_int, [c_int]),

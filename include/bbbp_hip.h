@@ -367,6 +367,39 @@ int bbbp_oblivious_predict(void* stream, const float* X, long n, int n_features,
                            const uint8_t* nan_true, const int* tree_first_split, const long* tree_first_leaf, const double* leaf_values,
                            int n_trees, double scale, double bias, double* leaf_scratch, double* out);
 
+/* ---- PCA: float64 column means and centred products on the float64 matrix pipe (csrc/pca.hip) -----------------------
+ * sklearn.decomposition.PCA(n).fit_transform in front of the PCA-fusion models (Models/multi_input_data_regression_opt_transformer_cnn_opt.py:30-33,
+ * its _morgan / _rdkit / _opt_more siblings) and of the MLPClassifier grid (Models/model_opt_maccs.py:104-109).  bbbp_amd/decomposition.py
+ * composes a fit from these and a host eigen-solve of the min(n, d)^2 matrix. */
+#define BBBP_DTYPE_F32 0
+#define BBBP_DTYPE_F64 1
+#define BBBP_F64C_NT 0   /* both operands k-contiguous: A[m * lda + k], B[n * ldb + k] */
+#define BBBP_F64C_TN 1   /* both operands k-major:      A[k * lda + m], B[k * ldb + n] */
+/* mean[j] = (sum_i X[i * ld + j]) / n in float64, X float32 or float64 (dtype: BBBP_DTYPE_*).  Fixed summation order: two calls give the
+ * same bits.  A non-finite input yields a non-finite mean. */
+int bbbp_pca_col_mean(void* stream, const void* X, int dtype, long n, int d, long ld, double* mean);
+/* C[M,N] = row_scale[m] * sum_k (A(m,k) - sa) (B(n,k) - sb), accumulated in float64.  The shifts are subtracted per element in float64
+ * while the operand is staged (never algebraically): a_shift / b_shift are indexed by k in NT (length K) and by the operand's own row /
+ * column index in TN (length M / N); NULL = no shift.  C is float64, or float32 rounded once from the accumulator.
+ * symmetric != 0: B must be A (same pointer, leading dimension, dtype, shift), M == N, no row_scale; only tiles on or below the diagonal are
+ * computed and every element is written to (m, n) and (n, m): C is bitwise symmetric.
+ * split_k: 0 lets the plan choose the number of K slabs, > 0 forces it.  With more than one slab the partial products go to `workspace`
+ * (bbbp_gemm_f64c_workspace_bytes for the same descriptor) and a second launch adds them in slab order: results are bit-reproducible. */
+typedef struct bbbp_gemm_f64c_desc {
+    int layout;                   /* BBBP_F64C_NT / BBBP_F64C_TN */
+    int M, N, K;
+    const void* A; int a_dtype; long lda;
+    const void* B; int b_dtype; long ldb;
+    const double* a_shift; const double* b_shift;
+    const double* row_scale;      /* [M], nullable */
+    void* C; int c_dtype; long ldc;
+    int symmetric;
+    int split_k;
+} bbbp_gemm_f64c_desc;
+/* 0 with a message in bbbp_last_error() for an invalid descriptor (pointers are not examined); 0 also when one slab suffices */
+size_t bbbp_gemm_f64c_workspace_bytes(const bbbp_gemm_f64c_desc* d);
+int bbbp_gemm_f64c(void* stream, const bbbp_gemm_f64c_desc* d, void* workspace, size_t workspace_bytes);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
