@@ -58,6 +58,14 @@ class GemmF64cDesc(Structure):
                 ("C", c_void_p), ("c_dtype", c_int), ("ldc", c_long), ("symmetric", c_int), ("split_k", c_int)]
 
 
+class KnnDesc(Structure):
+    """bbbp_knn_desc (include/bbbp_hip.h)."""
+    _fields_ = [("m", c_int), ("n", c_int), ("d", c_int), ("k", c_int),
+                ("Q", c_void_p), ("q_dtype", c_int), ("ldq", c_long), ("T", c_void_p), ("t_dtype", c_int), ("ldt", c_long),
+                ("mu", c_void_p), ("q_norm", c_void_p), ("t_norm", c_void_p), ("dist", c_void_p), ("ind", c_void_p),
+                ("exclude_self", c_int), ("slices", c_int)]
+
+
 _FP = c_void_p          # device float*
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -102,6 +110,10 @@ _SIGNATURES = {
     "bbbp_pca_col_mean": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_long, c_void_p]),
     "bbbp_gemm_f64c_workspace_bytes": (c_size_t, [POINTER(GemmF64cDesc)]),
     "bbbp_gemm_f64c": (c_int, [c_void_p, POINTER(GemmF64cDesc), c_void_p, c_size_t]),
+    "bbbp_knn_row_norms": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_long, c_void_p, c_void_p, c_void_p]),
+    "bbbp_knn_workspace_bytes": (c_size_t, [POINTER(KnnDesc)]),
+    "bbbp_knn_f64": (c_int, [c_void_p, POINTER(KnnDesc), c_void_p, c_size_t]),
+    "bbbp_knn_vote": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
     "bbbp_graph_stats": (c_int, [POINTER(c_long), POINTER(c_long)]),
     "bbbp_conv_last_clock": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "bbbp_set_conv_winograd": (c_int, [c_int]),

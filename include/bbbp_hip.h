@@ -400,6 +400,43 @@ typedef struct bbbp_gemm_f64c_desc {
 size_t bbbp_gemm_f64c_workspace_bytes(const bbbp_gemm_f64c_desc* d);
 int bbbp_gemm_f64c(void* stream, const bbbp_gemm_f64c_desc* d, void* workspace, size_t workspace_bytes);
 
+/* ---- neighbors: fused float64 brute-force k-nearest-neighbour search and classifier vote (csrc/knn.hip) ------------------
+ * KNeighborsClassifier() of the classification stack (Models/model_opt_maccs.py:126, 143-144) and the neighbour query a SMOTE starts
+ * with.  Euclidean metric, k <= 32.  The [m][n] distance matrix never exists in memory: HBM traffic is the operands, the norms and the
+ * lists.  bbbp_amd/neighbors.py composes NearestNeighbors / KNeighborsClassifier / grid_search_cv from these. */
+#define BBBP_KNN_UNIFORM 0
+#define BBBP_KNN_DISTANCE 1
+/* norms[i] = sum_k (X[i * ld + k] - mu[k])^2 in float64 (mu NULL: no shift), fixed summation order.  ORs 1 into *nonfinite (a device
+ * word the caller zeroed) when a row's sum is NaN or infinite -- a NaN / infinite element, or an overflowing square. */
+int bbbp_knn_row_norms(void* stream, const void* X, int dtype, long n, int d, long ld, const double* mu, double* norms, int* nonfinite);
+/* For every query row the k training rows of smallest Euclidean distance, in the total order (distance, training index).
+ * Selection runs on s = |q - mu|^2 + |t - mu|^2 - 2 (q - mu).(t - mu) with the Gram term on the float64 matrix pipe and the shift subtracted
+ * at staging; q_norm / t_norm are bbbp_knn_row_norms of Q / T with the same mu.  The k kept rows then get their distance recomputed by
+ * direct differences and are sorted again: dist is sqrt of that (exactly 0 for a duplicate of the query), ind the training index.
+ * exclude_self != 0: Q must be T (same pointer, leading dimension, dtype, m == n) and row i is not a neighbour of query i.
+ * slices: 0 lets the plan choose how many slices the training rows are cut into, > 0 forces it (<= 64).  With more than one slice the
+ * partial lists go to `workspace` (bbbp_knn_workspace_bytes for the same descriptor) and a merge launch combines them; the result is
+ * bit-identical for every slice count and from call to call. */
+typedef struct bbbp_knn_desc {
+    int m, n, d, k;
+    const void* Q; int q_dtype; long ldq;      /* [m][d], BBBP_DTYPE_* */
+    const void* T; int t_dtype; long ldt;      /* [n][d] */
+    const double* mu;                          /* [d], nullable */
+    const double* q_norm; const double* t_norm;
+    double* dist; long long* ind;              /* [m][k] each */
+    int exclude_self;
+    int slices;
+} bbbp_knn_desc;
+/* 0 with a message in bbbp_last_error() for an invalid descriptor (pointers are not examined); 0 also when one slice suffices */
+size_t bbbp_knn_workspace_bytes(const bbbp_knn_desc* d);
+int bbbp_knn_f64(void* stream, const bbbp_knn_desc* d, void* workspace, size_t workspace_bytes);
+/* Class vote over the first kk of the k neighbours of each of m queries.  labels[n]: class id (0 .. n_classes - 1, n_classes <= 32) of
+ * every training row.  weights: BBBP_KNN_UNIFORM, or BBBP_KNN_DISTANCE = 1 / dist, where a query with a zero among its kk distances
+ * gives those neighbours weight 1 and the others 0.  Weights are added in neighbour order in float64.  proba[m][n_classes] is
+ * normalised; pred[m] is the class of largest weight, the lowest id on ties. */
+int bbbp_knn_vote(void* stream, const double* dist, const long long* ind, long m, int k, int kk, const int* labels, long n, int n_classes,
+                  int weights, double* proba, int* pred);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
