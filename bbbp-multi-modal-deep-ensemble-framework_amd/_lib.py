@@ -77,6 +77,7 @@ _SIGNATURES = {
                               _FP, _FP, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_void_p, c_size_t]),
     "bbbp_gemm_folds_asum": (c_int, [c_int, c_int, c_int, c_int]),
     "bbbp_gemm_f32_grouped": (c_int, [c_void_p, POINTER(GemmDesc), c_int, c_void_p, c_size_t]),
+    "bbbp_gemm_kernel_form": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "bbbp_mixed_backward_wait_bucket": (c_int, [c_void_p, c_int]),
     "bbbp_mixed_backward_wait_released": (c_int, [c_void_p, c_int]),
     "bbbp_set_release_events": (c_int, [c_int]),

@@ -84,7 +84,10 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 // LAYOUT 0: NT, 1: NN, 2: TN;  VEC: 16-byte global loads on both operands
 // BKT: k-depth of a stage (0 = bk_of(BM)).  16 instead of 32 halves the LDS of the 128 x 128 tile to 33 KB, so four
 // work-groups share a CU instead of two: for a short K (the image FC's input gradient, K = 128 = 4 stages of 32) the tile's
-// prologue, epilogue and exposed load latency then overlap with three other groups' MFMAs instead of one.
+// prologue, epilogue and exposed load latency then overlap with three other groups' MFMAs instead of one.  (With the split-bf16 knob on,
+// the NN products of that description -- K <= 128 in whole 32-deep stages, whole 128-column blocks that cover every CU, M >= 256, the image
+// FC's input gradient among them -- now run on gemm_b3r_kernel, which removes the per-tile prologue instead of hiding it; this variant keeps
+// the f32 form of such products and K up to GemmKnobs::short_k.)
 template <int BM, int BN, int LAYOUT, bool VEC, int BKT = 0>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     BBBP_HIGH_PRIO();
@@ -374,6 +377,63 @@ struct B3Loader {
 // cycles in [0] global-load issue, [1] LDS reads + MFMA block + split, [2] barrier after it, [3] LDS writes, [4] barrier after them
 __device__ unsigned long long g_gemm_b3_phase[7];      // [5] all shader cycles of the wave, [6] the same span in 100 MHz wall ticks
 
+// The unsplit epilogue of a 128 x 128 split-bf16 tile whose first element is (m0, n0): wave (wm, wn) holds 2 x 2 accumulators of 32 x 32.
+// One function for gemm_b3_body and gemm_b3r_kernel, so that both round alike.
+__device__ __forceinline__ void b3_tile_epilogue(const GemmParams& p, const f32x16 (&acc)[2][2], int batch, int m0, int n0, int wm, int wn, int lane) {
+    const int r = lane & 31;
+    float* C = p.C + (long)batch * p.sC;
+    const float* R = p.R ? p.R + (long)batch * p.sR : nullptr;
+    if (!p.gate && !R) {
+        // Nothing is read per element (every input gradient and weight gradient without a residual): the 64 stores of a thread go out back to
+        // back.  In the general loop below each element's loads sit under that element's bounds test, so the compiler waits vmcnt(0) in every
+        // element -- which also waits for the store of the element before it: 64 store round trips in a row per tile.  Same expression per
+        // element as below (the gate factor there is 1.f): the same bits.
+        float bv[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = n0 + wn * 64 + j * 32 + r;
+            bv[j] = (p.bias && n < p.N) ? p.bias[n] : 0.f;
+        }
+        // a use of the bias in straight-line code: its load is waited for here, once, and not again under every element's bounds test
+        asm volatile("" : "+v"(bv[0]), "+v"(bv[1]));
+        auto store_all = [&](auto plain) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int n = n0 + wn * 64 + j * 32 + r;
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const int m = m0 + wm * 64 + i * 32 + mfma_row(q, lane);
+                        if (m < p.M && n < p.N) C[(long)m * p.ldc + n] = apply_act(p.alpha * acc[i][j][q] + bv[j], decltype(plain)::value ? 0 : p.act);
+                    }
+                }
+        };
+        if (p.act == 0) store_all(std::true_type{});
+        else store_all(std::false_type{});
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = n0 + wn * 64 + j * 32 + r;
+            const float bv = (p.bias && n < p.N) ? p.bias[n] : 0.f;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int m = m0 + wm * 64 + i * 32 + mfma_row(q, lane);
+                if (m < p.M && n < p.N) {
+                    float v = apply_act(p.alpha * acc[i][j][q] + bv, p.act);
+                    const float gsel = p.gate ? (p.gate[(long)batch * p.sG + (long)m * p.ldg + n] > 0.f ? p.gate_scale : 0.f) : 1.f;
+                    if (!p.gate_after) v *= gsel;
+                    if (R) v += R[(long)m * p.ldr + n];
+                    if (p.gate_after) v *= gsel;
+                    C[(long)m * p.ldc + n] = v;
+                }
+            }
+        }
+}
+
 template <int LAYOUT, bool PROBE>
 __device__ __forceinline__ void gemm_b3_body(const GemmParams& p) {
     BBBP_HIGH_PRIO();
@@ -539,33 +599,139 @@ __device__ __forceinline__ void gemm_b3_body(const GemmParams& p) {
         }
         return;
     }
-    float* C = p.C + (long)batch * p.sC;
-    const float* R = p.R ? p.R + (long)batch * p.sR : nullptr;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n = n0 + wn * 64 + j * 32 + r;
-            const float bv = (p.bias && n < p.N) ? p.bias[n] : 0.f;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int m = m0 + wm * 64 + i * 32 + mfma_row(q, lane);
-                if (m < p.M && n < p.N) {
-                    float v = apply_act(p.alpha * acc[i][j][q] + bv, p.act);
-                    const float gsel = p.gate ? (p.gate[(long)batch * p.sG + (long)m * p.ldg + n] > 0.f ? p.gate_scale : 0.f) : 1.f;
-                    if (!p.gate_after) v *= gsel;
-                    if (R) v += R[(long)m * p.ldr + n];
-                    if (p.gate_after) v *= gsel;
-                    C[(long)m * p.ldc + n] = v;
-                }
-            }
-        }
+    b3_tile_epilogue(p, acc, batch, m0, n0, wm, wn, lane);
 }
 
 template <int LAYOUT>
 __global__ __launch_bounds__(256, 2) void gemm_b3_kernel(GemmParams p) { gemm_b3_body<LAYOUT, false>(p); }
 template <int LAYOUT>
 __global__ __launch_bounds__(256, 2) void gemm_b3_probe_kernel(GemmParams p) { gemm_b3_body<LAYOUT, true>(p); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Weight-resident short-K NN form (GemmKernel::B3Resident): C[M][N] = A[M][K] B[K][N] with K <= 128 -- the image FC's input gradient,
+// dpool2[B][65536] = dcomb[:, 128:256] W[128][65536].  On gemm_b3_kernel<1> that product is cdiv(M, 128) x N / 128 tiles of four 32-deep
+// stages: every work-group pays a prologue of two load round trips and an epilogue, and the SAME 128 x 128 block of B is fetched, cut into
+// its three bf16 pieces and written to LDS once per row tile.  Here a work-group owns one 128-column block of B for ALL row tiles of A:
+//   * prologue: the block's whole K extent is loaded and split once (B3Loader<true>, stage by stage) and stays in LDS as
+//     [plane 3][column 128][128 k + 8] bf16 = 102 KB; the 272-byte row stride keeps the lane (r, h) fragment read (one ds_read_b128 per plane,
+//     k = 32 s + 16 kk + 8 h) and the loader's 8-byte k-quad writes (rows 4 apart) free of bank conflicts, as the 80-byte stride does for A;
+//   * main loop over (row tile, k stage): only A is streamed, exactly as gemm_b3_body streams it -- one 30 KB LDS stage, global loads two
+//     stages ahead in two float32 register sets, the split of the next stage under the MFMAs of this one, two barriers per stage.  The
+//     stream does not stop at a row tile's end: the first two stages of tile i + 1 are in flight during the last MFMAs and the stores of
+//     tile i, so a tile boundary costs the stores, not a load round trip;
+//   * per output element the same k stages in the same order, the same six piece products in the same order and b3_tile_epilogue: the bits
+//     of gemm_b3_kernel<1>.
+// LDS 132 KB: one work-group (four waves, up to 512 registers each) per CU; grid = N / 128 column blocks.  The plan requires K % 32 == 0,
+// K <= 128, N % 128 == 0 and batch == 1; rows past M are clamped by the loader and masked by the epilogue.
+constexpr int B3R_LD = 128 + 8;
+constexpr int B3R_PLANE = 128 * B3R_LD;
+constexpr size_t B3R_LDS = (size_t)3 * (B3R_PLANE + B3_PLANE) * sizeof(uint16_t);
+
+__global__ __launch_bounds__(256, 1) void gemm_b3r_kernel(GemmParams p) {
+    BBBP_HIGH_PRIO();
+    extern __shared__ __attribute__((aligned(16))) uint16_t smem16[];
+    uint16_t* Bs = smem16;
+    uint16_t* As = smem16 + 3 * B3R_PLANE;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int n0 = blockIdx.x * 128;
+    const int nt = p.K / B3_BK;                          // 1 .. 4 stages per row tile
+    const int stages = nt * ((p.M + 127) / 128);         // of the whole A stream
+
+    B3Loader<false> la;
+    int ld_s = 0, ld_m0 = 0;                             // the next stage to fetch: its index inside its row tile, the tile's first row
+    la.init(p.A, p.lda, p.M, 0, 0, p.K, t);
+    auto load_a = [&](int set) __attribute__((always_inline)) {
+        if (ld_s == nt) { ld_s = 0; ld_m0 += 128; la.init(p.A, p.lda, p.M, ld_m0, 0, p.K, t); }      // wave-uniform
+        la.load(set);
+        ++ld_s;
+    };
+    load_a(0);
+    if (stages > 1) load_a(1);
+    {
+        B3Loader<true> lb;
+        lb.init(p.B, p.ldb, p.N, n0, 0, p.K, t);
+        const int kq = t & 7, rq = t >> 3;
+        lb.load(0);
+        if (nt > 1) lb.load(1);
+#pragma unroll
+        for (int s = 0; s < 128 / B3_BK; ++s) {
+            if (s >= nt) break;
+            lb.split(s & 1);
+            if (s + 2 < nt) lb.load(s & 1);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl)
+                    *reinterpret_cast<u32x2*>(Bs + pl * B3R_PLANE + (4 * rq + i) * B3R_LD + s * B3_BK + 4 * kq) = lb.pk[i][pl];
+        }
+    }
+    la.split(0);
+    la.store(As);
+    __syncthreads();
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+    const uint16_t* afrag = As + (wm * 64 + r) * B3_LD + 8 * h;
+    const uint16_t* bfrag = Bs + (wn * 64 + r) * B3R_LD + 8 * h;
+    int s = 0, m0 = 0;                                   // the stage being multiplied: its index inside its row tile, the tile's first row
+    for (int g0 = 0; g0 < stages; g0 += 2) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int g = g0 + u;
+            if (g >= stages) break;
+            // float32 set u held stage g (split one stage ago): refill it with stage g + 2, which may belong to the next row tile
+            if (g + 2 < stages) load_a(u);
+#pragma unroll
+            for (int kk = 0; kk < B3_BK / 16; ++kk) {
+                bf16x8 a[2][3], b[2][3];
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) {
+                        a[i][pl] = *reinterpret_cast<const bf16x8*>(afrag + pl * B3_PLANE + i * 32 * B3_LD + kk * 16);
+                        b[i][pl] = *reinterpret_cast<const bf16x8*>(bfrag + pl * B3R_PLANE + i * 32 * B3R_LD + s * B3_BK + kk * 16);
+                    }
+                // the order of gemm_b3_body: smallest piece products first, the four tiles interleaved
+                constexpr int PA[6] = {1, 2, 0, 1, 0, 0}, PB[6] = {1, 0, 2, 0, 1, 0};
+#pragma unroll
+                for (int q = 0; q < 6; ++q)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][PA[q]], b[j][PB[q]], acc[i][j], 0, 0, 0);
+            }
+            // stage g + 1 of A -> bf16 pieces, in registers, under the MFMAs (unconditional: after the last stage it chews on stale registers)
+            la.split(u ^ 1);
+#pragma unroll
+            for (int q = 0; q < 48; ++q) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA ...
+                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);      // ... two VALU instructions of the split (half of gemm_b3_body's) under it
+            }
+            __syncthreads();                             // every wave is done reading this stage of A
+            if (g + 1 < stages) la.store(As);
+            if (s == nt - 1) {                           // the row tile is complete: out it goes while the next tile's loads are in flight
+                b3_tile_epilogue(p, acc, 0, m0, n0, wm, wn, lane);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+                s = 0; m0 += 128;
+            } else {
+                ++s;
+            }
+            __syncthreads();
+        }
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 64 x 64 tiles of the same split-bf16 form (round 3): products with a deep K whose output has too few 128 x 128 tiles to fill the chip
@@ -1340,6 +1506,11 @@ struct GemmKnobs {
     int short_k, short_tiles;      // BBBP_GEMM_SHORT_K / _SHORT_TILES: the 16-deep 128 x 128 form serves K <= short_k over >= short_tiles tiles per CU
     int reduce_vec4;     // BBBP_GEMM_REDUCE_VEC4: the float4 form of the split-K reduce kernel where alignment allows
     int b3_probe;        // BBBP_GEMM_B3_PROBE: the phase-stamping build of the split-bf16 kernel (bbbp_gemm_split_bf16_phases)
+    // BBBP_GEMM_B_RESIDENT: the weight-resident form (gemm_b3r_kernel) for NN products with K <= 128, K % 32 == 0, N % 128 == 0, M >= 256 and
+    // batch == 1.  Bit 0 (default): the form itself, where the N / 128 column blocks cover every CU.  Bit 1 (A/B runs and tests): products of
+    // that description take the 128 x 128 split-bf16 plan whatever their size.  So 0 is the plan without the form, 2 is gemm_b3_kernel<1>
+    // and 3 is gemm_b3r_kernel on every such product: same bits, two kernels.
+    int b_resident;
     int split_bf16;      // BBBP_GEMM_SPLIT_BF16 / bbbp_set_gemm_split_bf16
     int fold_reduce;     // BBBP_GEMM_FOLD_REDUCE / bbbp_set_gemm_fold_reduce: default off, measured slower, see DESIGN.md section 3
 };
@@ -1349,7 +1520,7 @@ GemmKnobs gemm_knobs() {
     static const GemmKnobs env{bbbp_env_int("BBBP_GEMM_DIRECT", 1), bbbp_env_int("BBBP_GEMM_DIRECT_KS", 2), bbbp_env_int("BBBP_GEMM_DIRECT_T", 2),
                                bbbp_env_int("BBBP_GEMM_B3_SMALL", 1), bbbp_env_int("BBBP_GEMM_TALL_B3", 1), bbbp_env_int("BBBP_GEMM_SPLIT_X10", 20),
                                bbbp_env_int("BBBP_GEMM_SPLIT_FULL", 0), bbbp_env_int("BBBP_GEMM_SHORT_K", 256), bbbp_env_int("BBBP_GEMM_SHORT_TILES", 4),
-                               bbbp_env_int("BBBP_GEMM_REDUCE_VEC4", 1), bbbp_env_int("BBBP_GEMM_B3_PROBE", 0), 0, 0};
+                               bbbp_env_int("BBBP_GEMM_REDUCE_VEC4", 1), bbbp_env_int("BBBP_GEMM_B3_PROBE", 0), bbbp_env_int("BBBP_GEMM_B_RESIDENT", 1), 0, 0};
     GemmKnobs k = env;
     k.split_bf16 = g_gemm_b3.get();
     k.fold_reduce = g_gemm_fold_reduce.get();
@@ -1394,13 +1565,14 @@ struct GemmProblem {
     bool quad_epilogue = false;    // C, bias, residual, gate and the slab are 16-byte aligned with strides that are multiples of 4
 };
 
-enum class GemmKernel {
-    Direct,               // gemm_direct_kernel: no LDS staging, 16x16 / 32x32 wave tiles, K slices reduced inside the work-group
-    B3Small,              // gemm_b3s_kernel: 64 x 64 split-bf16 tile, the whole K in one launch
-    B3,                   // gemm_b3_kernel: 128 x 128 split-bf16 tile
-    F32Tile128,           // gemm_f32_kernel<128, 128>
-    F32Tile128ShortK,     // gemm_f32_kernel<128, 128, ., true, 16>: four work-groups per CU
-    F32Tile64             // gemm_f32_kernel<64, 64>
+enum class GemmKernel {      // the values are what bbbp_gemm_kernel_form reports (include/bbbp_hip.h)
+    Direct = 0,               // gemm_direct_kernel: no LDS staging, 16x16 / 32x32 wave tiles, K slices reduced inside the work-group
+    B3Small = 1,              // gemm_b3s_kernel: 64 x 64 split-bf16 tile, the whole K in one launch
+    B3 = 2,                   // gemm_b3_kernel: 128 x 128 split-bf16 tile
+    F32Tile128 = 3,           // gemm_f32_kernel<128, 128>
+    F32Tile128ShortK = 4,     // gemm_f32_kernel<128, 128, ., true, 16>: four work-groups per CU
+    F32Tile64 = 5,            // gemm_f32_kernel<64, 64>
+    B3Resident = 6            // gemm_b3r_kernel: one 128-column block of B resident in LDS per work-group, every row tile of A streamed past it
 };
 struct GemmPlan {
     GemmKernel kernel = GemmKernel::F32Tile64;
@@ -1418,8 +1590,11 @@ struct GemmPlan {
 GemmPlan gemm_plan(const GemmProblem& pr, int ncu, const GemmKnobs& kn, bool split_k = true) {
     const int M = pr.M, N = pr.N, K = pr.K, batch = pr.batch;
     GemmPlan pl;
+    // GemmKnobs::b_resident: a k-major B of at most four whole stages in whole column blocks, under at least two row tiles to share its split
+    const bool resident_shape = pr.layout == 1 && kn.split_bf16 && K >= B3_BK && K <= 128 && K % B3_BK == 0 && N % 128 == 0 && M >= 256 && batch == 1;
+    const bool resident_any_size = resident_shape && (kn.b_resident & 2);
     // ---- the direct path serves launches that cannot fill the chip with 64x64 tiles anyway; big GEMMs keep the LDS tiling ----
-    if (kn.direct && 2.0 * M * N * (double)K * batch <= 1.2e9 && K <= 8192) {
+    if (kn.direct && !resident_any_size && 2.0 * M * N * (double)K * batch <= 1.2e9 && K <= 8192) {
         const int nch = cdiv(K, 16);
         pl.ks = nch <= 12 ? 1 : (cdiv(nch, 8) < kn.direct_ks ? cdiv(nch, 8) : kn.direct_ks);
         if (pl.ks == 3) pl.ks = 4;
@@ -1451,6 +1626,7 @@ GemmPlan gemm_plan(const GemmProblem& pr, int ncu, const GemmKnobs& kn, bool spl
     // Deep K with a large, 128-divisible output (the F = 2048 encoder's FFN / projection GEMMs): same argument.
     if (K >= 512 && M >= 256 && N >= 256 && covered * 100 <= (long)M * N * 115) pl.tile = 128;
     if (kn.tall_b3 && K >= 1024 && M >= 1024 && N >= 128 && covered * 10 <= (long)M * N * 16) pl.tile = 128;      // GemmKnobs::tall_b3
+    if (resident_any_size) pl.tile = 128;
     // ---- split-K.  Few output tiles and a deep K (weight gradients over the batch, the 65536-wide image FC, FFN2): these
     // launches are latency-bound at one work-group per tile, so spread K over ~2 work-groups per CU. ----
     const long tiles = pl.tile == 128 ? t128 : t64;
@@ -1481,6 +1657,9 @@ GemmPlan gemm_plan(const GemmProblem& pr, int ncu, const GemmKnobs& kn, bool spl
         pl.splits = 1; pl.kchunk = cdiv(K, B3_BK) * B3_BK;
         pl.gx = cdiv(N, B3S_T); pl.gy = cdiv(M, B3S_T); pl.gz = batch;
         pl.slab_bytes = 0; pl.reduce = pl.reduce_vec4 = false;
+    } else if (b3 && resident_shape && (kn.b_resident & 1) && (resident_any_size || N / 128 >= ncu)) {
+        pl.kernel = GemmKernel::B3Resident;      // K <= 128: never split
+        pl.gx = N / 128; pl.gy = 1; pl.gz = 1;
     } else if (b3) {
         pl.kernel = GemmKernel::B3;
         pl.in_kernel_reduce = kn.fold_reduce && pl.splits > 1 && (long)pl.gx * pl.gy * batch <= ARRIVAL_REGION;
@@ -1636,6 +1815,9 @@ int gemm_run(hipStream_t st, const bbbp_gemm_desc& g, void* workspace, size_t wo
         if (pl.in_kernel_reduce) p.arrivals = arrival_counters(st);
         with_constant<0, 1, 2>(pr.layout, [&](auto L) { rc = launch_b3<CONST_OF(L)>(p, grid, kn.b3_probe != 0, st); });
         break;
+    case GemmKernel::B3Resident:
+        rc = launch_lds(gemm_b3r_kernel, grid, 256, B3R_LDS, st, p);
+        break;
     case GemmKernel::F32Tile128ShortK:
         with_constant<0, 1, 2>(pr.layout, [&](auto L) { launch_f32_tile<128, 128, CONST_OF(L), true, 16>(p, grid, st); });
         break;
@@ -1670,6 +1852,12 @@ extern "C" int bbbp_gemm_folds_asum(int M, int N, int K, int batch) {
 // shapes that a known NT / NN layout puts on the 64 x 64 split-bf16 tile, which never touches them.  Callers size their scratch by this.
 extern "C" size_t bbbp_gemm_workspace_bytes(int M, int N, int K, int batch) {
     return (M <= 0 || N <= 0) ? 0 : gemm_plan_any_layout(M, N, K, batch).slab_bytes;
+}
+
+extern "C" int bbbp_gemm_kernel_form(int transA, int transB, int M, int N, int K, int batch) {
+    if (M <= 0 || N <= 0 || K <= 0 || batch < 1 || (transA && transB)) return -1;
+    const GemmProblem pr{M, N, K, batch, transA ? 2 : (transB ? 0 : 1)};
+    return (int)gemm_plan(pr, bbbp_num_cus(), gemm_knobs()).kernel;
 }
 
 extern "C" int bbbp_gemm_f32(void* stream, int transA, int transB, int M, int N, int K, float alpha,

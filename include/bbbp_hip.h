@@ -79,6 +79,11 @@ int bbbp_gemm_folds_asum(int M, int N, int K, int batch);
  * together -- dV | dP and dQ | dK of the attention backward -- go out as ONE launch when both are small; anything
  * else runs back to back on `stream`.  Results are identical to `count` bbbp_gemm_f32 calls. */
 int bbbp_gemm_f32_grouped(void* stream, const bbbp_gemm_desc* problems, int count, void* workspace, size_t workspace_bytes);
+/* Which kernel family a product of this layout and shape runs on, under the process's BBBP_GEMM_* settings (host side, no GPU work):
+ * 0 small-product path, 1 64 x 64 split-bf16 tile, 2 128 x 128 split-bf16 tile, 3 128 x 128 f32 tile, 4 its short-K variant, 5 64 x 64 f32 tile,
+ * 6 weight-resident split-bf16 form (A B with K <= 128: one column block of B per work-group, every row tile of A streamed past it);
+ * -1 for sizes or a layout bbbp_gemm_f32 rejects.  For A/B scripts and tests; a caller never needs it to run a product. */
+int bbbp_gemm_kernel_form(int transA, int transB, int M, int N, int K, int batch);
 
 /* ---- Conv2d(k3,s1,p1) + ReLU + MaxPool2d(2,2), NCHW ------------------------------------------
  * forward: R:85-87 (3->32, 128x128) and R:88-90 (32->64, 64x64).  y is the pooled output,
