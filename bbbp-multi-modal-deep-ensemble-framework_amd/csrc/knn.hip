@@ -5,10 +5,9 @@
 //   bbbp_knn_vote       class probabilities and the arg-max class from a prefix of the neighbour lists (uniform or 1 / distance weights).
 //
 // Search.  One work-group owns 64 queries and walks a contiguous slice of the training rows in tiles of 64.  Per tile the Gram block
-// (Q - mu)(T - mu)^T runs on v_mfma_f64_16x16x4_f64 with the staging scheme of pca_gemm_kernel (pca.hip): k in chunks of 16 through two
-// LDS buffers, chunk c + 1 in flight while chunk c multiplies, conversion to float64 and the shift once at staging, LDS rows of 18, clamped
-// loads for ragged m / n / d.  The shift matters: s = |q|^2 + |t|^2 - 2 q.t cancels against the squared norms, so the expansion runs on
-// centred rows, whose norms are of the order of the distances.
+// (Q - mu)(T - mu)^T is one f64_tile_product (f64_tile.h: v_mfma_f64_16x16x4_f64, the staging pipeline, the shift subtracted at staging,
+// clamped loads for ragged m / n / d).  The shift matters: s = |q|^2 + |t|^2 - 2 q.t cancels against the squared norms, so the expansion
+// runs on centred rows, whose norms are of the order of the distances.
 // Selection.  Every query keeps its k best (s, index) sorted in LDS ([slot][query]: the 64 lanes of the inserting wave touch 64
 // consecutive words).  The total order is "smaller s, then smaller training index".  In the tile epilogue each thread compares its 16
 // accumulator elements with the k-th entry of their query (one compare in the common case); survivors go to a 64 x 65 tile that reuses
@@ -21,22 +20,15 @@
 // Refine.  One wave per query recomputes the squared distance of the k kept rows by direct differences sum_k (q_k - t_k)^2 (lane l sums
 // k = l, l + 64, ..., then a fixed butterfly), sorts by (distance, index) and writes sqrt: a duplicate of the query gets exactly 0.0 and
 // returned distances carry a relative error, not the expansion's absolute one.
-#include "common.h"
-#include "bbbp_hip.h"
+#include "f64_tile.h"
 #include <math.h>
 
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int KT = 64;           // queries per work-group, training rows per tile
-constexpr int KC = 16;           // k per staged chunk
-constexpr int KS = KC + 2;       // LDS row length in doubles
-constexpr int KTHREADS = 256;
-constexpr int KPER = KT * KC / KTHREADS;     // elements per thread per operand per chunk (4)
 constexpr int KMAX = 32;         // largest list
 constexpr int KSLICES = 64;      // largest slice count: one lane per slice in the merge
-constexpr int KTP = KT + 1;      // row length of the survivor tile
+constexpr int KTP = F64_TILE + 1;      // row length of the survivor tile
+static_assert(F64_TILE * KTP <= F64_TILE_LDS, "the survivor tile must fit in the staging buffers");
 constexpr int NO_INDEX = 0x7fffffff;
 
 // What one search looks like; the launcher and bbbp_knn_workspace_bytes both ask knn_plan.
@@ -51,12 +43,12 @@ struct KnnPlan {
 // search).  `forced` > 0 overrides (tests).
 KnnPlan knn_plan(int m, int n, int k, int ncu, int forced) {
     KnnPlan pl;
-    pl.tiles_q = cdiv(m, KT);
+    pl.tiles_q = cdiv(m, F64_TILE);
     int s = forced;
     if (s <= 0) {
         const long want = 2L * ncu / pl.tiles_q;
         s = (int)(want < 1 ? 1 : want);
-        if (s > n / (4 * KT)) s = n / (4 * KT);
+        if (s > n / (4 * F64_TILE)) s = n / (4 * F64_TILE);
         if (s > KSLICES) s = KSLICES;
         if (s < 1) s = 1;
     }
@@ -76,116 +68,47 @@ struct KnnParams {
     int exclude_self, tiles_q, slices, rows_per_slice;
 };
 
-template <bool F32>
-__device__ __forceinline__ double ld_elem(const void* p, long i) {
-    if (F32) return (double)static_cast<const float*>(p)[i];
-    return static_cast<const double*>(p)[i];
-}
-
 // (s, i) before (t, j) in the total order
 __device__ __forceinline__ bool before(double s, int i, double t, int j) { return s < t || (s == t && i < j); }
 
-// One operand's share of a chunk: thread t holds row t >> 2, k = 4 (t & 3) .. + 3; row and k clamped into the matrix.
-template <bool F32>
-__device__ __forceinline__ void fetch(const void* base, long ld, int row0, int extent, int k0, int K, double (&v)[KPER]) {
-    const int t = threadIdx.x;
-    const int r = row0 + (t >> 2), rc = r < extent ? r : extent - 1;
-#pragma unroll
-    for (int j = 0; j < KPER; ++j) {
-        const int k = k0 + KPER * (t & 3) + j, kc = k < K ? k : K - 1;
-        v[j] = ld_elem<F32>(base, (long)rc * ld + kc);
-    }
-}
-
-// registers -> LDS image [row][k], shift subtracted in float64, zero where k >= K
-__device__ __forceinline__ void stage(double* lds, const double (&v)[KPER], const double* shift, int k0, int K) {
-    const int t = threadIdx.x, lr = t >> 2;
-#pragma unroll
-    for (int j = 0; j < KPER; ++j) {
-        const int lk = KPER * (t & 3) + j, k = k0 + lk, kc = k < K ? k : K - 1;
-        const double s = shift ? shift[kc] : 0.0;
-        lds[lr * KS + lk] = (k < K) ? v[j] - s : 0.0;
-    }
-}
-
 template <bool QF32, bool TF32>
-__global__ __launch_bounds__(KTHREADS) void knn_search_kernel(KnnParams p) {
-    __shared__ double lds[2 * 2 * KT * KS];         // [buffer][operand][row][k]; between two tiles: the survivor tile [query][KTP]
-    __shared__ double best_s[KMAX * KT];            // [slot][query], sorted
-    __shared__ int best_i[KMAX * KT];
-    __shared__ unsigned survivors[KT * 2];          // [query][half]: bit c of half h = training row 32 h + c of the tile survived
+__global__ __launch_bounds__(F64_THREADS) void knn_search_kernel(KnnParams p) {
+    __shared__ double lds[F64_TILE_LDS];            // the staging buffers; between two tiles: the survivor tile [query][KTP]
+    __shared__ double best_s[KMAX * F64_TILE];      // [slot][query], sorted
+    __shared__ int best_i[KMAX * F64_TILE];
+    __shared__ unsigned survivors[F64_TILE * 2];    // [query][half]: bit c of half h = training row 32 h + c of the tile survived
     const int tq = blockIdx.x % p.tiles_q, slice = blockIdx.x / p.tiles_q;
-    const int m0 = tq * KT;
+    const int m0 = tq * F64_TILE;
     const int r0 = slice * p.rows_per_slice;
     const long rend = (long)r0 + p.rows_per_slice;
     const int r1 = rend < p.n ? (int)rend : p.n;      // an empty slice (r0 >= n) runs no tile and writes unfilled lists
-    const int nch = (p.d + KC - 1) / KC;
+    const int nch = max((p.d + F64_CHUNK - 1) / F64_CHUNK, 1);      // d > 0: never the product's empty-range exit
     const int k = p.k;
 
-    for (int i = threadIdx.x; i < KMAX * KT; i += KTHREADS) { best_s[i] = INFINITY; best_i[i] = NO_INDEX; }
-    if (threadIdx.x < KT * 2) survivors[threadIdx.x] = 0u;
+    for (int i = threadIdx.x; i < KMAX * F64_TILE; i += F64_THREADS) { best_s[i] = INFINITY; best_i[i] = NO_INDEX; }
+    if (threadIdx.x < F64_TILE * 2) survivors[threadIdx.x] = 0u;
     __syncthreads();
 
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-    const int q = lane & 15, kq = lane >> 4;
-    double* const L0 = lds;
-    double* const L1 = lds + 2 * KT * KS;
+    const F64Frag f;
 
-    for (int n0 = r0; n0 < r1; n0 += KT) {
+    for (int n0 = r0; n0 < r1; n0 += F64_TILE) {
         f64x4 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
-        double ra[KPER], rb[KPER];
-        fetch<QF32>(p.Q, p.ldq, m0, p.m, 0, p.d, ra);
-        fetch<TF32>(p.T, p.ldt, n0, p.n, 0, p.d, rb);
-        stage(L0, ra, p.mu, 0, p.d);
-        stage(L0 + KT * KS, rb, p.mu, 0, p.d);
-        __syncthreads();
-        for (int c = 0; c < nch; ++c) {
-            const bool more = c + 1 < nch;
-            if (more) {                              // chunk c + 1: global -> registers while chunk c's MFMAs run
-                fetch<QF32>(p.Q, p.ldq, m0, p.m, (c + 1) * KC, p.d, ra);
-                fetch<TF32>(p.T, p.ldt, n0, p.n, (c + 1) * KC, p.d, rb);
-            }
-            const double* As = (c & 1) ? L1 : L0;
-            const double* Bs = As + KT * KS;
-#pragma unroll
-            for (int kk = 0; kk < KC; kk += 4) {
-                double a[2], b[2];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) a[i] = As[(wm + 16 * i + q) * KS + kk + kq];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) b[j] = Bs[(wn + 16 * j + q) * KS + kk + kq];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-            }
-            if (more) {                              // the other buffer was last read before the barrier that ended chunk c - 1
-                double* nx = (c & 1) ? L0 : L1;
-                stage(nx, ra, p.mu, (c + 1) * KC, p.d);
-                stage(nx + KT * KS, rb, p.mu, (c + 1) * KC, p.d);
-            }
-            __syncthreads();
-        }
+        f64_tile_product<false, QF32, TF32>(lds, f, p.Q, p.ldq, m0, p.m, p.mu, p.T, p.ldt, n0, p.n, p.mu, p.d, 0, nch, acc);
 
-        // Tile epilogue.  C/D of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 reg.  Nobody reads the staging buffers any more
-        // (the barrier above): survivors go to lds as [query][KTP].
+        // Tile epilogue.  Nobody reads the staging buffers any more (the barrier that ends the product): survivors go to lds as
+        // [query][KTP].
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int lrow = wm + 16 * i + kq + 4 * r, row = m0 + lrow;
+                const int lrow = f.row(i, r), row = m0 + lrow;
                 if (row >= p.m) continue;
                 const double qn = p.q_norm[row];
-                const double thr_s = best_s[(k - 1) * KT + lrow];
-                const int thr_i = best_i[(k - 1) * KT + lrow];
+                const double thr_s = best_s[(k - 1) * F64_TILE + lrow];
+                const int thr_i = best_i[(k - 1) * F64_TILE + lrow];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const int lcol = wn + 16 * j + q, col = n0 + lcol;
+                    const int lcol = f.col(j), col = n0 + lcol;
                     if (col >= r1 || (p.exclude_self && col == row)) continue;
                     const double s = (qn + p.t_norm[col]) - 2.0 * acc[i][j][r];
                     if (!before(s, col, thr_s, thr_i)) continue;
@@ -194,7 +117,7 @@ __global__ __launch_bounds__(KTHREADS) void knn_search_kernel(KnnParams p) {
                 }
             }
         __syncthreads();
-        if (threadIdx.x < KT) {                      // wave 0: lane = query, insertion from the tail
+        if (threadIdx.x < F64_TILE) {                // wave 0: lane = query, insertion from the tail
             const int lrow = threadIdx.x;
             for (int h = 0; h < 2; ++h) {
                 unsigned bits = survivors[lrow * 2 + h];
@@ -204,29 +127,29 @@ __global__ __launch_bounds__(KTHREADS) void knn_search_kernel(KnnParams p) {
                     bits &= bits - 1;
                     const double s = lds[lrow * KTP + lcol];
                     const int col = n0 + lcol;
-                    if (!before(s, col, best_s[(k - 1) * KT + lrow], best_i[(k - 1) * KT + lrow])) continue;
+                    if (!before(s, col, best_s[(k - 1) * F64_TILE + lrow], best_i[(k - 1) * F64_TILE + lrow])) continue;
                     int j = k - 1;
-                    while (j > 0 && before(s, col, best_s[(j - 1) * KT + lrow], best_i[(j - 1) * KT + lrow])) {
-                        best_s[j * KT + lrow] = best_s[(j - 1) * KT + lrow];
-                        best_i[j * KT + lrow] = best_i[(j - 1) * KT + lrow];
+                    while (j > 0 && before(s, col, best_s[(j - 1) * F64_TILE + lrow], best_i[(j - 1) * F64_TILE + lrow])) {
+                        best_s[j * F64_TILE + lrow] = best_s[(j - 1) * F64_TILE + lrow];
+                        best_i[j * F64_TILE + lrow] = best_i[(j - 1) * F64_TILE + lrow];
                         --j;
                     }
-                    best_s[j * KT + lrow] = s;
-                    best_i[j * KT + lrow] = col;
+                    best_s[j * F64_TILE + lrow] = s;
+                    best_i[j * F64_TILE + lrow] = col;
                 }
             }
         }
         __syncthreads();                             // before the next tile stages over the survivor tile
     }
 
-    if (threadIdx.x < KT && m0 + threadIdx.x < p.m) {
+    if (threadIdx.x < F64_TILE && m0 + threadIdx.x < p.m) {
         const int lrow = threadIdx.x;
         const size_t row = (size_t)m0 + lrow;
         if (p.slices > 1) {
             const size_t o = ((size_t)slice * p.m + row) * k;
-            for (int j = 0; j < k; ++j) { p.part_s[o + j] = best_s[j * KT + lrow]; p.part_i[o + j] = best_i[j * KT + lrow]; }
+            for (int j = 0; j < k; ++j) { p.part_s[o + j] = best_s[j * F64_TILE + lrow]; p.part_i[o + j] = best_i[j * F64_TILE + lrow]; }
         } else {
-            for (int j = 0; j < k; ++j) { p.dist[row * k + j] = best_s[j * KT + lrow]; p.ind[row * k + j] = best_i[j * KT + lrow]; }
+            for (int j = 0; j < k; ++j) { p.dist[row * k + j] = best_s[j * F64_TILE + lrow]; p.ind[row * k + j] = best_i[j * F64_TILE + lrow]; }
         }
     }
 }
@@ -340,13 +263,11 @@ __global__ __launch_bounds__(256) void knn_vote_kernel(const double* dist, const
     pred[row] = arg;
 }
 
-bool dtype_ok(int t) { return t == BBBP_DTYPE_F32 || t == BBBP_DTYPE_F64; }
-
 // descriptor checks shared by the launcher and the workspace query (no pointer is dereferenced)
 int check_desc(const bbbp_knn_desc* d, bool need_pointers) {
     BBBP_CHECK_ARG(d != nullptr, "bbbp_knn_f64: null descriptor");
     BBBP_CHECK_ARG(d->m > 0 && d->n > 0 && d->d > 0, "bbbp_knn_f64: m, n, d must be positive (got %d, %d, %d)", d->m, d->n, d->d);
-    BBBP_CHECK_ARG(d->n <= 0x7fffffff - KT, "bbbp_knn_f64: n %d leaves no room for the last tile's indices", d->n);
+    BBBP_CHECK_ARG(d->n <= 0x7fffffff - F64_TILE, "bbbp_knn_f64: n %d leaves no room for the last tile's indices", d->n);
     BBBP_CHECK_ARG(d->k >= 1 && d->k <= KMAX, "bbbp_knn_f64: k %d outside [1, %d]", d->k, KMAX);
     const int avail = d->exclude_self ? d->n - 1 : d->n;
     BBBP_CHECK_ARG(d->k <= avail, "bbbp_knn_f64: k %d exceeds the %d training rows a query can be given", d->k, avail);
@@ -362,16 +283,6 @@ int check_desc(const bbbp_knn_desc* d, bool need_pointers) {
                            "bbbp_knn_f64: exclude_self needs Q = T with the same leading dimension and dtype");
     }
     return BBBP_OK;
-}
-
-typedef void (*KnnKernel)(KnnParams);
-KnnKernel pick_search(int qf32, int tf32) {
-    if (qf32) return tf32 ? knn_search_kernel<true, true> : knn_search_kernel<true, false>;
-    return tf32 ? knn_search_kernel<false, true> : knn_search_kernel<false, false>;
-}
-KnnKernel pick_refine(int qf32, int tf32) {
-    if (qf32) return tf32 ? knn_refine_kernel<true, true> : knn_refine_kernel<true, false>;
-    return tf32 ? knn_refine_kernel<false, true> : knn_refine_kernel<false, false>;
 }
 
 }  // namespace
@@ -399,15 +310,20 @@ extern "C" int bbbp_knn_f64(void* stream, const bbbp_knn_desc* d, void* workspac
     p.m = d->m; p.n = d->n; p.d = d->d; p.k = d->k;
     p.exclude_self = d->exclude_self ? 1 : 0;
     p.tiles_q = pl.tiles_q; p.slices = pl.slices; p.rows_per_slice = pl.rows_per_slice;
-    const int qf32 = d->q_dtype == BBBP_DTYPE_F32, tf32 = d->t_dtype == BBBP_DTYPE_F32;
+    void (*search)(KnnParams) = nullptr;
+    void (*refine)(KnnParams) = nullptr;
+    with_bools(d->q_dtype == BBBP_DTYPE_F32, d->t_dtype == BBBP_DTYPE_F32, [&](auto Q, auto T) {
+        search = knn_search_kernel<Q.value, T.value>;
+        refine = knn_refine_kernel<Q.value, T.value>;
+    });
     const unsigned per_wave = (unsigned)(((long)d->m + 3) / 4);
-    hipLaunchKernelGGL(pick_search(qf32, tf32), dim3((unsigned)(pl.tiles_q * pl.slices)), dim3(KTHREADS), 0, st, p);
+    hipLaunchKernelGGL(search, dim3((unsigned)(pl.tiles_q * pl.slices)), dim3(F64_THREADS), 0, st, p);
     BBBP_CHECK_LAUNCH();
     if (pl.slices > 1) {
         hipLaunchKernelGGL(knn_merge_kernel, dim3(per_wave), dim3(256), 0, st, p);
         BBBP_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(pick_refine(qf32, tf32), dim3(per_wave), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(refine, dim3(per_wave), dim3(256), 0, st, p);
     BBBP_CHECK_LAUNCH();
     return BBBP_OK;
 }

@@ -17,28 +17,24 @@ Out of scope: ``inverse_transform`` (a third operand layout), whitening, randomi
 """
 from __future__ import annotations
 
-import ctypes
 import numbers
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _dense, _lib
 
 MAX_SOLVE = 8192           # largest min(n, d) handed to the host eigen-solver
 _NT, _TN = 0, 1
-_DT = {torch.float32: 0, torch.float64: 1}
 
 
 def _gemm_f64c(layout, M, N, K, A, lda, B, ldb, out, a_shift=None, b_shift=None, row_scale=None, symmetric=False, split_k=0):
     """One ``bbbp_gemm_f64c`` launch on the current stream; ``out`` [M, N] contiguous float32 / float64."""
     p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    d = _lib.GemmF64cDesc(layout, M, N, K, A.data_ptr(), _DT[A.dtype], lda, B.data_ptr(), _DT[B.dtype], ldb,
-                          p(a_shift), p(b_shift), p(row_scale), out.data_ptr(), _DT[out.dtype], N, int(symmetric), int(split_k))
+    d = _lib.GemmF64cDesc(layout, M, N, K, A.data_ptr(), _dense.DT[A.dtype], lda, B.data_ptr(), _dense.DT[B.dtype], ldb,
+                          p(a_shift), p(b_shift), p(row_scale), out.data_ptr(), _dense.DT[out.dtype], N, int(symmetric), int(split_k))
     L = _lib.lib()
-    nbytes = L.bbbp_gemm_f64c_workspace_bytes(ctypes.byref(d))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device) if nbytes else None
-    _lib.check(L.bbbp_gemm_f64c(torch.cuda.current_stream().cuda_stream, ctypes.byref(d), p(ws), nbytes), "bbbp_gemm_f64c")
+    _dense.launch_with_workspace(L.bbbp_gemm_f64c_workspace_bytes, L.bbbp_gemm_f64c, d, out.device, "bbbp_gemm_f64c")
     return out
 
 
@@ -52,9 +48,8 @@ def gemm_f64c(A, B, *, layout="NT", a_shift=None, b_shift=None, row_scale=None, 
     for name, t in (("A", A), ("B", B)):
         if not (isinstance(t, torch.Tensor) and t.is_cuda):
             raise RuntimeError(f"gemm_f64c: {name} must be a CUDA (HIP) tensor; there is no CPU fallback")
-        if t.dtype not in _DT or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        if t.dtype not in _dense.DT or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
             raise RuntimeError(f"gemm_f64c: {name} must be a 2-D float32 / float64 tensor with unit inner stride")
-    ld = lambda t: max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]  # noqa: E731
     if layout == "NT":
         (M, K), (N, Kb) = A.shape, B.shape
     else:
@@ -67,7 +62,7 @@ def gemm_f64c(A, B, *, layout="NT", a_shift=None, b_shift=None, row_scale=None, 
             raise RuntimeError(f"gemm_f64c: {name} must be a contiguous CUDA float64 vector of length {want}")
     out = torch.empty((M, N), dtype=out_dtype, device=A.device)
     with torch.cuda.device(A.device):
-        return _gemm_f64c(_NT if layout == "NT" else _TN, M, N, K, A, ld(A), B, ld(B), out, a_shift, b_shift, row_scale, symmetric, split_k)
+        return _gemm_f64c(_NT if layout == "NT" else _TN, M, N, K, A, _dense.ld(A), B, _dense.ld(B), out, a_shift, b_shift, row_scale, symmetric, split_k)
 
 
 class PCA:
@@ -139,19 +134,7 @@ class PCA:
     # ---- input handling ---------------------------------------------------------------------------------------------
     def _to_device(self, X):
         """(device tensor [n, d] float32 / float64 with unit inner stride and dense rows, was_numpy)"""
-        was_numpy = not isinstance(X, torch.Tensor)
-        if was_numpy:
-            X = np.asarray(X)
-            if X.dtype not in (np.float32, np.float64):
-                X = X.astype(np.float64)
-            X = torch.from_numpy(np.ascontiguousarray(X))
-        elif not X.is_cuda:
-            raise RuntimeError(f"PCA: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
-        if X.dim() != 2:
-            raise ValueError(f"PCA: expected a 2-D [n, d] input, got shape {tuple(X.shape)}")
-        if X.dtype not in _DT:
-            X = X.to(torch.float64)
-        return X.to(self.device).contiguous(), was_numpy
+        return _dense.to_device_matrix(X, self.device, "PCA", allow_row_stride=False)
 
     # ---- fit --------------------------------------------------------------------------------------------------------
     def fit(self, X):
@@ -177,7 +160,7 @@ class PCA:
         L = _lib.lib()
         with torch.cuda.device(self.device):
             mean_d = torch.empty(d, dtype=torch.float64, device=self.device)
-            _lib.check(L.bbbp_pca_col_mean(torch.cuda.current_stream().cuda_stream, X.data_ptr(), _DT[X.dtype], n, d, d, mean_d.data_ptr()),
+            _lib.check(L.bbbp_pca_col_mean(_dense.stream(), X.data_ptr(), _dense.DT[X.dtype], n, d, d, mean_d.data_ptr()),
                        "bbbp_pca_col_mean")
             mean = mean_d.cpu().numpy()
             if not np.isfinite(mean).all():

@@ -19,22 +19,16 @@ one GPU.  There is no CPU path.
 """
 from __future__ import annotations
 
-import ctypes
 import numbers
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _dense, _lib
 
 MAX_NEIGHBORS = 32
 MAX_CLASSES = 32
-_DT = {torch.float32: 0, torch.float64: 1}
 _WEIGHTS = {"uniform": 0, "distance": 1}
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _check_k(k, what="n_neighbors"):
@@ -45,11 +39,6 @@ def _check_k(k, what="n_neighbors"):
     return int(k)
 
 
-def _ld(t):
-    """Leading dimension of a [n, d] tensor with unit inner stride."""
-    return max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
-
-
 def _vote(dist, ind, kk, labels, n_classes, weights):
     """``bbbp_knn_vote`` over the first ``kk`` columns of ``dist`` / ``ind`` [m, k]: (proba [m, n_classes] float64, pred [m] int32)."""
     m, k = dist.shape
@@ -57,7 +46,7 @@ def _vote(dist, ind, kk, labels, n_classes, weights):
     pred = torch.empty(m, dtype=torch.int32, device=dist.device)
     if m:
         with torch.cuda.device(dist.device):
-            _lib.check(_lib.lib().bbbp_knn_vote(_stream(), dist.data_ptr(), ind.data_ptr(), m, k, kk, labels.data_ptr(), labels.numel(), n_classes,
+            _lib.check(_lib.lib().bbbp_knn_vote(_dense.stream(), dist.data_ptr(), ind.data_ptr(), m, k, kk, labels.data_ptr(), labels.numel(), n_classes,
                                                 _WEIGHTS[weights], proba.data_ptr(), pred.data_ptr()), "bbbp_knn_vote")
     return proba, pred
 
@@ -79,30 +68,15 @@ class NearestNeighbors:
 
     # ---- input handling ---------------------------------------------------------------------------------------------
     def _to_device(self, X):
-        """(device tensor [n, d] float32 / float64 with unit inner stride -- a row / column slice of a larger matrix is used in place, anything
-        else is copied --, was_numpy)"""
-        was_numpy = not isinstance(X, torch.Tensor)
-        if was_numpy:
-            X = np.asarray(X)
-            if X.dtype not in (np.float32, np.float64):
-                X = X.astype(np.float64)
-            X = torch.from_numpy(np.ascontiguousarray(X))
-        elif not X.is_cuda:
-            raise RuntimeError(f"neighbors: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
-        if X.dim() != 2:
-            raise ValueError(f"neighbors: expected a 2-D [n, d] input, got shape {tuple(X.shape)}")
-        if X.dtype not in _DT:
-            X = X.to(torch.float64)
-        X = X.to(self.device)
-        in_place = (X.shape[1] == 1 or X.stride(1) == 1) and (X.shape[0] <= 1 or X.stride(0) >= X.shape[1])
-        return (X if in_place else X.contiguous()), was_numpy
+        """(device tensor [n, d] float32 / float64 with unit inner stride, a row / column slice of a larger matrix in place; was_numpy)"""
+        return _dense.to_device_matrix(X, self.device, "neighbors", allow_row_stride=True)
 
     def _norms(self, X, what):
         """Centred squared row norms of X (float64, device); ValueError when X holds NaN or infinity (one host read of the flag)."""
         n, d = X.shape
         norms = torch.empty(n, dtype=torch.float64, device=self.device)
         flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-        _lib.check(_lib.lib().bbbp_knn_row_norms(_stream(), X.data_ptr(), _DT[X.dtype], n, d, _ld(X), self._mean_d.data_ptr(), norms.data_ptr(),
+        _lib.check(_lib.lib().bbbp_knn_row_norms(_dense.stream(), X.data_ptr(), _dense.DT[X.dtype], n, d, _dense.ld(X), self._mean_d.data_ptr(), norms.data_ptr(),
                                                  flag.data_ptr()), "bbbp_knn_row_norms")
         if int(flag.item()):
             raise ValueError(f"neighbors: {what} contains NaN or infinity (or values whose squares overflow float64)")
@@ -118,7 +92,7 @@ class NearestNeighbors:
             self.__dict__.pop(name, None)
         with torch.cuda.device(self.device):
             self._mean_d = torch.empty(d, dtype=torch.float64, device=self.device)
-            _lib.check(_lib.lib().bbbp_pca_col_mean(_stream(), X.data_ptr(), _DT[X.dtype], n, d, _ld(X), self._mean_d.data_ptr()), "bbbp_pca_col_mean")
+            _lib.check(_lib.lib().bbbp_pca_col_mean(_dense.stream(), X.data_ptr(), _dense.DT[X.dtype], n, d, _dense.ld(X), self._mean_d.data_ptr()), "bbbp_pca_col_mean")
             try:
                 self._norms_d = self._norms(X, "the training set")
             except ValueError:
@@ -151,12 +125,11 @@ class NearestNeighbors:
             if m == 0:
                 return dist, ind
             qn = self._norms_d if exclude else self._norms(Q, "the query set")
-            desc = _lib.KnnDesc(m, n, d, k, Q.data_ptr(), _DT[Q.dtype], _ld(Q), self._X.data_ptr(), _DT[self._X.dtype], _ld(self._X), self._mean_d.data_ptr(),
-                                qn.data_ptr(), self._norms_d.data_ptr(), dist.data_ptr(), ind.data_ptr(), int(exclude), int(slices))
+            desc = _lib.KnnDesc(m, n, d, k, Q.data_ptr(), _dense.DT[Q.dtype], _dense.ld(Q), self._X.data_ptr(), _dense.DT[self._X.dtype],
+                                _dense.ld(self._X), self._mean_d.data_ptr(), qn.data_ptr(), self._norms_d.data_ptr(), dist.data_ptr(),
+                                ind.data_ptr(), int(exclude), int(slices))
             L = _lib.lib()
-            nbytes = L.bbbp_knn_workspace_bytes(ctypes.byref(desc))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if nbytes else None
-            _lib.check(L.bbbp_knn_f64(_stream(), ctypes.byref(desc), None if ws is None else ws.data_ptr(), nbytes), "bbbp_knn_f64")
+            _dense.launch_with_workspace(L.bbbp_knn_workspace_bytes, L.bbbp_knn_f64, desc, self.device, "bbbp_knn_f64")
         return dist, ind
 
     def kneighbors(self, X=None, n_neighbors=None, return_distance=True, *, slices=0):
