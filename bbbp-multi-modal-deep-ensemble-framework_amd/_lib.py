@@ -66,6 +66,26 @@ class KnnDesc(Structure):
                 ("exclude_self", c_int), ("slices", c_int)]
 
 
+class SvmKernelDesc(Structure):
+    """bbbp_svm_kernel_desc (include/bbbp_hip.h)."""
+    _fields_ = [("n", c_int), ("d", c_int), ("kernel", c_int), ("gamma", c_double),
+                ("X", c_void_p), ("x_dtype", c_int), ("ldx", c_long), ("mu", c_void_p), ("norms", c_void_p), ("K", c_void_p), ("ldk", c_long)]
+
+
+class SvmProblem(Structure):
+    """bbbp_svm_problem (include/bbbp_hip.h)."""
+    _fields_ = [("K", c_void_p), ("ldk", c_long), ("rows", c_void_p), ("y", c_void_p), ("alpha", c_void_p), ("grad", c_void_p), ("diag", c_void_p),
+                ("rho", c_void_p), ("n_iter", c_void_p), ("done", c_void_p), ("n", c_int), ("C", c_double), ("tol", c_double)]
+
+
+class SvmDecisionDesc(Structure):
+    """bbbp_svm_decision_desc (include/bbbp_hip.h)."""
+    _fields_ = [("m", c_int), ("n_sv", c_int), ("d", c_int), ("kernel", c_int), ("gamma", c_double),
+                ("Q", c_void_p), ("q_dtype", c_int), ("ldq", c_long), ("SV", c_void_p), ("sv_dtype", c_int), ("ldsv", c_long),
+                ("mu", c_void_p), ("q_norm", c_void_p), ("sv_norm", c_void_p), ("coef", c_void_p), ("intercept", c_double), ("out", c_void_p),
+                ("slices", c_int)]
+
+
 _FP = c_void_p          # device float*
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -115,6 +135,10 @@ _SIGNATURES = {
     "bbbp_knn_workspace_bytes": (c_size_t, [POINTER(KnnDesc)]),
     "bbbp_knn_f64": (c_int, [c_void_p, POINTER(KnnDesc), c_void_p, c_size_t]),
     "bbbp_knn_vote": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
+    "bbbp_svm_kernel_matrix": (c_int, [c_void_p, POINTER(SvmKernelDesc)]),
+    "bbbp_svm_smo": (c_int, [c_void_p, POINTER(SvmProblem), c_int, c_int]),
+    "bbbp_svm_decision_workspace_bytes": (c_size_t, [POINTER(SvmDecisionDesc)]),
+    "bbbp_svm_decision": (c_int, [c_void_p, POINTER(SvmDecisionDesc), c_void_p, c_size_t]),
     "bbbp_graph_stats": (c_int, [POINTER(c_long), POINTER(c_long)]),
     "bbbp_conv_last_clock": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "bbbp_set_conv_winograd": (c_int, [c_int]),

@@ -442,6 +442,64 @@ int bbbp_knn_f64(void* stream, const bbbp_knn_desc* d, void* workspace, size_t w
 int bbbp_knn_vote(void* stream, const double* dist, const long long* ind, long m, int k, int kk, const int* labels, long n, int n_classes,
                   int weights, double* proba, int* pred);
 
+/* ---- svm: float64 kernel matrix, batched SMO solver and fused decision function (csrc/svm.hip) ---------------------------
+ * SVC() of the classification stack (Models/model_opt_maccs.py:124-180), searched over C in {0.1, 1, 10} x kernel in {linear, rbf}.
+ * bbbp_amd/svm.py composes SVC / grid_search_cv from these. */
+#define BBBP_SVM_LINEAR 0
+#define BBBP_SVM_RBF 1
+/* K[i][j] = sum_k X[i][k] X[j][k] (linear, uncentred: mu and norms are not read) or exp(-gamma |x_i - x_j|^2) (rbf), float64.
+ * rbf: the squared distance is |x_i - mu|^2 + |x_j - mu|^2 - 2 (x_i - mu).(x_j - mu), clamped at 0, with the inner product on the float64
+ * matrix pipe, the shift subtracted at staging and norms = the row-norm entry point of the neighbours section run on X with the same mu
+ * (which also flags non-finite input).  K is bitwise symmetric and the rbf diagonal is exactly 1. */
+typedef struct bbbp_svm_kernel_desc {
+    int n, d;
+    int kernel;                                /* BBBP_SVM_* */
+    double gamma;
+    const void* X; int x_dtype; long ldx;      /* [n][d], BBBP_DTYPE_* */
+    const double* mu;                          /* [d], nullable */
+    const double* norms;                       /* [n], rbf only */
+    double* K; long ldk;                       /* [n][ldk] */
+} bbbp_svm_kernel_desc;
+int bbbp_svm_kernel_matrix(void* stream, const bbbp_svm_kernel_desc* d);
+/* One C-SVC dual problem: min 1/2 a^T Q a - e^T a, 0 <= a <= C, y^T a = 0, Q[s][t] = y[s] y[t] K[r(s)][r(t)] with r = rows (NULL: the
+ * identity), so that a fold is a subset of one shared matrix; every entry of rows must index a row of K.  y holds +1.0 / -1.0.
+ * State: alpha and grad (start a problem with alpha = 0, grad = -1, *n_iter = 0, *done = 0); diag is scratch of n doubles.
+ * Outputs: *rho, *n_iter (iterations so far), *done (1 once m(alpha) - M(alpha) < tol). */
+typedef struct bbbp_svm_problem {
+    const double* K; long ldk;
+    const int* rows;                           /* [n], nullable */
+    const double* y;                           /* [n] */
+    double* alpha; double* grad; double* diag; /* [n] each */
+    double* rho; int* n_iter; int* done;
+    int n;
+    double C, tol;
+} bbbp_svm_problem;
+/* libsvm's solver without shrinking (second-order working-set selection, its clipping, tau = 1e-12, ties to the later index), one
+ * work-group per problem.  A launch runs at most `iters` iterations of every problem whose *done is 0 and returns: the caller reads the
+ * done flags and calls again with the unfinished problems.  `problems` is a host array.  A problem's result does not depend on the
+ * others in the batch and is bit-identical from call to call. */
+int bbbp_svm_smo(void* stream, const bbbp_svm_problem* problems, int n_problems, int iters);
+/* out[q] = sum_s coef[s] k(SV[s], Q[q]) + intercept, the kernel as above (rbf: q_norm / sv_norm are the row norms of Q / SV with the same mu).
+ * The kernel block is consumed in registers; one partial sum per (tile of 64 support vectors, query) goes to `workspace`
+ * (bbbp_svm_decision_workspace_bytes for the same descriptor) and a second launch adds them in tile order.  slices: 0 lets the plan choose
+ * how many work-groups share a query tile's support vectors, > 0 forces it (<= 64); the result does not depend on it. */
+typedef struct bbbp_svm_decision_desc {
+    int m, n_sv, d;
+    int kernel;
+    double gamma;
+    const void* Q; int q_dtype; long ldq;      /* [m][d] */
+    const void* SV; int sv_dtype; long ldsv;   /* [n_sv][d] */
+    const double* mu;                          /* [d], nullable */
+    const double* q_norm; const double* sv_norm;
+    const double* coef;                        /* [n_sv] */
+    double intercept;
+    double* out;                               /* [m] */
+    int slices;
+} bbbp_svm_decision_desc;
+/* 0 with a message in bbbp_last_error() for an invalid descriptor (pointers are not examined) */
+size_t bbbp_svm_decision_workspace_bytes(const bbbp_svm_decision_desc* d);
+int bbbp_svm_decision(void* stream, const bbbp_svm_decision_desc* d, void* workspace, size_t workspace_bytes);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
