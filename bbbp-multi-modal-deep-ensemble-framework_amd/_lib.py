@@ -86,6 +86,12 @@ class SvmDecisionDesc(Structure):
                 ("slices", c_int)]
 
 
+class LogregProblem(Structure):
+    """bbbp_logreg_problem (include/bbbp_hip.h)."""
+    _fields_ = [("X", c_void_p), ("x_dtype", c_int), ("ld", c_long), ("n", c_int), ("d", c_int), ("t", c_void_p), ("C", c_double), ("tol", c_double),
+                ("fit_intercept", c_int), ("max_iter", c_int), ("theta", c_void_p), ("trial", c_void_p), ("state", c_void_p), ("flags", c_void_p)]
+
+
 _FP = c_void_p          # device float*
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -139,6 +145,11 @@ _SIGNATURES = {
     "bbbp_svm_smo": (c_int, [c_void_p, POINTER(SvmProblem), c_int, c_int]),
     "bbbp_svm_decision_workspace_bytes": (c_size_t, [POINTER(SvmDecisionDesc)]),
     "bbbp_svm_decision": (c_int, [c_void_p, POINTER(SvmDecisionDesc), c_void_p, c_size_t]),
+    "bbbp_logreg_state_bytes": (c_size_t, [c_int, c_int]),
+    "bbbp_logreg_state_layout": (c_int, [c_int, c_int, POINTER(c_long)]),
+    "bbbp_logreg_rounds": (c_int, [c_void_p, POINTER(LogregProblem), c_int, c_int]),
+    "bbbp_logreg_eval": (c_int, [c_void_p, POINTER(LogregProblem)]),
+    "bbbp_logreg_decision": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_int, c_void_p]),
     "bbbp_graph_stats": (c_int, [POINTER(c_long), POINTER(c_long)]),
     "bbbp_conv_last_clock": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "bbbp_set_conv_winograd": (c_int, [c_int]),

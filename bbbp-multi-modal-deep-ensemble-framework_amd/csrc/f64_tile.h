@@ -1,4 +1,5 @@
-// The staged float64 tile product on v_mfma_f64_16x16x4_f64, shared by the centred GEMM (pca.hip) and the kNN search (knn.hip):
+// The staged float64 tile product on v_mfma_f64_16x16x4_f64, shared by the centred GEMM (pca.hip), the kNN search (knn.hip), the SVC kernel
+// matrix (svm.hip) and the weighted Gram matrix of the logistic regression (logreg.hip, which also scales A per k):
 //     acc[64 x 64] += sum_k (A(m,k) - sa) (B(n,k) - sb)     over the 16-wide k chunks [c0, c1)
 // Operands stream from HBM, float32 or float64, both k-contiguous (NT) or both k-major (TN).  A 64 x 64 work-group tile is run by four
 // waves of 32 x 32 (2 x 2 MFMA tiles: 32 accumulator registers).  K goes in chunks of 16 through two LDS buffers: chunk c + 1 travels
@@ -67,9 +68,12 @@ __device__ __forceinline__ void fetch(const void* base, long ld, int row0, int e
 }
 
 // registers -> LDS image [row][k], shift subtracted in float64, zero where k >= K.  The shift runs over the operand's rows (TN) or over
-// k (NT: row0 and extent are not used).
-template <bool TN>
-__device__ __forceinline__ void stage(double* lds, const double (&v)[F64_PER], const double* shift, int row0, int extent, int k0, int K) {
+// k (NT: row0 and extent are not used).  KSCALE (TN only): the shifted value is multiplied by kscale[k], one factor per k -- the weighted
+// Gram matrix X^T diag(w) X of logreg.hip.
+template <bool TN, bool KSCALE = false>
+__device__ __forceinline__ void stage(double* lds, const double (&v)[F64_PER], const double* shift, int row0, int extent, int k0, int K,
+                                      const double* kscale = nullptr) {
+    static_assert(TN || !KSCALE, "the per-k scale is staged in the TN form only");
     const int t = threadIdx.x;
     if (TN) {
         const int lr = t & 63, r = row0 + lr, rc = r < extent ? r : extent - 1;
@@ -77,7 +81,12 @@ __device__ __forceinline__ void stage(double* lds, const double (&v)[F64_PER], c
 #pragma unroll
         for (int j = 0; j < F64_PER; ++j) {
             const int lk = (t >> 6) + 4 * j;
-            lds[lr * F64_ROW + lk] = (k0 + lk < K) ? v[j] - s : 0.0;
+            if (KSCALE) {
+                const int k = k0 + lk, kc = k < K ? k : K - 1;
+                lds[lr * F64_ROW + lk] = (k < K) ? (v[j] - s) * kscale[kc] : 0.0;
+            } else {
+                lds[lr * F64_ROW + lk] = (k0 + lk < K) ? v[j] - s : 0.0;
+            }
         }
     } else {
         const int lr = t >> 2;
@@ -104,10 +113,11 @@ struct F64Frag {
 
 // acc = the tile product over chunks [c0, c1) (zero when the range is empty).  All 256 threads call it with their F64Frag; `lds` holds
 // F64_TILE_LDS doubles.  It returns behind the barrier that ends the last chunk: nobody reads `lds` any more and the caller may reuse it.
-template <bool TN, bool AF32, bool BF32>
+// AKSCALE: operand A is multiplied by a_kscale[k] (K doubles) after its shift; without it a_kscale is not read.
+template <bool TN, bool AF32, bool BF32, bool AKSCALE = false>
 __device__ __forceinline__ void f64_tile_product(double* lds, const F64Frag& f, const void* A, long lda, int a_row0, int a_extent, const double* a_shift,
                                                  const void* B, long ldb, int b_row0, int b_extent, const double* b_shift, int K, int c0,
-                                                 int c1, f64x4 (&acc)[2][2]) {
+                                                 int c1, f64x4 (&acc)[2][2], const double* a_kscale = nullptr) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -116,7 +126,7 @@ __device__ __forceinline__ void f64_tile_product(double* lds, const F64Frag& f, 
     double ra[F64_PER], rb[F64_PER];
     fetch<TN, AF32>(A, lda, a_row0, a_extent, c0 * F64_CHUNK, K, ra);
     fetch<TN, BF32>(B, ldb, b_row0, b_extent, c0 * F64_CHUNK, K, rb);
-    stage<TN>(lds, ra, a_shift, a_row0, a_extent, c0 * F64_CHUNK, K);
+    stage<TN, AKSCALE>(lds, ra, a_shift, a_row0, a_extent, c0 * F64_CHUNK, K, a_kscale);
     stage<TN>(lds + F64_OPERAND, rb, b_shift, b_row0, b_extent, c0 * F64_CHUNK, K);
     __syncthreads();
     for (int c = c0; c < c1; ++c) {
@@ -142,7 +152,7 @@ __device__ __forceinline__ void f64_tile_product(double* lds, const F64Frag& f, 
         }
         if (more) {                              // the other buffer was last read before the barrier that ended chunk c - 1
             double* nx = lds + (cur ^ 1) * (2 * F64_OPERAND);
-            stage<TN>(nx, ra, a_shift, a_row0, a_extent, (c + 1) * F64_CHUNK, K);
+            stage<TN, AKSCALE>(nx, ra, a_shift, a_row0, a_extent, (c + 1) * F64_CHUNK, K, a_kscale);
             stage<TN>(nx + F64_OPERAND, rb, b_shift, b_row0, b_extent, (c + 1) * F64_CHUNK, K);
         }
         __syncthreads();

@@ -500,6 +500,51 @@ typedef struct bbbp_svm_decision_desc {
 size_t bbbp_svm_decision_workspace_bytes(const bbbp_svm_decision_desc* d);
 int bbbp_svm_decision(void* stream, const bbbp_svm_decision_desc* d, void* workspace, size_t workspace_bytes);
 
+/* ---- logreg: batched float64 Newton solver for binary L2 logistic regression (csrc/logreg.hip) ------------------------------
+ * LogisticRegression(max_iter=1000) of the classification stack (Models/model_opt_maccs.py:124-180), searched over C in {0.1, 1, 10}.
+ * bbbp_amd/linear_model.py composes LogisticRegression / grid_search_cv from these.
+ * Objective (scikit-learn's scaling): f(w, b) = 1/n sum_i log(1 + exp(s_i)) + |w|^2 / (2 C n), s_i = -z_i for t_i = 1 and z_i for t_i = 0,
+ * z = X w + b; the intercept is not penalised; a problem is converged once max |grad f| <= tol.  theta = (w[0..d), b) holds d + 1 doubles
+ * whether or not the intercept is fitted (b stays 0 without it). */
+#define BBBP_LOGREG_MAX_D 255
+#define BBBP_LOGREG_RUNNING 0          /* *status while a problem is not done */
+#define BBBP_LOGREG_CONVERGED 0        /* *status once done: max |grad f| <= tol */
+#define BBBP_LOGREG_MAX_ITER 1         /* max_iter accepted steps taken */
+#define BBBP_LOGREG_LINE_SEARCH 2      /* 21 trial steps rejected */
+#define BBBP_LOGREG_PIVOT 3            /* a non-positive Cholesky pivot */
+typedef struct bbbp_logreg_problem {
+    const void* X; int x_dtype; long ld;       /* [n][d], BBBP_DTYPE_* */
+    int n, d;
+    const double* t;                           /* [n], 0.0 / 1.0 */
+    double C, tol;
+    int fit_intercept;
+    int max_iter;                              /* accepted Newton steps, >= 1 */
+    double* theta;                             /* [d + 1]: the last accepted point, the result */
+    double* trial;                             /* [d + 1]: the point the next round evaluates */
+    double* state;                             /* bbbp_logreg_state_bytes(n, d) bytes of solver state and partial sums */
+    int* flags;                                /* [4]: n_iter (accepted steps), status (BBBP_LOGREG_*), done, trials of the current line search */
+} bbbp_logreg_problem;
+/* Bytes of a problem's `state` (0 with a message for n < 1, d < 1 or d > BBBP_LOGREG_MAX_D).  It depends on n and d only, as does the
+ * order of every sum: a problem's numbers do not depend on what else is in the batch. */
+size_t bbbp_logreg_state_bytes(int n, int d);
+/* Offsets, in doubles, of what a round leaves in `state` for the trial point it evaluated: out[0] the loss f, out[1] the gradient [d + 1],
+ * out[2] z [n], out[3] the residual r = p - t [n], out[4] the curvature w [n], out[5] the Hessian's upper triangle packed by rows
+ * (row a holds columns a .. p - 1, p = d + fit_intercept; bbbp_logreg_eval only: the solver factors it in place). */
+int bbbp_logreg_state_layout(int n, int d, long out[6]);
+/* `rounds` rounds of the damped Newton iteration for every problem whose done flag is 0, all problems side by side: (1) the row pass --
+ * z, r, w and per-block partial sums of the loss, gradient and the Hessian's intercept row at `trial`; (2) the weighted Gram matrix
+ * X^T diag(w) X on the float64 matrix pipe, one triangle, in row slabs; (3) one work-group per problem sums the partials in fixed order,
+ * accepts or rejects the trial (scikit-learn's NewtonSolver rules: f' <= f + 2^-11 alpha g.s, or |f' - f| <= 16 eps |f| with a smaller
+ * 1-norm of the gradient; at most 21 halvings), tests convergence and max_iter, factors H by Cholesky, solves and writes the next trial.
+ * Start a problem with theta, trial, state and flags zeroed.  `problems` is a host array; the caller reads the done flags and calls again
+ * while any is 0. */
+int bbbp_logreg_rounds(void* stream, const bbbp_logreg_problem* problems, int n_problems, int rounds);
+/* One evaluation at `trial` with no step: loss, gradient, z, r, w and the packed Hessian in `state` (bbbp_logreg_state_layout). */
+int bbbp_logreg_eval(void* stream, const bbbp_logreg_problem* problem);
+/* out[q] = sum_k X[q][k] theta[k] + (fit_intercept ? theta[d] : 0): the row pass's dot product, so a training row's value is bitwise the
+ * one the solver saw. */
+int bbbp_logreg_decision(void* stream, const void* X, int x_dtype, long ld, int m, int d, const double* theta, int fit_intercept, double* out);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
