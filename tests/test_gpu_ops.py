@@ -229,15 +229,29 @@ def test_gemm_errors(dev):
     assert out.shape == (0, 6)
 
 
-def _conv_case(dev, B, cin, cout, hw, seed, uniform_patches=False):
+def _conv_inputs(B, cin, cout, hw, seed, uniform_patches=False):
     x = rnd(B, cin, hw, hw, seed=seed)
     if uniform_patches:        # flat regions => exact ties inside pooling windows (white image background)
         x[:, :, : hw // 2, :] = 1.0
     w = rnd(cout, cin, 3, 3, seed=seed + 1, scale=0.2)
     b = rnd(cout, seed=seed + 2, scale=0.1)
+    gy = rnd(B, cout, hw // 2, hw // 2, seed=seed + 3)
+    return x, w, b, gy
+
+
+def _conv_run(dev, x, w, b, gy):
+    """The device calls of _conv_case: forward, weight gradient and (cin != 3) data gradient.  Returns (y, mask, dw, db, dx or None)."""
+    y, mask = ops.conv3x3_relu_pool_fwd(x.to(dev), w.to(dev), b.to(dev))
+    dw, db = ops.conv3x3_relu_pool_bwd_weight(x.to(dev), gy.to(dev), mask)
+    dx = ops.conv3x3_relu_pool_bwd_data(gy.to(dev), mask, w.to(dev)) if x.shape[1] != 3 else None
+    return y, mask, dw, db, dx
+
+
+def _conv_case(dev, B, cin, cout, hw, seed, uniform_patches=False):
+    x, w, b, gy = _conv_inputs(B, cin, cout, hw, seed, uniform_patches)
     # float64 oracle: torch's own fp32 CPU weight-gradient carries ~2e-3 (of max) summation error at these sizes
     xr, wr, br = (t_.double().clone().requires_grad_(True) for t_ in (x, w, b))
-    y, mask = ops.conv3x3_relu_pool_fwd(x.to(dev), w.to(dev), b.to(dev))
+    y, mask, dw, db, dx = _conv_run(dev, x, w, b, gy)
     assert int(mask.max()) <= 4
     # The gradients are sums over POOLING DECISIONS (which of four pre-activations is the maximum; whether it is positive).  A window whose
     # two largest values agree to float32 rounding may legitimately route its gradient to either -- ONE such window moves 9 * cin entries of
@@ -258,15 +272,14 @@ def _conv_case(dev, B, cin, cout, hw, seed, uniform_patches=False):
         assert float(gap.max()) <= 1e-5 * float(pre[0].abs().mean()) + 1e-12, float(gap.max())
         assert float(differ.float().mean()) < 1e-4
     yr = oracle.conv3x3_relu_pool(xr, wr, br, pool_mask=m_cpu)
-    gy = rnd(*yr.shape, seed=seed + 3)
+    assert tuple(gy.shape) == tuple(yr.shape)
     yr.backward(gy.double())
     assert_close(y.cpu().numpy(), yr.detach().numpy(), rtol=1e-5, atol_frac=1e-6, what="conv fwd")
-    dw, db = ops.conv3x3_relu_pool_bwd_weight(x.to(dev), gy.to(dev), mask)
     assert_close(dw.cpu().numpy(), wr.grad.numpy(), rtol=1e-4, atol_frac=2e-5, what="conv dw")
     assert_close(db.cpu().numpy(), br.grad.numpy(), rtol=1e-4, atol_frac=2e-5, what="conv db")
     if cin != 3:
-        dx = ops.conv3x3_relu_pool_bwd_data(gy.to(dev), mask, w.to(dev))
         assert_close(dx.cpu().numpy(), xr.grad.numpy(), rtol=1e-4, atol_frac=2e-5, what="conv dx")
+    return y, mask, dw, db, dx
 
 
 @pytest.fixture(params=[0, 32, 96], ids=["f32", "split-bf16-wgrad", "split-bf16-fwd+wgrad"])
@@ -396,8 +409,7 @@ def test_conv_rejects_unsupported(dev):
         ops.conv3x3_relu_pool_fwd(torch.zeros(1, 5, 64, 64, device=dev), torch.zeros(8, 5, 3, 3, device=dev), torch.zeros(8, device=dev))
 
 
-@pytest.mark.parametrize("rows,cols", [(5, 7), (512, 167), (33, 2048), (4, 64), (512, 2048), (3, 1024), (7, 1500), (2, 4096), (5, 1022), (3, 4100)])
-def test_layernorm(dev, rows, cols):
+def _layernorm_case(dev, rows, cols):
     x, r = rnd(rows, cols, seed=1), rnd(rows, cols, seed=2)
     gam, bet, dy = rnd(cols, seed=3), rnd(cols, seed=4), rnd(rows, cols, seed=5)
     xr, rr, gr, br = (t.clone().double().requires_grad_(True) for t in (x, r, gam, bet))
@@ -409,10 +421,15 @@ def test_layernorm(dev, rows, cols):
     assert_close(dz.cpu().numpy(), xr.grad.numpy(), rtol=1e-4, atol_frac=2e-5, what="ln dx")
     assert_close(dg.cpu().numpy(), gr.grad.numpy(), rtol=1e-4, atol_frac=2e-5, what="ln dgamma")
     assert_close(db.cpu().numpy(), br.grad.numpy(), rtol=1e-4, atol_frac=2e-5, what="ln dbeta")
+    return y, z, mean, rstd, dz, dx, dg, db
 
 
-@pytest.mark.parametrize("rows,cols", [(6, 2048), (3, 1500), (5, 167)])
-def test_layernorm_dropout_draws_the_dropout_kernels_stream(dev, rows, cols):
+@pytest.mark.parametrize("rows,cols", [(5, 7), (512, 167), (33, 2048), (4, 64), (512, 2048), (3, 1024), (7, 1500), (2, 4096), (5, 1022), (3, 4100)])
+def test_layernorm(dev, rows, cols):
+    _layernorm_case(dev, rows, cols)
+
+
+def _layernorm_dropout_case(dev, rows, cols):
     """z = dropout(x) + residual inside the LayerNorm kernels (the work-group-per-row form for 1024..4096 columns draws one Philox block
     per float4, the wave-per-row form one per element): both must give the elements bbbp_dropout draws for the contiguous [rows, cols]
     tensor -- bit for bit -- and the backward's dx must apply the same mask."""
@@ -427,10 +444,15 @@ def test_layernorm_dropout_draws_the_dropout_kernels_stream(dev, rows, cols):
     assert_close(y.cpu().numpy(), want.numpy(), rtol=1e-5, what="ln(dropout) fwd")
     dz, dx, _, _ = ops.layernorm_bwd(dy, z, gam, mean, rstd, dropout_p=p, seed=seed)
     assert torch.equal(dx, ops.dropout(dz, p, seed))
+    return y, z, mean, rstd, xd, dz, dx
 
 
-@pytest.mark.parametrize("rows,cols", [(9, 9), (512, 512), (3, 4096), (70, 33)])
-def test_softmax(dev, rows, cols):
+@pytest.mark.parametrize("rows,cols", [(6, 2048), (3, 1500), (5, 167)])
+def test_layernorm_dropout_draws_the_dropout_kernels_stream(dev, rows, cols):
+    _layernorm_dropout_case(dev, rows, cols)
+
+
+def _softmax_case(dev, rows, cols):
     x, dp = rnd(rows, cols, seed=1, scale=3.0), rnd(rows, cols, seed=2)
     xr = x.clone().double().requires_grad_(True)
     pr = torch.softmax(xr, dim=-1)
@@ -440,13 +462,20 @@ def test_softmax(dev, rows, cols):
     assert_close(p.cpu().numpy(), pr.detach().numpy(), rtol=1e-5, what="softmax")
     ds = ops.softmax_bwd(dp.to(dev), p)
     assert_close(ds.cpu().numpy(), xr.grad.numpy(), rtol=1e-4, atol_frac=2e-5, what="softmax bwd")
+    return p, ds
 
 
-def test_batchnorm_golden_and_random(dev):
+@pytest.mark.parametrize("rows,cols", [(9, 9), (512, 512), (3, 4096), (70, 33)])
+def test_softmax(dev, rows, cols):
+    _softmax_case(dev, rows, cols)
+
+
+def _batchnorm_case(dev):
     g = golden("ops")
     x, w, b = (torch.from_numpy(g[k]).to(dev) for k in ("bn/x", "bn/w", "bn/b"))
     rm, rv = torch.zeros(6, device=dev), torch.ones(6, device=dev)
     y, sm, sr = ops.batchnorm1d_fwd(x, w, b, rm, rv, training=True)
+    out = [y, sm, sr, rm.clone(), rv.clone()]
     assert_close(y.cpu().numpy(), g["bn/y_train"], rtol=1e-5, what="bn train")
     assert_close(rm.cpu().numpy(), g["bn/running_mean"], rtol=1e-5, what="bn running_mean")
     assert_close(rv.cpu().numpy(), g["bn/running_var"], rtol=1e-5, what="bn running_var")
@@ -454,7 +483,8 @@ def test_batchnorm_golden_and_random(dev):
     assert_close(dx.cpu().numpy(), g["bn/gx"], rtol=1e-4, atol_frac=2e-5, what="bn dx")
     assert_close(dg.cpu().numpy(), g["bn/gw"], rtol=1e-4, atol_frac=2e-5, what="bn dgamma")
     assert_close(db.cpu().numpy(), g["bn/gb"], rtol=1e-4, atol_frac=2e-5, what="bn dbeta")
-    y2, _, _ = ops.batchnorm1d_fwd(x, w, b, rm, rv, training=False)
+    y2, sm2, sr2 = ops.batchnorm1d_fwd(x, w, b, rm, rv, training=False)
+    out += [dx, dg, db, y2, sm2, sr2]
     assert_close(y2.cpu().numpy(), g["bn/y_eval"], rtol=1e-5, what="bn eval")
     with pytest.raises(RuntimeError, match="more than 1 value per channel"):
         ops.batchnorm1d_fwd(x[:1].contiguous(), w, b, rm, rv, training=True)     # same failure as nn.BatchNorm1d
@@ -466,12 +496,17 @@ def test_batchnorm_golden_and_random(dev):
     yr = F.batch_norm(Xr, rm.cpu().double(), rv.cpu().double(), W.cpu().double(), Bb.cpu().double(), False, 0.1, 1e-5)
     yr.backward(dy.double())
     y, sm, sr = ops.batchnorm1d_fwd(X, W, Bb, rm, rv, training=False)
-    dx, _, _ = ops.batchnorm1d_bwd(dy.to(dev), X, W, sm, sr, training=False)
+    dx, dg, db = ops.batchnorm1d_bwd(dy.to(dev), X, W, sm, sr, training=False)
     assert_close(y.cpu().numpy(), yr.detach().numpy(), rtol=1e-5, what="bn eval big")
     assert_close(dx.cpu().numpy(), Xr.grad.numpy(), rtol=1e-4, what="bn eval dx")
+    return out + [y, sm, sr, dx, dg, db]
 
 
-def test_bias_act_bwd_and_mse(dev):
+def test_batchnorm_golden_and_random(dev):
+    _batchnorm_case(dev)
+
+
+def _bias_act_bwd_and_mse_case(dev):
     y = torch.relu(rnd(50, 70, seed=1)); dy = rnd(50, 70, seed=2)
     want = dy * (y > 0)
     d = dy.clone().to(dev)
@@ -482,15 +517,25 @@ def test_bias_act_bwd_and_mse(dev):
     loss, dpred = ops.mse(pred.to(dev), tgt.to(dev))
     assert_close(loss.cpu().numpy(), [float(((pred - tgt) ** 2).mean())], rtol=1e-5, what="mse")
     assert_close(dpred.cpu().numpy(), (2 * (pred - tgt) / 37).numpy(), rtol=1e-5, what="dmse")
+    return d, db, loss, dpred
 
 
-def test_dropout_statistics_and_determinism(dev):
+def test_bias_act_bwd_and_mse(dev):
+    _bias_act_bwd_and_mse_case(dev)
+
+
+def _dropout_case(dev):
     x = torch.ones(1 << 20, device=dev)
     y1, y2, y3 = ops.dropout(x, 0.1, seed=5), ops.dropout(x, 0.1, seed=5), ops.dropout(x, 0.1, seed=6)
     assert torch.equal(y1, y2) and not torch.equal(y1, y3)
     keep = float((y1 > 0).float().mean())
     assert abs(keep - 0.9) < 2e-3
     assert abs(float(y1.mean()) - 1.0) < 3e-3 and abs(float(y1.max()) - 1 / 0.9) < 1e-6
+    return y1, y3
+
+
+def test_dropout_statistics_and_determinism(dev):
+    _dropout_case(dev)
 
 
 def test_adamw_matches_oracle(dev):
