@@ -92,6 +92,14 @@ class LogregProblem(Structure):
                 ("fit_intercept", c_int), ("max_iter", c_int), ("theta", c_void_p), ("trial", c_void_p), ("state", c_void_p), ("flags", c_void_p)]
 
 
+class GbtChain(Structure):
+    """bbbp_gbt_chain (include/bbbp_hip.h)."""
+    _fields_ = [("XT", c_void_p), ("order0", c_void_p), ("y", c_void_p), ("n", c_int), ("d", c_int), ("n_estimators", c_int), ("max_depth", c_int),
+                ("min_samples_split", c_int), ("min_samples_leaf", c_int), ("learning_rate", c_double), ("init", c_double), ("work", c_void_p),
+                ("left", c_void_p), ("right", c_void_p), ("feature", c_void_p), ("n_node_samples", c_void_p), ("threshold", c_void_p), ("value", c_void_p),
+                ("tree_nodes", c_void_p), ("train_score", c_void_p), ("raw", c_void_p)]
+
+
 _FP = c_void_p          # device float*
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -150,6 +158,11 @@ _SIGNATURES = {
     "bbbp_logreg_rounds": (c_int, [c_void_p, POINTER(LogregProblem), c_int, c_int]),
     "bbbp_logreg_eval": (c_int, [c_void_p, POINTER(LogregProblem)]),
     "bbbp_logreg_decision": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "bbbp_gbt_fit_tree_capacity": (c_int, [c_int]),
+    "bbbp_gbt_fit_work_bytes": (c_size_t, [c_int, c_int]),
+    "bbbp_gbt_fit": (c_int, [c_void_p, POINTER(GbtChain), c_void_p, c_int]),
+    "bbbp_gbt_staged_decision": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                         c_double, c_double, c_void_p, c_int, c_void_p]),
     "bbbp_graph_stats": (c_int, [POINTER(c_long), POINTER(c_long)]),
     "bbbp_conv_last_clock": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "bbbp_set_conv_winograd": (c_int, [c_int]),

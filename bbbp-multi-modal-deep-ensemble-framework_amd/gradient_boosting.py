@@ -1,0 +1,415 @@
+"""``sklearn.ensemble.GradientBoostingClassifier`` for the GPU: two classes, log-loss, exact-split regression trees fitted level by level.
+
+The classification stack of the reference (``Models/model_opt_maccs.py:124-200``) searches ``GradientBoostingClassifier`` over
+``n_estimators in {50, 100, 200}``, ``learning_rate in {0.01, 0.05, 0.1}``, ``max_depth in {3, 5, 7}`` and ``min_samples_split in
+{2, 5, 10}`` under ``GridSearchCV(cv=5, scoring='f1')`` -- 405 fits on about 6 400 rows of 100 features -- and uses the same learner as
+the ``StackingClassifier``'s final estimator.  The entry points of ``csrc/gbt.hip`` carry it:
+
+* a training matrix is cast to float32 (scikit-learn's trees compare float32 features), transposed and every column's rows are sorted
+  stably once; all chains over that matrix share both;
+* ``bbbp_gbt_fit`` fits any number of chains side by side, one tree level per round of six launches, with no host read before the end;
+* ``bbbp_gbt_staged_decision`` walks query rows through the trees in stage order and writes the raw score at every requested stage count
+  in one pass, with scikit-learn's ``predict_stages`` arithmetic: a model adopted by ``from_sklearn`` predicts bit for bit what
+  scikit-learn predicts.
+
+The algorithm is scikit-learn 1.7's (``ensemble/_gb.py``, ``tree/_splitter.pyx``, ``_criterion.pyx``): raw scores start at the prior's
+logit, a stage fits one tree to ``g = y - expit(raw)`` with the ``friedman_mse`` split score ``(n_r S_l - n_l S_r)^2 / (n_l n_r)``, a leaf's
+value is ``mean(g) / mean(p (1 - p))`` and ``raw += learning_rate * value[leaf]``.  Residuals take few distinct values, so many splits
+tie; scikit-learn breaks ties by a random feature order (its trees differ between any two ``random_state`` values), here the lowest
+feature index wins among equal computed scores, then the lowest position.  Trees are therefore not scikit-learn's trees; they are
+certified instead (``tests/gbt_replay.py``).  Results are bit-identical for a problem alone, in any batch, in any order and run to run.
+
+Out of scope (each is refused by name): more than two classes, other losses and criteria, ``subsample < 1``, ``max_features``,
+``sample_weight``, ``init`` estimators, ``n_iter_no_change``, ``max_leaf_nodes``, ``ccp_alpha``, ``min_impurity_decrease != 0``,
+``max_depth > 7``, more than 8 192 rows or 1 024 features, more than one GPU.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import numbers
+import types
+
+import numpy as np
+import torch
+
+from . import _dense, _lib
+from .linear_model import _binary_targets
+from .trees import ForestGPU
+
+MAX_ROWS, MAX_FEATURES, MAX_DEPTH, MAX_TREES = 8192, 1024, 7, 10000        # BBBP_GBT_FIT_MAX_*
+GRID_KEYS = ("n_estimators", "learning_rate", "max_depth", "min_samples_split", "min_samples_leaf")
+EPS32 = float(np.finfo(np.float32).eps)
+_SKLEARN_DEFAULTS = dict(loss="log_loss", criterion="friedman_mse", subsample=1.0, max_features=None, init=None, n_iter_no_change=None,
+                         max_leaf_nodes=None, ccp_alpha=0.0, min_impurity_decrease=0.0, min_weight_fraction_leaf=0.0, warm_start=False)
+
+
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def _check_params(n_estimators, learning_rate, max_depth, min_samples_split, min_samples_leaf, who="GradientBoostingClassifier"):
+    if not _is_int(n_estimators) or not 1 <= n_estimators <= MAX_TREES:
+        raise ValueError(f"{who}: n_estimators must be an int in 1..{MAX_TREES}, got {n_estimators!r}")
+    if isinstance(learning_rate, bool) or not isinstance(learning_rate, numbers.Real) or not (0.0 < float(learning_rate) < float("inf")):
+        raise ValueError(f"{who}: learning_rate must be a positive finite number, got {learning_rate!r}")
+    if max_depth is None or not _is_int(max_depth):
+        raise NotImplementedError(f"{who}: max_depth must be an int in 1..{MAX_DEPTH}, got {max_depth!r}")
+    if max_depth < 1:
+        raise ValueError(f"{who}: max_depth must be an int in 1..{MAX_DEPTH}, got {max_depth!r}")
+    if max_depth > MAX_DEPTH:
+        raise NotImplementedError(f"{who}: max_depth {max_depth} exceeds the {MAX_DEPTH} levels the kernels keep per tree")
+    if not _is_int(min_samples_split):
+        raise NotImplementedError(f"{who}: min_samples_split must be an int >= 2 (fractions are not supported), got {min_samples_split!r}")
+    if min_samples_split < 2:
+        raise ValueError(f"{who}: min_samples_split must be an int >= 2, got {min_samples_split!r}")
+    if not _is_int(min_samples_leaf):
+        raise NotImplementedError(f"{who}: min_samples_leaf must be an int >= 1 (fractions are not supported), got {min_samples_leaf!r}")
+    if min_samples_leaf < 1:
+        raise ValueError(f"{who}: min_samples_leaf must be an int >= 1, got {min_samples_leaf!r}")
+
+
+def _check_shape(n, d, who):
+    if n < 2 or d < 1:
+        raise ValueError(f"{who}: need at least two rows and one feature, got shape {(n, d)}")
+    if n > MAX_ROWS:
+        raise ValueError(f"{who}: n = {n} rows, at most {MAX_ROWS} are supported (BBBP_GBT_FIT_MAX_N)")
+    if d > MAX_FEATURES:
+        raise ValueError(f"{who}: d = {d} features, at most {MAX_FEATURES} are supported (BBBP_GBT_FIT_MAX_D)")
+
+
+def _training_matrix32(X, who):
+    """X as float32 [n, d], numpy (host) or a CUDA tensor, checked for shape and finiteness; a numpy input never touches the GPU here."""
+    if isinstance(X, torch.Tensor):
+        if not X.is_cuda:
+            raise RuntimeError(f"{who}: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
+        if X.dim() != 2:
+            raise ValueError(f"{who}: expected a 2-D [n, d] input, got shape {tuple(X.shape)}")
+        _check_shape(X.shape[0], X.shape[1], who)
+        X32 = X.to(torch.float32)
+        if not bool(torch.isfinite(X32).all()):
+            raise ValueError(f"{who}: X contains NaN, infinity or a value too large for float32")
+        return X32
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError(f"{who}: expected a 2-D [n, d] input, got shape {X.shape}")
+    _check_shape(X.shape[0], X.shape[1], who)
+    with np.errstate(over="ignore"):
+        X32 = np.ascontiguousarray(X, dtype=np.float32)
+    if not np.isfinite(X32).all():
+        raise ValueError(f"{who}: X contains NaN, infinity or a value too large for float32")
+    return X32
+
+
+def _prior_logit(t):
+    """scikit-learn's initial raw score for ``init=None``: the logit of the positive class's share, clipped to [eps32, 1 - eps32]."""
+    from scipy.special import logit
+    return float(logit(np.clip(np.float64(np.mean(t)), EPS32, 1.0 - EPS32)))
+
+
+class _Matrix:
+    """One training matrix on the device: float32 by columns, and every column's rows sorted stably by value (``torch.sort``: done once
+    per matrix, outside the hot path)."""
+
+    def __init__(self, X32, device):
+        X32 = X32 if isinstance(X32, torch.Tensor) else torch.from_numpy(X32)
+        self.XT = X32.to(device).t().contiguous()
+        self.order0 = torch.sort(self.XT, dim=1, stable=True).indices.to(torch.int32).contiguous()
+        self.d, self.n = self.XT.shape
+
+
+class _Chain:
+    """One model to fit: its outputs, its work area and the descriptor ``bbbp_gbt_fit`` takes.  Nothing needs initialising."""
+
+    def __init__(self, mat, t_d, init, n_estimators, learning_rate, max_depth, min_samples_split, min_samples_leaf):
+        L, dev = _lib.lib(), mat.XT.device
+        nbytes = L.bbbp_gbt_fit_work_bytes(mat.n, mat.d)
+        self.cap = L.bbbp_gbt_fit_tree_capacity(max_depth)
+        if not nbytes or not self.cap:
+            raise ValueError("gradient_boosting: " + L.bbbp_last_error().decode("utf-8", "replace"))
+        T = int(n_estimators)
+        self.mat, self.t, self.T, self.init, self.learning_rate = mat, t_d, T, float(init), float(learning_rate)
+        self.params = (T, float(learning_rate), int(max_depth), int(min_samples_split), int(min_samples_leaf))
+        self.work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)  # noqa: E731
+        f64 = lambda k: torch.empty(k, dtype=torch.float64, device=dev)  # noqa: E731
+        self.left, self.right, self.feature, self.nns = i32(T * self.cap), i32(T * self.cap), i32(T * self.cap), i32(T * self.cap)
+        self.threshold, self.value = f64(T * self.cap), f64(T * self.cap)
+        self.tree_nodes, self.train_score, self.raw = i32(T), f64(T), f64(mat.n)
+        self.desc = _lib.GbtChain(mat.XT.data_ptr(), mat.order0.data_ptr(), t_d.data_ptr(), mat.n, mat.d, T, int(max_depth), int(min_samples_split),
+                                  int(min_samples_leaf), float(learning_rate), float(init), self.work.data_ptr(), self.left.data_ptr(),
+                                  self.right.data_ptr(), self.feature.data_ptr(), self.nns.data_ptr(), self.threshold.data_ptr(), self.value.data_ptr(),
+                                  self.tree_nodes.data_ptr(), self.train_score.data_ptr(), self.raw.data_ptr())
+
+    def trees(self):
+        """The fitted trees as flat host arrays in ``ForestGPU.flatten_sklearn``'s convention (absolute child indices, -1 at a leaf), plus
+        ``n_node_samples``; the one host read of a fit."""
+        counts = self.tree_nodes.cpu().numpy().astype(np.int64)
+        if (counts < 1).any():
+            raise RuntimeError(f"gradient_boosting: the fit kernels reported an index outside its array in tree {int(np.argmax(counts < 1))} "
+                               "(a defect of csrc/gbt.hip, not of the data); no model is returned")
+        root = np.concatenate([[0], np.cumsum(counts)])
+        keep = (np.arange(self.cap)[None, :] < counts[:, None]).ravel()
+        offs = np.repeat(root[:-1], counts)
+        pick = lambda a: a.cpu().numpy()[keep]  # noqa: E731
+        left, right = pick(self.left).astype(np.int64), pick(self.right).astype(np.int64)
+        return dict(left=np.where(left >= 0, left + offs, -1).astype(np.int32), right=np.where(right >= 0, right + offs, -1).astype(np.int32),
+                    feature=pick(self.feature), threshold=pick(self.threshold), value=pick(self.value), n_node_samples=pick(self.nns),
+                    root=root.astype(np.int32))
+
+
+def _fit_chains(chains):
+    """``bbbp_gbt_fit`` over all chains in one batch: the descriptors go to the device once, nothing is read back here."""
+    dev = chains[0].work.device
+    arr = (_lib.GbtChain * len(chains))(*[c.desc for c in chains])
+    on_device = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    _lib.check(_lib.lib().bbbp_gbt_fit(_dense.stream(), arr, on_device.data_ptr(), len(chains)), "bbbp_gbt_fit")
+    return on_device                                   # kept alive by the caller until the results are read
+
+
+def _check_trees(trees, n_features):
+    """Host-side validation of tree arrays handed to the decision kernel: every index it follows stays inside its arrays."""
+    left, right, feature, root = trees["left"], trees["right"], trees["feature"], trees["root"]
+    n_nodes = len(left)
+    if not (len(right) == len(feature) == len(trees["threshold"]) == len(trees["value"]) == n_nodes) or root[-1] != n_nodes or root[0] != 0:
+        raise ValueError("gradient_boosting: tree arrays of unequal length")
+    if np.any(np.diff(root) < 1):
+        raise ValueError("gradient_boosting: an empty tree")
+    split = left >= 0
+    if np.any(left[split] >= n_nodes) or np.any(right[split] < 0) or np.any(right[split] >= n_nodes) or np.any(feature < 0) or np.any(feature >= n_features):
+        raise ValueError("gradient_boosting: a child or feature index outside its array")
+
+
+class GradientBoostingClassifier:
+    """``GradientBoostingClassifier(n_estimators=100, learning_rate=0.1, max_depth=3, min_samples_split=2, min_samples_leaf=1, *,
+    device="cuda")``: scikit-learn's names for two classes and the log-loss.
+
+    ``fit`` takes a numpy array or a CUDA tensor [n, d] (n <= 8 192, d <= 1 024; cast to float32, as scikit-learn's trees do) and labels
+    with two distinct values; ``classes_[1]`` is the positive class.  It sets ``classes_``, ``n_estimators_``, ``n_features_in_``,
+    ``init_`` (the prior's logit), ``train_score_`` (scikit-learn's: twice the mean of ``log(1 + exp(raw)) - y raw`` after each stage) and ``trees_``: ``left``, ``right``, ``feature``,
+    float64 ``threshold``, ``value``, ``n_node_samples`` and ``root`` in ``ForestGPU.flatten_sklearn``'s convention, nodes numbered level
+    by level.  ``decision_function`` returns float64 [m] (numpy for numpy input, a CUDA tensor for a CUDA tensor), positive meaning
+    ``classes_[1]``; ``staged_decision_function`` yields it after every stage; ``predict_proba`` is ``[1 - p, p]`` with ``p =
+    expit(decision)``; ``predict`` is ``classes_[decision >= 0]``, scikit-learn's rule."""
+
+    def __init__(self, n_estimators=100, learning_rate=0.1, max_depth=3, min_samples_split=2, min_samples_leaf=1, *, device="cuda", random_state=None,
+                 verbose=0, **other):
+        for name, value in other.items():
+            if name not in _SKLEARN_DEFAULTS:
+                raise ValueError(f"GradientBoostingClassifier: unknown parameter {name}")
+            if value is not _SKLEARN_DEFAULTS[name] and not (isinstance(value, (numbers.Real, str)) and value == _SKLEARN_DEFAULTS[name]):
+                raise NotImplementedError(f"GradientBoostingClassifier: {name}={value!r} is not supported (only {_SKLEARN_DEFAULTS[name]!r})")
+        _check_params(n_estimators, learning_rate, max_depth, min_samples_split, min_samples_leaf)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"GradientBoostingClassifier: device {device!r}: trees are fitted on the GPU (no CPU fallback)")
+        self.n_estimators, self.learning_rate, self.max_depth = int(n_estimators), float(learning_rate), int(max_depth)
+        self.min_samples_split, self.min_samples_leaf = int(min_samples_split), int(min_samples_leaf)
+        self.random_state = random_state                 # accepted and unused: ties are broken by the fixed rule, not by a random order
+
+    # ---- fit --------------------------------------------------------------------------------------------------------
+    def fit(self, X, y, sample_weight=None):
+        who = "GradientBoostingClassifier"
+        if sample_weight is not None:
+            raise ValueError(f"{who}: sample_weight is not supported")
+        classes, t = _binary_targets(y, None, who)
+        X32 = _training_matrix32(X, who)
+        if X32.shape[0] != len(t):
+            raise ValueError(f"{who}: X has {X32.shape[0]} rows, y has {len(t)}")
+        with torch.cuda.device(self.device):
+            mat = _Matrix(X32, self.device)
+            chain = _Chain(mat, torch.from_numpy(t).to(self.device), _prior_logit(t), self.n_estimators, self.learning_rate, self.max_depth,
+                           self.min_samples_split, self.min_samples_leaf)
+            keep = _fit_chains([chain])
+            self._adopt(classes, chain)
+            del keep
+        return self
+
+    def _adopt(self, classes, chain, n_estimators=None):
+        """Fitted attributes from a fitted chain; ``n_estimators`` below the chain's keeps its first trees (a shorter model is the prefix of a
+        longer one)."""
+        trees = chain.trees()
+        T = chain.T if n_estimators is None else int(n_estimators)
+        if T < chain.T:
+            end = int(trees["root"][T])
+            trees = {k: (v[:T + 1] if k == "root" else v[:end]) for k, v in trees.items()}
+        self._set_model(classes, trees, chain.init, chain.learning_rate, chain.mat.d)
+        self.train_score_ = chain.train_score.cpu().numpy()[:T].copy()
+        self._train_raw = chain.raw.cpu().numpy() if T == chain.T else None       # the training rows' raw scores after the last stage (tests)
+
+    def _set_model(self, classes, trees, init, learning_rate, n_features):
+        _check_trees(trees, n_features)
+        self.classes_, self.trees_, self.init_, self.n_features_in_ = classes, trees, float(init), int(n_features)
+        self.n_estimators_ = len(trees["root"]) - 1
+        self._lr = float(learning_rate)
+        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)  # noqa: E731
+        self._dev = {k: to(trees[k], np.float64 if k in ("threshold", "value") else np.int32) for k in ("left", "right", "feature", "threshold", "value", "root")}
+
+    @classmethod
+    def from_sklearn(cls, fitted, device="cuda"):
+        """Adopt a fitted scikit-learn ``GradientBoostingClassifier`` (two classes, ``init=None``) for prediction only:
+        ``decision_function`` and every stage of ``staged_decision_function`` equal scikit-learn's bit for bit."""
+        from scipy.special import logit
+        from sklearn.dummy import DummyClassifier
+        if getattr(fitted, "n_classes_", None) != 2 or fitted.estimators_.shape[1] != 1:
+            raise ValueError("GradientBoostingClassifier.from_sklearn: exactly two classes are supported")
+        if not isinstance(fitted.init_, DummyClassifier) or fitted.init_.strategy != "prior":
+            raise NotImplementedError("GradientBoostingClassifier.from_sklearn: init estimators are not supported (only init=None, the prior)")
+        self = cls(1, float(fitted.learning_rate), device=device)
+        shim = types.SimpleNamespace(estimators_=list(fitted.estimators_[:, 0]), n_features_in_=fitted.n_features_in_, n_outputs_=1)
+        left, right, feature, threshold, value, root, d = ForestGPU.flatten_sklearn(shim)
+        nns = np.concatenate([e.tree_.n_node_samples for e in shim.estimators_])
+        trees = dict(left=left.astype(np.int32), right=right.astype(np.int32), feature=feature.astype(np.int32), threshold=threshold, value=value,
+                     n_node_samples=nns.astype(np.int32), root=root.astype(np.int32))
+        init = float(logit(np.clip(np.float64(fitted.init_.class_prior_[1]), EPS32, 1.0 - EPS32)))
+        self.n_estimators = len(root) - 1
+        # the fitting parameters are kept only where this class would accept them (scikit-learn allows None and fractions): an adopted
+        # model predicts, it is not refitted
+        for name in ("max_depth", "min_samples_split", "min_samples_leaf"):
+            setattr(self, name, getattr(fitted, name) if _is_int(getattr(fitted, name)) else None)
+        self._set_model(np.asarray(fitted.classes_), trees, init, float(fitted.learning_rate), d)
+        self.train_score_ = np.asarray(fitted.train_score_, dtype=np.float64).copy()
+        self._train_raw = None
+        return self
+
+    # ---- decision ---------------------------------------------------------------------------------------------------
+    def _queries(self, X):
+        if not hasattr(self, "_dev"):
+            raise RuntimeError("gradient_boosting: not fitted")
+        was_numpy = not isinstance(X, torch.Tensor)
+        if was_numpy:
+            X = np.asarray(X)
+            if X.ndim != 2:
+                raise ValueError(f"gradient_boosting: expected a 2-D [m, d] input, got shape {X.shape}")
+            with np.errstate(over="ignore"):
+                X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
+        elif not X.is_cuda:
+            raise RuntimeError(f"gradient_boosting: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
+        if X.dim() != 2 or X.shape[1] != self.n_features_in_:
+            raise ValueError(f"gradient_boosting: the queries must be [m, {self.n_features_in_}], got shape {tuple(X.shape)}")
+        return X.to(self.device, torch.float32).contiguous(), was_numpy
+
+    def _staged(self, Xq, stages):
+        """Raw scores [len(stages), m] after ``stages`` trees each (ascending, within 1..n_estimators_)."""
+        m = Xq.shape[0]
+        out = torch.empty((len(stages), m), dtype=torch.float64, device=self.device)
+        if m == 0:
+            return out
+        stages_d = torch.tensor(list(stages), dtype=torch.int32, device=self.device)
+        t = self._dev
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().bbbp_gbt_staged_decision(_dense.stream(), Xq.data_ptr(), Xq.shape[1], m, Xq.shape[1], t["left"].data_ptr(),
+                                                           t["right"].data_ptr(), t["feature"].data_ptr(), t["threshold"].data_ptr(), t["value"].data_ptr(),
+                                                           t["root"].data_ptr(), self.n_estimators_, self.init_, self._lr, stages_d.data_ptr(), len(stages),
+                                                           out.data_ptr()), "bbbp_gbt_staged_decision")
+        return out
+
+    def decision_function(self, X):
+        """The raw score of every row after all stages; positive means ``classes_[1]``."""
+        Xq, was_numpy = self._queries(X)
+        out = self._staged(Xq, [self.n_estimators_])[0]
+        return out.cpu().numpy() if was_numpy else out
+
+    def staged_decision_function(self, X):
+        """Yields the raw scores [m] after 1, 2, ... trees (computed in one pass over the trees)."""
+        Xq, was_numpy = self._queries(X)
+        out = self._staged(Xq, range(1, self.n_estimators_ + 1))
+        out = out.cpu().numpy() if was_numpy else out
+        for s in range(self.n_estimators_):
+            yield out[s]
+
+    def predict_proba(self, X):
+        """[m, 2]: ``[1 - p, p]`` with ``p = expit(decision_function(X))``."""
+        Xq, was_numpy = self._queries(X)
+        p = torch.special.expit(self._staged(Xq, [self.n_estimators_])[0])
+        out = torch.stack([1.0 - p, p], dim=1)
+        return out.cpu().numpy() if was_numpy else out
+
+    def predict_log_proba(self, X):
+        """log of ``predict_proba``, each column from ``logsigmoid`` of the decision value."""
+        Xq, was_numpy = self._queries(X)
+        z = self._staged(Xq, [self.n_estimators_])[0]
+        out = torch.stack([torch.nn.functional.logsigmoid(-z), torch.nn.functional.logsigmoid(z)], dim=1)
+        return out.cpu().numpy() if was_numpy else out
+
+    def predict(self, X):
+        """Class labels as a numpy array of ``classes_``' dtype: ``classes_[1]`` where the decision value is >= 0 (scikit-learn's rule)."""
+        Xq, _ = self._queries(X)
+        return self.classes_[(self._staged(Xq, [self.n_estimators_])[0] >= 0).cpu().numpy().astype(np.intp)]
+
+
+def grid_points(param_grid, who="gradient_boosting.grid_search_cv"):
+    """The grid's points in scikit-learn's order (sorted keys, ``itertools.product``; a list of grids one after the other) and each point's
+    full parameter tuple (n_estimators, learning_rate, max_depth, min_samples_split, min_samples_leaf), checked."""
+    from itertools import product
+    points = []
+    for sub in ([param_grid] if isinstance(param_grid, dict) else list(param_grid)):
+        unknown = set(sub) - set(GRID_KEYS)
+        if unknown:
+            raise ValueError(f"{who}: unsupported grid keys {sorted(unknown)}")
+        keys = sorted(sub)
+        points += [dict(zip(keys, vals)) for vals in product(*(sub[k] for k in keys))]
+    if not points:
+        raise ValueError(f"{who}: the grid is empty")
+    defaults = dict(n_estimators=100, learning_rate=0.1, max_depth=3, min_samples_split=2, min_samples_leaf=1)
+    full = [tuple({**defaults, **pt}[k] for k in GRID_KEYS) for pt in points]
+    for params in full:
+        _check_params(*params, who=who)
+    return points, full
+
+
+def _cv_chains(X32, t_all, folds, full, dev):
+    """One chain per (fold, distinct (learning_rate, max_depth, min_samples_split, min_samples_leaf)) to the largest ``n_estimators`` asked
+    of it, all fitted in one batch.  Returns ({(fold, rest): chain}, the folds' test rows on the device, what must outlive the read)."""
+    longest = {}
+    for params in full:
+        longest[params[1:]] = max(longest.get(params[1:], 0), params[0])
+    chains, queries = {}, []
+    for fi, (tr, te) in enumerate(folds):
+        mat = _Matrix(X32[tr], dev)
+        t_d = torch.from_numpy(t_all[tr]).to(dev)
+        init = _prior_logit(t_all[tr])
+        queries.append(torch.from_numpy(X32[te]).to(dev))
+        for rest, T in longest.items():
+            chains[(fi, rest)] = _Chain(mat, t_d, init, T, *rest)
+    return chains, queries, _fit_chains(list(chains.values()))
+
+
+def grid_search_cv(X, y, param_grid, cv: int = 5, device="cuda"):
+    """The reference's ``GridSearchCV(GradientBoostingClassifier(), param_grid, cv=5, scoring='f1')`` (model_opt_maccs.py:124-200) over
+    ``n_estimators``, ``learning_rate``, ``max_depth``, ``min_samples_split`` and ``min_samples_leaf``.
+
+    Same conventions as ``svm.grid_search_cv`` and ``linear_model.grid_search_cv``: sorted keys, ``itertools.product`` order,
+    scikit-learn's ``StratifiedKFold(cv)``, ``f1_score`` of ``classes_[1]``, the first maximum wins.  Without subsampling a shorter model is
+    the prefix of a longer one, so every fold fits one chain per distinct (learning_rate, max_depth, min_samples_split,
+    min_samples_leaf) to the largest ``n_estimators`` asked of it and the shorter models are scored from staged decisions.  All chains of
+    all folds are fitted in one batch; every grid point equals a single ``fit`` on that fold bit for bit; the refit follows.
+    Returns (best_params, mean F1 per point, the classifier refitted on all rows with best_params)."""
+    from sklearn.metrics import f1_score
+    from sklearn.model_selection import StratifiedKFold
+    who = "gradient_boosting.grid_search_cv"
+    points, full = grid_points(param_grid, who)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who}: device {device!r}: trees are fitted on the GPU (no CPU fallback)")
+    X = np.asarray(X)
+    y = np.asarray(y)
+    classes, t_all = _binary_targets(y, X.shape[0] if X.ndim == 2 else None, who)
+    X32 = _training_matrix32(X, who)
+    pos = classes[1]
+    folds = list(StratifiedKFold(n_splits=cv).split(X32, y))
+    f1 = np.zeros((len(points), len(folds)))
+    with torch.cuda.device(dev):
+        chains, queries, keep = _cv_chains(X32, t_all, folds, full, dev)
+        for (fi, rest), chain in chains.items():
+            clf = GradientBoostingClassifier(chain.T, *rest, device=dev)
+            clf._adopt(classes, chain)
+            wanted = sorted({p[0] for p in full if p[1:] == rest})
+            staged = (clf._staged(queries[fi], wanted) >= 0).cpu().numpy()
+            preds = {T: classes[staged[j].astype(np.intp)] for j, T in enumerate(wanted)}
+            for pi, params in enumerate(full):
+                if params[1:] == rest:
+                    f1[pi, fi] = f1_score(y[folds[fi][1]], preds[params[0]], pos_label=pos)
+        del keep, chains, queries
+    scores = [float(v) for v in f1.mean(axis=1)]
+    best = int(np.argmax(scores))
+    fitted = GradientBoostingClassifier(*full[best], device=dev).fit(X32, y)
+    return points[best], scores, fitted

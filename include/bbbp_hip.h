@@ -545,6 +545,48 @@ int bbbp_logreg_eval(void* stream, const bbbp_logreg_problem* problem);
  * one the solver saw. */
 int bbbp_logreg_decision(void* stream, const void* X, int x_dtype, long ld, int m, int d, const double* theta, int fit_intercept, double* out);
 
+/* ---- gbt fit: gradient-boosted classification trees fitted by exact split search (csrc/gbt.hip) --------------------------------
+ * GradientBoostingClassifier of the classification stack (Models/model_opt_maccs.py:124-200): two classes, log-loss, friedman_mse, no
+ * subsampling, the prior as init.  bbbp_amd/gradient_boosting.py composes GradientBoostingClassifier / grid_search_cv from these.
+ * A chain is one model being fitted; chains over one training matrix share XT and order0.  A tree t of a chain owns the node slots
+ * [t * capacity, t * capacity + tree_nodes[t]) of the six node arrays, capacity = 2^(max_depth + 1) - 1; nodes are numbered level by
+ * level from the root 0, children are tree-relative, -1 marks a leaf (feature 0, threshold -2 there); value is mean(g) of a split
+ * node and the update mean(g) / mean(p (1 - p)) of a leaf. */
+#define BBBP_GBT_FIT_MAX_N 8192
+#define BBBP_GBT_FIT_MAX_D 1024
+#define BBBP_GBT_FIT_MAX_DEPTH 7
+#define BBBP_GBT_FIT_MAX_TREES 10000
+#define BBBP_GBT_FIT_MAX_WALK 4096        /* steps of one tree walk in the decision kernel; a longer walk yields NaN */
+typedef struct bbbp_gbt_chain {
+    const float* XT;                           /* [d][n]: the training matrix, float32, one feature after the other */
+    const int* order0;                         /* [d][n]: per feature the row indices sorted stably by value */
+    const double* y;                           /* [n], 0.0 / 1.0 */
+    int n, d;
+    int n_estimators, max_depth, min_samples_split, min_samples_leaf;
+    double learning_rate;
+    double init;                               /* the raw score every row starts from */
+    void* work;                                /* bbbp_gbt_fit_work_bytes(n, d) bytes, 16-byte aligned; need not be initialised */
+    int* left; int* right; int* feature; int* n_node_samples; double* threshold; double* value;      /* [n_estimators][capacity] */
+    int* tree_nodes;                           /* [n_estimators]; -1 from the first tree on in which an index left its array (a defect) */
+    double* train_score;                       /* [n_estimators]: scikit-learn's train_score_, 2 x the mean of log(1 + exp(raw)) - y raw after each stage */
+    double* raw;                               /* [n]: the training rows' raw scores after the last stage */
+} bbbp_gbt_chain;
+/* Node slots per tree, 2^(max_depth + 1) - 1 (0 with a message outside 1..BBBP_GBT_FIT_MAX_DEPTH). */
+int bbbp_gbt_fit_tree_capacity(int max_depth);
+/* Bytes of a chain's `work` (0 with a message for n < 2, d < 1, n > BBBP_GBT_FIT_MAX_N or d > BBBP_GBT_FIT_MAX_D). */
+size_t bbbp_gbt_fit_work_bytes(int n, int d);
+/* Fit every chain, all side by side, without a host read: max over chains of n_estimators * (max_depth + 1) rounds of six launches.
+ * `chains` is a host array, `chains_device` the same bytes in device memory (the kernels read their descriptors there).  A chain's
+ * numbers do not depend on what else is in the batch. */
+int bbbp_gbt_fit(void* stream, const bbbp_gbt_chain* chains, const bbbp_gbt_chain* chains_device, int n_chains);
+/* out[s][q] = init + sum over the first stages[s] trees, in tree order, of learning_rate * value[leaf] (scikit-learn's predict_stages
+ * order, product and sum rounded separately) for query rows X [m][d] float32: one pass over the trees.  Children are absolute indices
+ * into the node arrays, root[t] is tree t's first node; `stages` (device, [n_stages]) ascends strictly within 1..n_trees; a row goes
+ * left when (double)x[feature] <= threshold. */
+int bbbp_gbt_staged_decision(void* stream, const float* X, long ld, int m, int d, const int* left, const int* right, const int* feature,
+                             const double* threshold, const double* value, const int* root, int n_trees, double init, double learning_rate,
+                             const int* stages, int n_stages, double* out);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
