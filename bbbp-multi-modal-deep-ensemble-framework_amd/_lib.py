@@ -92,6 +92,14 @@ class LogregProblem(Structure):
                 ("fit_intercept", c_int), ("max_iter", c_int), ("theta", c_void_p), ("trial", c_void_p), ("state", c_void_p), ("flags", c_void_p)]
 
 
+class RfTree(Structure):
+    """bbbp_rf_tree (include/bbbp_hip.h)."""
+    _fields_ = [("XT", c_void_p), ("order0", c_void_p), ("y", c_void_p), ("n", c_int), ("d", c_int), ("max_depth", c_int), ("min_samples_split", c_int),
+                ("min_samples_leaf", c_int), ("max_features", c_int), ("bootstrap", c_int), ("tree_index", c_int), ("seed", c_uint64), ("work", c_void_p),
+                ("left", c_void_p), ("right", c_void_p), ("feature", c_void_p), ("n_node_samples", c_void_p), ("threshold", c_void_p), ("value", c_void_p),
+                ("value0", c_void_p), ("n_nodes", c_void_p)]
+
+
 class GbtChain(Structure):
     """bbbp_gbt_chain (include/bbbp_hip.h)."""
     _fields_ = [("XT", c_void_p), ("order0", c_void_p), ("y", c_void_p), ("n", c_int), ("d", c_int), ("n_estimators", c_int), ("max_depth", c_int),
@@ -163,6 +171,12 @@ _SIGNATURES = {
     "bbbp_gbt_fit": (c_int, [c_void_p, POINTER(GbtChain), c_void_p, c_int]),
     "bbbp_gbt_staged_decision": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                          c_double, c_double, c_void_p, c_int, c_void_p]),
+    "bbbp_rf_fit_tree_capacity": (c_int, [c_int]),
+    "bbbp_rf_fit_work_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "bbbp_rf_hash": (c_uint64, [c_uint64, c_uint64]),
+    "bbbp_rf_fit": (c_int, [c_void_p, POINTER(RfTree), c_void_p, c_int, c_void_p]),
+    "bbbp_rf_predict_proba": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int, c_int, c_int, c_void_p]),
     "bbbp_graph_stats": (c_int, [POINTER(c_long), POINTER(c_long)]),
     "bbbp_conv_last_clock": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "bbbp_set_conv_winograd": (c_int, [c_int]),

@@ -1,0 +1,638 @@
+// Random-forest classification trees, fitted on the GPU: RandomForestClassifier and DecisionTreeClassifier of the classification stack
+// (Models/model_opt_maccs.py:124-200; two classes, Gini, bootstrap rows as integer weights, a feature subset per node), searched over
+// n_estimators x max_depth x min_samples_split x min_samples_leaf.  scikit-learn's rules (ensemble/_forest.py, tree/_splitter.pyx,
+// _criterion.pyx), restated: features are float32; a node of m distinct rows is a leaf at max_depth, below min_samples_split or
+// 2 min_samples_leaf rows, when it is pure or when no drawn feature has a valid position; a position is valid between two values more than
+// 1e-7f apart with min_samples_leaf rows on either side; the best position maximises (W_R L_1 - W_L R_1)^2 / (W_L W_R) over the node's drawn
+// features, W the weight totals and L_1, R_1 the class-1 weights of the sides.  With n <= 8192 numerator and denominator are exact integers
+// (below 2^53 and 2^26) and the score is one correctly rounded float64 division: no sum has an order, a tree is the same alone, in any
+// batch and run to run, and a numpy restatement (tests/rf_numpy.py) reproduces it bit for bit.  Among equal scores the lowest feature
+// wins, then the lowest position.
+//
+// Random numbers are one counter-based hash (rf_hash): a tree's key is hash(seed, tree), a child's key hash(parent's key, side); bootstrap
+// draw j is hash(hash(key(root), RF_BOOT), j) mapped to [0, n) by multiply-high; a node's candidate features are the max_features features
+// with the lowest hash(key, 2 + f) among those not constant in the node.  A subtree therefore depends on its rows, min_samples_leaf,
+// max_features and its path alone: a tree grown under a larger min_samples_split or a smaller max_depth is the pruning of the unlimited one.
+//
+// A *tree* is one descriptor; many trees grow side by side, trees over one matrix share its column-major float32 copy and its presorted
+// row order per feature.  Every feature's order is kept partitioned into the level's nodes, each segment sorted by that feature; a row
+// carries the 16-bit slot of its node within the level (RF_DEAD once it sits in a leaf).  A level can hold thousands of nodes, so the node
+// tables live in global memory.  `init` (three launches) draws the weights and compacts each order to the rows of positive weight.  One
+// *round* grows one level of every tree with six launches:
+//   stats      one wave per node: weight totals over the node's segment of feature 0's order, n_node_samples, value, the stop rules
+//   draw       one wave per active node: which features are constant, their hash ranks, the drawn list and each (node, feature)'s place in it
+//   split      one work-group per (feature, tree): a segmented integer scan of (weight, weight x class) packed in 32 bits over the
+//              feature's order, the score at the valid positions of nodes that drew the feature, a segmented arg-max (lowest position among
+//              equals), merged per (node, drawn feature) by the one thread at the segment's last position of the pass: no atomics
+//   choose     one work-group per tree: arg-max over a node's drawn features, threshold, children numbered level by level, the next table
+//   side       one thread per row: the slot at the next level
+//   partition  one work-group per (feature, tree): every segment stably by side; rows of leaves stay where they are
+// Depth is not known in advance: rounds are enqueued in blocks of RF_BLOCK_ROUNDS, then one word is read that says whether any tree still grows.
+#include "common.h"
+#include "bbbp_hip.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int RF_SCAN = 256;                  // positions per pass of the compact, split and partition kernels = their threads
+constexpr int RF_BLOCK_ROUNDS = 8;            // levels enqueued between two reads of the `alive` word
+constexpr unsigned RF_DEAD = 0xffffu;         // slot of a row that is in no node of the level
+constexpr int NODE_LEAF = 0, NODE_ACTIVE = 1;
+constexpr float RF_FEATURE_THRESHOLD = 1e-7f;
+constexpr unsigned long long RF_BOOT = 0xB007ull;          // the stream of a tree's bootstrap draws; features use 2 + f <= 1025, sides 0 and 1
+
+__host__ __device__ inline unsigned long long rf_mix(unsigned long long z) {          // the splitmix64 finaliser
+    z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
+    z ^= z >> 27; z *= 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z;
+}
+__host__ __device__ inline unsigned long long rf_hash(unsigned long long a, unsigned long long b) {
+    return rf_mix(rf_mix(a) + 0x9e3779b97f4a7c15ull * (b + 1ull));
+}
+
+struct TreeState { int level, nk, nk_prev, n_nodes, n_eff, done, active, error; };
+struct Table { int *start, *cnt, *node; unsigned long long* key; };       // the nodes of one level, by slot
+__host__ __device__ inline int tree_capacity(int n) { return 2 * n - 1; }
+
+struct Work {                                 // offsets into a tree's `work`, in bytes; all multiples of 16
+    size_t order[2], hist, wy, slot, tab_start[2], tab_cnt[2], tab_node[2], tab_key[2], flag, wtot, ndrawn, left_base, sp_rank, sp_feature, sp_thr,
+        code, feat, cand_enc, cand_pos, state, total;
+};
+__host__ __device__ inline Work work_layout(int n, int d, int mf) {
+    Work w;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { size_t o = at; at += (bytes + 15) / 16 * 16; return o; };
+    const size_t N = (size_t)n;
+    w.order[0] = take((size_t)d * N * 2); w.order[1] = take((size_t)d * N * 2);
+    w.hist = take(N * 4); w.wy = take(N * 4); w.slot = take(N * 2);
+    w.tab_start[0] = take(N * 4); w.tab_cnt[0] = take(N * 4); w.tab_node[0] = take(N * 4); w.tab_key[0] = take(N * 8);      // no loop: an indexed
+    w.tab_start[1] = take(N * 4); w.tab_cnt[1] = take(N * 4); w.tab_node[1] = take(N * 4); w.tab_key[1] = take(N * 8);      // member goes to scratch
+    w.flag = take(N * 4); w.wtot = take(N * 4); w.ndrawn = take(N * 4); w.left_base = take(N * 4);
+    w.sp_rank = take(N * 4); w.sp_feature = take(N * 4); w.sp_thr = take(N * 8);
+    w.code = take(N * (size_t)d * 2); w.feat = take(N * (size_t)mf * 2);
+    w.cand_enc = take(N * (size_t)mf * 8); w.cand_pos = take(N * (size_t)mf * 4);
+    w.state = take(sizeof(TreeState));
+    w.total = at;
+    return w;
+}
+
+struct View {                                 // a tree's work area, typed
+    uint16_t *order_a, *order_b; unsigned* hist; unsigned* wy; uint16_t* slot; Table tab_a, tab_b;
+    int* flag; unsigned* wtot; int *ndrawn, *left_base, *sp_rank, *sp_feature; double* sp_thr;
+    uint16_t *code, *feat; unsigned long long* cand_enc; int* cand_pos; TreeState* st;
+};
+__device__ inline View view_of(const bbbp_rf_tree& c) {
+    const Work w = work_layout(c.n, c.d, c.max_features);
+    char* b = static_cast<char*>(c.work);
+    View v;
+    v.order_a = (uint16_t*)(b + w.order[0]); v.order_b = (uint16_t*)(b + w.order[1]);
+    v.hist = (unsigned*)(b + w.hist); v.wy = (unsigned*)(b + w.wy); v.slot = (uint16_t*)(b + w.slot);
+    v.tab_a = Table{(int*)(b + w.tab_start[0]), (int*)(b + w.tab_cnt[0]), (int*)(b + w.tab_node[0]), (unsigned long long*)(b + w.tab_key[0])};
+    v.tab_b = Table{(int*)(b + w.tab_start[1]), (int*)(b + w.tab_cnt[1]), (int*)(b + w.tab_node[1]), (unsigned long long*)(b + w.tab_key[1])};
+    v.flag = (int*)(b + w.flag); v.wtot = (unsigned*)(b + w.wtot); v.ndrawn = (int*)(b + w.ndrawn); v.left_base = (int*)(b + w.left_base);
+    v.sp_rank = (int*)(b + w.sp_rank); v.sp_feature = (int*)(b + w.sp_feature); v.sp_thr = (double*)(b + w.sp_thr);
+    v.code = (uint16_t*)(b + w.code); v.feat = (uint16_t*)(b + w.feat);
+    v.cand_enc = (unsigned long long*)(b + w.cand_enc); v.cand_pos = (int*)(b + w.cand_pos);
+    v.st = (TreeState*)(b + w.state);
+    return v;
+}
+// Level L reads order buffer L & 1 and table L & 1; `partition` and `choose` write the other one
+// (`c ? v.a : v.b` on members is a select between their addresses and would keep the whole view in scratch: select between copies)
+template <class T> __device__ inline T pick(bool second, T a, T b) { return second ? b : a; }
+__device__ inline uint16_t* order_of(const View& v, int level) { return pick(level & 1, v.order_a, v.order_b); }
+__device__ inline Table table_of(const View& v, int level) {
+    const bool b = level & 1;
+    return Table{pick(b, v.tab_a.start, v.tab_b.start), pick(b, v.tab_a.cnt, v.tab_b.cnt), pick(b, v.tab_a.node, v.tab_b.node), pick(b, v.tab_a.key, v.tab_b.key)};
+}
+// A row index read from an order array, kept inside [0, n): a wrong order never gives a wild address.  It cannot happen while the kernels are
+// right; if it does, the tree's error word is set (every writer stores the same 1) and `choose` reports it as n_nodes = -1
+__device__ inline int row_of(const uint16_t* src, int p, int n, TreeState* st) {
+    const int i = src[p];
+    if (i < n) return i;
+    st->error = 1;
+    return 0;
+}
+// A node's segment, kept inside [0, n_eff): s >= 0, m >= 1, s + m <= n_eff, or the empty segment and the error word
+__device__ inline void segment_of(const Table& tab, int k, int n_eff, TreeState* st, int& s, int& m) {
+    s = tab.start[k]; m = tab.cnt[k];
+    if (s < 0 || m < 1 || s > n_eff - m) { st->error = 1; s = 0; m = 0; }
+}
+
+// ---- init: weights, the compacted orders, the root --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rf_init_rows_kernel(const bbbp_rf_tree* trees) {
+    const bbbp_rf_tree c = trees[blockIdx.y];
+    const View v = view_of(c);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *v.st = TreeState{0, 0, 0, 0, 0, 0, 0, 0};
+    if (i < c.n) v.hist[i] = c.bootstrap ? 0u : 1u;
+}
+__global__ __launch_bounds__(256) void rf_init_boot_kernel(const bbbp_rf_tree* trees) {
+    const bbbp_rf_tree c = trees[blockIdx.y];
+    if (!c.bootstrap) return;
+    const View v = view_of(c);
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= c.n) return;
+    const unsigned long long stream = rf_hash(rf_hash(c.seed, (unsigned long long)c.tree_index), RF_BOOT);
+    const unsigned i = (unsigned)__umul64hi(rf_hash(stream, (unsigned long long)j), (unsigned long long)c.n);      // < n
+    atomicAdd(&v.hist[i < (unsigned)c.n ? i : 0u], 1u);     // integer counts: the histogram does not depend on the order of the adds
+}
+__global__ __launch_bounds__(RF_SCAN) void rf_init_compact_kernel(const bbbp_rf_tree* trees) {
+    const bbbp_rf_tree c = trees[blockIdx.y];
+    const View v = view_of(c);
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = c.n;
+    if (f >= c.d) return;                                   // the grid is sized for the widest tree of the batch
+    __shared__ int wave_cnt[2][4];
+    const int* src = c.order0 + (long)f * n;
+    uint16_t* dst = v.order_a + (long)f * n;
+    int before = 0;
+    for (int base = 0, it = 0; base < n; base += RF_SCAN, ++it) {
+        const int p = base + tid;
+        int i = p < n ? src[p] : 0;
+        if ((unsigned)i >= (unsigned)n) { v.st->error = 1; i = 0; }
+        const bool keep = p < n && v.hist[i] > 0u;
+        const unsigned long long ballot = __ballot(keep);
+        int* wc = wave_cnt[it & 1];
+        if (lane == 0) wc[wave] = __popcll(ballot);
+        __syncthreads();
+        int to = before + __popcll(ballot & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) to += wc[w];
+        before += wc[0] + wc[1] + wc[2] + wc[3];
+        if (keep) dst[to] = (uint16_t)i;                    // to < n: it counts kept rows in front of p
+    }
+    if (f != 0) return;
+    for (int i = tid; i < n; i += RF_SCAN) {
+        const unsigned w = v.hist[i], y1 = c.y[i] > 0.5 ? 1u : 0u;
+        v.wy[i] = (w << 16) | (w * y1);                     // w <= n <= 8192: both halves stay below 2^16 in every partial sum
+        v.slot[i] = w ? (uint16_t)0 : (uint16_t)RF_DEAD;
+    }
+    if (tid == 0) {
+        v.st->n_eff = before; v.st->nk = 1; v.st->n_nodes = 1;
+        v.tab_a.start[0] = 0; v.tab_a.cnt[0] = before; v.tab_a.node[0] = 0;
+        v.tab_a.key[0] = rf_hash(c.seed, (unsigned long long)c.tree_index);
+    }
+}
+
+// ---- stats: the level's nodes: totals, n_node_samples, value, the stop rules ------------------------------------------------------------
+__global__ __launch_bounds__(256) void rf_stats_kernel(const bbbp_rf_tree* trees) {
+    const bbbp_rf_tree c = trees[blockIdx.y];
+    const View v = view_of(c);
+    if (v.st->done) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int level = v.st->level, nk = min(v.st->nk, c.n), n_eff = min(v.st->n_eff, c.n), cap = tree_capacity(c.n);
+    const Table tab = table_of(v, level);
+    const uint16_t* src = order_of(v, level);               // feature 0's order: the nodes' segments are contiguous in it
+    for (int k = blockIdx.x * 4 + wave; k < nk; k += gridDim.x * 4) {
+        int s, m;
+        segment_of(tab, k, n_eff, v.st, s, m);
+        unsigned acc = 0u;
+        for (int p = lane; p < m; p += 64) acc += v.wy[row_of(src, s + p, c.n, v.st)];
+        for (int off = 32; off >= 1; off >>= 1) acc += (unsigned)__shfl_xor((int)acc, off);
+        if (lane != 0) continue;
+        const unsigned W = acc >> 16, W1 = acc & 0xffffu;
+        int node = tab.node[k];
+        if ((unsigned)node >= (unsigned)cap || W == 0u || W1 > W) { v.st->error = 1; node = 0; }
+        // scikit-learn's impurity <= EPSILON: with integer weights W <= 8192 the Gini impurity is 0 for a pure node and at least
+        // (2 W - 2) / W^2 > 2.4e-4 otherwise
+        const bool leaf = level >= c.max_depth || m < c.min_samples_split || m < 2 * c.min_samples_leaf || W1 == 0u || W1 == W;
+        c.n_node_samples[node] = m;
+        c.value[node] = W ? (double)W1 / (double)W : 0.0;
+        c.value0[node] = W ? (double)(W - W1) / (double)W : 0.0;
+        v.wtot[k] = acc;
+        if (leaf) {
+            v.flag[k] = NODE_LEAF;
+            c.left[node] = -1; c.right[node] = -1; c.feature[node] = 0; c.threshold[node] = -2.0;
+        } else {
+            v.flag[k] = NODE_ACTIVE;
+            v.st->active = 1;                               // every writer stores the same 1; `choose` clears it for the next level
+        }
+    }
+}
+
+// ---- draw: an active node's candidate features ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rf_draw_kernel(const bbbp_rf_tree* trees) {
+    const bbbp_rf_tree c = trees[blockIdx.y];
+    const View v = view_of(c);
+    if (v.st->done || !v.st->active) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = c.n, d = c.d, mf = c.max_features;
+    const int level = v.st->level, nk = min(v.st->nk, n), n_eff = min(v.st->n_eff, n);
+    const Table tab = table_of(v, level);
+    const uint16_t* src = order_of(v, level);
+    __shared__ unsigned long long sh[4][BBBP_RF_FIT_MAX_D];
+    __shared__ uint8_t snc[4][BBBP_RF_FIT_MAX_D];
+    unsigned long long* h = sh[wave];
+    uint8_t* nc = snc[wave];
+    for (int k0 = blockIdx.x * 4; k0 < nk; k0 += gridDim.x * 4) {          // the same trip count for the four waves: barriers inside
+        const int k = k0 + wave;
+        const bool on = k < nk && v.flag[k] == NODE_ACTIVE;
+        int s = 0, m = 0;
+        if (on) segment_of(tab, k, n_eff, v.st, s, m);
+        const unsigned long long key = on ? tab.key[k] : 0ull;
+        if (on && m > 0)
+            for (int f = lane; f < d; f += 64) {
+                const float* col = c.XT + (long)f * n;
+                const uint16_t* of = src + (long)f * n;
+                const float a = col[row_of(of, s, n, v.st)], b = col[row_of(of, s + m - 1, n, v.st)];
+                nc[f] = b > a + RF_FEATURE_THRESHOLD ? 1 : 0;
+                h[f] = rf_hash(key, 2ull + (unsigned long long)f);
+            }
+        __syncthreads();
+        int drawn_before = 0;
+        if (on && m > 0) {
+            for (int f0 = 0; f0 < d; f0 += 64) {
+                const int f = f0 + lane;
+                bool drawn = false;
+                if (f < d && nc[f]) {
+                    const unsigned long long hf = h[f];
+                    int rank = 0;
+                    for (int g = 0; g < d; ++g) rank += (nc[g] && (h[g] < hf || (h[g] == hf && g < f))) ? 1 : 0;
+                    drawn = rank < mf;
+                }
+                const unsigned long long ballot = __ballot(drawn);
+                const int j = drawn_before + __popcll(ballot & ((1ull << lane) - 1ull));          // < mf: ranks are distinct
+                if (f < d) v.code[(long)k * d + f] = (drawn && j < mf) ? (uint16_t)(j + 1) : (uint16_t)0;
+                if (drawn && j < mf) {
+                    v.feat[(long)k * mf + j] = (uint16_t)f;
+                    v.cand_enc[(long)k * mf + j] = 0ull;
+                    v.cand_pos[(long)k * mf + j] = 0;
+                }
+                drawn_before += __popcll(ballot);
+            }
+            if (lane == 0) v.ndrawn[k] = min(drawn_before, mf);
+        }
+        __syncthreads();
+    }
+}
+
+// ---- split: the best (score, position) per (node, drawn feature) for one feature ----------------------------------------------------------
+__global__ __launch_bounds__(RF_SCAN) void rf_split_kernel(const bbbp_rf_tree* trees) {
+    const bbbp_rf_tree c = trees[blockIdx.y];
+    const View v = view_of(c);
+    if (v.st->done || !v.st->active) return;
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = c.n, d = c.d, mf = c.max_features;
+    if (f >= d) return;                                     // the grid is sized for the widest tree of the batch
+    const int level = v.st->level, nk = min(v.st->nk, n), n_eff = min(v.st->n_eff, n);
+    const Table tab = table_of(v, level);
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned* swy = reinterpret_cast<unsigned*>(smem);                            // [n] (weight, weight x class)
+    uint16_t* sslot = reinterpret_cast<uint16_t*>(swy + n);                       // [n]
+    __shared__ unsigned wave_val[4], carry_s;
+    __shared__ int wave_flag[4], wave_pos[4];
+    __shared__ unsigned long long wave_enc[4];
+    for (int i = tid; i < n; i += RF_SCAN) { swy[i] = v.wy[i]; sslot[i] = v.slot[i]; }
+    if (tid == 0) carry_s = 0u;
+    __syncthreads();
+    const uint16_t* src = order_of(v, level) + (long)f * n;
+    const float* col = c.XT + (long)f * n;
+    const int msl = c.min_samples_leaf;
+    for (int base = 0; base < n_eff; base += RF_SCAN) {
+        const int p = base + tid;
+        const bool in = p < n_eff;
+        const int i = in ? row_of(src, p, n, v.st) : 0;
+        const unsigned k = in ? sslot[i] : RF_DEAD;
+        bool act = false;
+        int s = 0, m = 0, j = 0;
+        unsigned wt = 0u;
+        if (k != RF_DEAD) {
+            if (k >= (unsigned)nk) v.st->error = 1;
+            else if (v.flag[k] == NODE_ACTIVE) {
+                j = v.code[(long)k * d + f];
+                if (j > mf) { v.st->error = 1; j = 0; }
+                if (j > 0) { segment_of(tab, (int)k, n_eff, v.st, s, m); act = m > 0 && p >= s && p < s + m; wt = v.wtot[k]; }
+            }
+        }
+        const unsigned x = act ? swy[i] : 0u;
+        const unsigned carry = carry_s;                     // the inclusive sum at position base - 1, inside its segment
+        // segmented inclusive scan inside the wave: a segment starts at its node's first position and at every position that is not scored
+        unsigned val = x;
+        int flg = (!act || p == s) ? 1 : 0;
+        const int own = flg;
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned pv = (unsigned)__shfl_up((int)val, off);
+            const int pf = __shfl_up(flg, off);
+            if (lane >= off) {
+                if (!flg) val += pv;
+                flg |= pf;
+            }
+        }
+        if (lane == 63) { wave_val[wave] = val; wave_flag[wave] = flg; }
+        __syncthreads();
+        unsigned pre = carry;                               // what precedes this wave in its first segment
+        for (int w = 0; w < wave; ++w) pre = wave_flag[w] ? wave_val[w] : pre + wave_val[w];
+        if (!flg) val += pre;
+        if (tid == RF_SCAN - 1) carry_s = val;
+        // the candidate between positions p - 1 and p
+        unsigned long long enc = 0ull;
+        if (act && p > s) {
+            const int n_l = p - s, n_r = m - n_l;
+            const float fv = col[i], fv_prev = col[row_of(src, p - 1, n, v.st)];
+            if (fv > fv_prev + RF_FEATURE_THRESHOLD && n_l >= msl && n_r >= msl) {
+                const unsigned left = val - x;              // the exclusive sum: everything in front of p in the segment
+                const long long W = wt >> 16, W1 = wt & 0xffffu, WL = left >> 16, L1 = left & 0xffffu, WR = W - WL, R1 = W1 - L1;
+                if (WL <= 0 || WR <= 0) v.st->error = 1;
+                else {
+                    const long long diff = WR * L1 - WL * R1;                      // |diff| <= 2^26: the square is exact in 64 bits and in a double
+                    const double score = (double)(diff * diff) / (double)(WL * WR);
+                    enc = (unsigned long long)__double_as_longlong(score) + 1ull;  // scores are >= 0: their bits order as integers; 0 = none
+                }
+            }
+        }
+        // segmented arg-max with the same segments: the lowest position among equal scores
+        int pos = p;
+        flg = own;
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned long long pe = (unsigned long long)__shfl_up((long long)enc, off);
+            const int pp = __shfl_up(pos, off);
+            const int pf = __shfl_up(flg, off);
+            if (lane >= off) {
+                if (!flg && pe != 0ull && pe >= enc) { enc = pe; pos = pp; }
+                flg |= pf;
+            }
+        }
+        if (lane == 63) { wave_enc[wave] = enc; wave_pos[wave] = pos; }
+        __syncthreads();
+        if (!flg) {
+            unsigned long long be = 0ull;
+            int bp = 0;
+            for (int w = 0; w < wave; ++w) {
+                if (wave_flag[w] || (wave_enc[w] != 0ull && wave_enc[w] > be)) { be = wave_enc[w]; bp = wave_pos[w]; }
+            }
+            if (be != 0ull && be >= enc) { enc = be; pos = bp; }
+        }
+        // the segment's last position of this pass merges into the (node, drawn feature) slot: one thread per slot and pass, passes in order
+        if (act && enc != 0ull && (p + 1 == s + m || tid == RF_SCAN - 1)) {
+            const long at = (long)k * mf + (j - 1);
+            if (enc > v.cand_enc[at]) { v.cand_enc[at] = enc; v.cand_pos[at] = pos; }
+        }
+        __syncthreads();                                    // the next pass may merge into the same slot from another wave
+    }
+}
+size_t split_lds_bytes(int n) { return (size_t)n * 6; }
+
+// ---- choose: the best drawn feature per node, its threshold and children, the next level's table ---------------------------------------
+__device__ inline void block_scan2(int& a, int& b, int* tmp, int tid) {       // inclusive sums over the 256 threads; tmp: [2][4] ints
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int pa = __shfl_up(a, off), pb = __shfl_up(b, off);
+        if (lane >= off) { a += pa; b += pb; }
+    }
+    __syncthreads();                                        // tmp may still be read from the previous call
+    if (lane == 63) { tmp[wave] = a; tmp[4 + wave] = b; }
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) { a += tmp[w]; b += tmp[4 + w]; }
+}
+__global__ __launch_bounds__(256) void rf_choose_kernel(const bbbp_rf_tree* trees, int* alive, int last_round) {
+    const bbbp_rf_tree c = trees[blockIdx.x];
+    const View v = view_of(c);
+    const TreeState st = *v.st;
+    if (st.done) return;
+    const int tid = threadIdx.x, n = c.n, mf = c.max_features, cap = tree_capacity(n);
+    __shared__ int tmp[8];
+    __syncthreads();                                        // every thread holds the state before thread 0 rewrites it
+    if (!st.active) {
+        if (tid == 0) { v.st->done = 1; *c.n_nodes = st.error ? -1 : st.n_nodes; }
+        return;
+    }
+    const int level = st.level, nk = min(st.nk, n), n_eff = min(st.n_eff, n);
+    const Table tab = table_of(v, level), next = table_of(v, level + 1);
+    int splits_before = 0, lefts_before = 0;
+    for (int base = 0; base < nk; base += 256) {
+        const int k = base + tid;
+        const bool on = k < nk && v.flag[k] == NODE_ACTIVE;
+        int s = 0, m = 0, bf = 0, bp = 0, node = 0;
+        unsigned long long best = 0ull;
+        if (on) {
+            segment_of(tab, k, n_eff, v.st, s, m);
+            node = tab.node[k];
+            if ((unsigned)node >= (unsigned)cap) { v.st->error = 1; node = 0; }
+            const int nd = min(v.ndrawn[k], mf);
+            for (int j = 0; j < nd; ++j) {                  // features ascend with j: the lowest feature wins among equal scores
+                const unsigned long long e = v.cand_enc[(long)k * mf + j];
+                if (e > best) { best = e; bf = v.feat[(long)k * mf + j]; bp = v.cand_pos[(long)k * mf + j]; }
+            }
+            if (bf >= c.d) { v.st->error = 1; bf = 0; best = 0ull; }
+        }
+        const bool split = on && best != 0ull && bp > s && bp < s + m;
+        const int n_left = split ? bp - s : 0;
+        int rank = split ? 1 : 0, lefts = n_left;
+        block_scan2(rank, lefts, tmp, tid);
+        const int r = splits_before + rank - (split ? 1 : 0);
+        if (split) {
+            const uint16_t* src = order_of(v, level) + (long)bf * n;
+            const float a = c.XT[(long)bf * n + row_of(src, bp - 1, n, v.st)], b = c.XT[(long)bf * n + row_of(src, bp, n, v.st)];
+            double thr = (double)a / 2.0 + (double)b / 2.0;
+            if (thr == (double)b) thr = (double)a;
+            const int lc = st.n_nodes + 2 * r, rc = lc + 1;
+            if (rc >= cap || 2 * r + 1 >= n) { v.st->error = 1; v.sp_rank[k] = -1; }      // cannot happen: a level's nodes are non-empty and disjoint
+            else {
+                c.left[node] = lc; c.right[node] = rc; c.feature[node] = bf; c.threshold[node] = thr;
+                v.sp_rank[k] = r; v.sp_feature[k] = bf; v.sp_thr[k] = thr;
+                v.left_base[r] = lefts_before + lefts - n_left;          // rows that go left in the segments in front of this one
+                const unsigned long long key = tab.key[k];
+                next.start[2 * r] = s; next.cnt[2 * r] = n_left; next.node[2 * r] = lc; next.key[2 * r] = rf_hash(key, 0ull);
+                next.start[2 * r + 1] = s + n_left; next.cnt[2 * r + 1] = m - n_left; next.node[2 * r + 1] = rc; next.key[2 * r + 1] = rf_hash(key, 1ull);
+            }
+        } else if (k < nk) {
+            v.sp_rank[k] = -1;
+            if (on) { c.left[node] = -1; c.right[node] = -1; c.feature[node] = 0; c.threshold[node] = -2.0; }       // no valid split: a leaf after all
+        }
+        // the running totals: the last thread's inclusive sums
+        __syncthreads();
+        if (tid == 255) { tmp[0] = rank; tmp[4] = lefts; }
+        __syncthreads();
+        splits_before += tmp[0]; lefts_before += tmp[4];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int error = v.st->error;
+        if (splits_before == 0 || error) {
+            v.st->done = 1;
+            *c.n_nodes = error ? -1 : st.n_nodes;
+        } else {
+            v.st->level = level + 1; v.st->nk_prev = nk; v.st->nk = 2 * splits_before; v.st->n_nodes = st.n_nodes + 2 * splits_before; v.st->active = 0;
+            if (last_round) *alive = 1;
+        }
+    }
+}
+
+// ---- side: every row's slot at the next level ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rf_side_kernel(const bbbp_rf_tree* trees) {
+    const bbbp_rf_tree c = trees[blockIdx.y];
+    const View v = view_of(c);
+    if (v.st->done) return;                                 // `choose` has moved the state on to the next level
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= c.n) return;
+    const unsigned k = v.slot[i];
+    if (k == RF_DEAD) return;
+    if (k >= (unsigned)min(v.st->nk_prev, c.n)) { v.st->error = 1; v.slot[i] = (uint16_t)RF_DEAD; return; }
+    const int r = v.sp_rank[k];
+    if (r < 0) { v.slot[i] = (uint16_t)RF_DEAD; return; }
+    int bf = v.sp_feature[k];
+    if ((unsigned)bf >= (unsigned)c.d) { v.st->error = 1; bf = 0; }
+    const int side = ((double)c.XT[(long)bf * c.n + i] <= v.sp_thr[k]) ? 0 : 1;
+    v.slot[i] = (uint16_t)(2 * r + side);
+}
+
+// ---- partition: every feature's order, stably, by side inside each split segment -----------------------------------------------------------
+__global__ __launch_bounds__(RF_SCAN) void rf_partition_kernel(const bbbp_rf_tree* trees) {
+    const bbbp_rf_tree c = trees[blockIdx.y];
+    const View v = view_of(c);
+    if (v.st->done) return;
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = c.n;
+    if (f >= c.d) return;                                   // the grid is sized for the widest tree of the batch
+    const int level = v.st->level - 1, nk_new = min(v.st->nk, n), n_eff = min(v.st->n_eff, n);
+    if (level < 0) return;
+    const Table next = table_of(v, level + 1);
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint16_t* sslot = reinterpret_cast<uint16_t*>(smem);              // [n] new slots
+    __shared__ int wave_cnt[2][4];
+    for (int i = tid; i < n; i += RF_SCAN) sslot[i] = v.slot[i];
+    __syncthreads();
+    const uint16_t* src = order_of(v, level) + (long)f * n;
+    uint16_t* dst = order_of(v, level + 1) + (long)f * n;
+    int before = 0;                                                   // rows going left in front of this pass
+    for (int base = 0, it = 0; base < n_eff; base += RF_SCAN, ++it) {
+        const int p = base + tid;
+        const bool in = p < n_eff;
+        const int i = in ? row_of(src, p, n, v.st) : 0;
+        unsigned cs = in ? sslot[i] : RF_DEAD;
+        if (cs != RF_DEAD && cs >= (unsigned)nk_new) { v.st->error = 1; cs = RF_DEAD; }
+        const bool moving = cs != RF_DEAD, left = moving && !(cs & 1u);
+        const unsigned long long ballot = __ballot(left);
+        int* wc = wave_cnt[it & 1];
+        if (lane == 0) wc[wave] = __popcll(ballot);
+        __syncthreads();
+        int lefts = before + __popcll(ballot & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) lefts += wc[w];
+        before += wc[0] + wc[1] + wc[2] + wc[3];
+        if (in) {
+            int to = p;                                               // a row of a leaf stays where it is
+            if (moving) {
+                const int r = (int)(cs >> 1), s = next.start[2 * r], nl = next.cnt[2 * r];
+                const int in_seg = lefts - v.left_base[r];            // rows of this segment going left in front of p
+                to = left ? s + in_seg : s + nl + (p - s - in_seg);
+            }
+            if ((unsigned)to < (unsigned)n_eff) dst[to] = (uint16_t)i;
+            else v.st->error = 1;
+        }
+    }
+}
+size_t partition_lds_bytes(int n) { return (size_t)n * 2; }
+
+// ---- predict: class probabilities of query rows from a forest, optionally pruned by limits ------------------------------------------------
+struct PredictArgs {
+    const float* X; long ld; int m, d;
+    const int *left, *right, *feature; const double *threshold, *p0, *p1; const int *n_node_samples, *root;
+    int n_trees, max_depth, min_samples_split; double* out;
+};
+__global__ __launch_bounds__(256) void rf_predict_kernel(PredictArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.m) return;
+    const float* x = a.X + (long)i * a.ld;
+    double s0 = 0.0, s1 = 0.0;
+    for (int t = 0; t < a.n_trees; ++t) {
+        int node = a.root[t], depth = 0;
+        int l = a.left[node];
+        // bounded: arrays handed to the C ABI directly cannot spin a wave for ever
+        while (l >= 0 && depth < a.max_depth && a.n_node_samples[node] >= a.min_samples_split && depth < BBBP_RF_MAX_WALK) {
+            node = (double)x[a.feature[node]] <= a.threshold[node] ? l : a.right[node];
+            l = a.left[node];
+            ++depth;
+        }
+        const bool lost = l >= 0 && depth >= BBBP_RF_MAX_WALK && depth < a.max_depth;
+        s0 = lost ? __builtin_nan("") : s0 + a.p0[node];    // scikit-learn's forest: the trees' probabilities summed in tree order
+        s1 = lost ? __builtin_nan("") : s1 + a.p1[node];
+    }
+    a.out[2 * (long)i] = s0 / (double)a.n_trees;
+    a.out[2 * (long)i + 1] = s1 / (double)a.n_trees;
+}
+
+int check_tree(const bbbp_rf_tree& c, int q) {
+    BBBP_CHECK_ARG(c.n >= 2 && c.d >= 1, "rf_fit: tree %d: n >= 2 and d >= 1 must hold, got n %d d %d", q, c.n, c.d);
+    BBBP_CHECK_ARG(c.n <= BBBP_RF_FIT_MAX_N, "rf_fit: tree %d: n %d exceeds BBBP_RF_FIT_MAX_N %d", q, c.n, BBBP_RF_FIT_MAX_N);
+    BBBP_CHECK_ARG(c.d <= BBBP_RF_FIT_MAX_D, "rf_fit: tree %d: d %d exceeds BBBP_RF_FIT_MAX_D %d", q, c.d, BBBP_RF_FIT_MAX_D);
+    BBBP_CHECK_ARG(c.max_depth >= 1, "rf_fit: tree %d: max_depth %d must be >= 1", q, c.max_depth);
+    BBBP_CHECK_ARG(c.min_samples_split >= 2, "rf_fit: tree %d: min_samples_split %d must be >= 2", q, c.min_samples_split);
+    BBBP_CHECK_ARG(c.min_samples_leaf >= 1, "rf_fit: tree %d: min_samples_leaf %d must be >= 1", q, c.min_samples_leaf);
+    BBBP_CHECK_ARG(c.max_features >= 1 && c.max_features <= c.d, "rf_fit: tree %d: max_features %d outside 1..d = %d", q, c.max_features, c.d);
+    BBBP_CHECK_ARG(c.tree_index >= 0, "rf_fit: tree %d: tree_index %d must be >= 0", q, c.tree_index);
+    BBBP_CHECK_ARG(c.XT && c.order0 && c.y && c.work && c.left && c.right && c.feature && c.n_node_samples && c.threshold && c.value && c.value0 &&
+                       c.n_nodes, "rf_fit: tree %d: null pointer", q);
+    return BBBP_OK;
+}
+
+}  // namespace
+
+extern "C" int bbbp_rf_fit_tree_capacity(int n) {
+    if (n < 2 || n > BBBP_RF_FIT_MAX_N) {
+        bbbp_set_error("rf_fit_tree_capacity: n %d outside 2..%d", n, BBBP_RF_FIT_MAX_N);
+        return 0;
+    }
+    return tree_capacity(n);
+}
+
+extern "C" size_t bbbp_rf_fit_work_bytes(int n, int d, int max_features) {
+    if (n < 2 || d < 1) { bbbp_set_error("rf_fit_work_bytes: n >= 2 and d >= 1 must hold, got n %d d %d", n, d); return 0; }
+    if (n > BBBP_RF_FIT_MAX_N) { bbbp_set_error("rf_fit_work_bytes: n %d exceeds BBBP_RF_FIT_MAX_N %d", n, BBBP_RF_FIT_MAX_N); return 0; }
+    if (d > BBBP_RF_FIT_MAX_D) { bbbp_set_error("rf_fit_work_bytes: d %d exceeds BBBP_RF_FIT_MAX_D %d", d, BBBP_RF_FIT_MAX_D); return 0; }
+    if (max_features < 1 || max_features > d) { bbbp_set_error("rf_fit_work_bytes: max_features %d outside 1..d = %d", max_features, d); return 0; }
+    return work_layout(n, d, max_features).total;
+}
+
+extern "C" unsigned long long bbbp_rf_hash(unsigned long long a, unsigned long long b) { return rf_hash(a, b); }
+
+extern "C" int bbbp_rf_fit(void* stream, const bbbp_rf_tree* trees, const bbbp_rf_tree* trees_device, int n_trees, int* alive_device) {
+    BBBP_CHECK_ARG(trees && trees_device && alive_device, "rf_fit: null pointer");
+    BBBP_CHECK_ARG(n_trees >= 1 && n_trees <= 65535, "rf_fit: n_trees %d outside 1..65535", n_trees);
+    int max_n = 0, max_d = 0;
+    for (int q = 0; q < n_trees; ++q) {
+        if (int rc = check_tree(trees[q], q)) return rc;
+        max_n = trees[q].n > max_n ? trees[q].n : max_n;
+        max_d = trees[q].d > max_d ? trees[q].d : max_d;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t split_lds = split_lds_bytes(max_n), part_lds = partition_lds_bytes(max_n);
+    if (int rc = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(rf_split_kernel), split_lds)) return rc;
+    if (int rc = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(rf_partition_kernel), part_lds)) return rc;
+    const unsigned T = (unsigned)n_trees;
+    const dim3 rows((unsigned)cdiv(max_n, 256), T), feats((unsigned)max_d, T), nodes((unsigned)clampi(cdiv(max_n, 64), 1, 32), T), one(T);
+    hipLaunchKernelGGL(rf_init_rows_kernel, rows, dim3(256), 0, st, trees_device);
+    hipLaunchKernelGGL(rf_init_boot_kernel, rows, dim3(256), 0, st, trees_device);
+    hipLaunchKernelGGL(rf_init_compact_kernel, feats, dim3(RF_SCAN), 0, st, trees_device);
+    BBBP_CHECK_LAUNCH();
+    // a tree of n rows has at most n - 1 levels that split, and one more round to find that nothing is left
+    const int max_blocks = max_n / RF_BLOCK_ROUNDS + 2;
+    for (int b = 0; b < max_blocks; ++b) {
+        BBBP_CHECK_HIP(hipMemsetAsync(alive_device, 0, sizeof(int), st));
+        for (int r = 0; r < RF_BLOCK_ROUNDS; ++r) {
+            hipLaunchKernelGGL(rf_stats_kernel, nodes, dim3(256), 0, st, trees_device);
+            hipLaunchKernelGGL(rf_draw_kernel, nodes, dim3(256), 0, st, trees_device);
+            hipLaunchKernelGGL(rf_split_kernel, feats, dim3(RF_SCAN), split_lds, st, trees_device);
+            hipLaunchKernelGGL(rf_choose_kernel, one, dim3(256), 0, st, trees_device, alive_device, r == RF_BLOCK_ROUNDS - 1 ? 1 : 0);
+            hipLaunchKernelGGL(rf_side_kernel, rows, dim3(256), 0, st, trees_device);
+            hipLaunchKernelGGL(rf_partition_kernel, feats, dim3(RF_SCAN), part_lds, st, trees_device);
+            BBBP_CHECK_LAUNCH();
+        }
+        int alive = 0;                                      // the only host read before the result
+        BBBP_CHECK_HIP(hipMemcpyAsync(&alive, alive_device, sizeof(int), hipMemcpyDeviceToHost, st));
+        BBBP_CHECK_HIP(hipStreamSynchronize(st));
+        if (!alive) return BBBP_OK;
+    }
+    bbbp_set_error("rf_fit: a tree still grows after %d levels", max_blocks * RF_BLOCK_ROUNDS);
+    return BBBP_ERR_HIP;
+}
+
+extern "C" int bbbp_rf_predict_proba(void* stream, const float* X, long ld, int m, int d, const int* left, const int* right, const int* feature,
+                                     const double* threshold, const double* p0, const double* p1, const int* n_node_samples, const int* root,
+                                     int n_trees, int max_depth, int min_samples_split, double* out) {
+    BBBP_CHECK_ARG(m >= 1 && d >= 1, "rf_predict_proba: m and d must be positive, got m %d d %d", m, d);
+    BBBP_CHECK_ARG(ld >= d, "rf_predict_proba: leading dimension %ld below d %d", ld, d);
+    BBBP_CHECK_ARG(n_trees >= 1 && max_depth >= 0 && min_samples_split >= 0, "rf_predict_proba: n_trees %d, max_depth %d, min_samples_split %d", n_trees,
+                   max_depth, min_samples_split);
+    BBBP_CHECK_ARG(X && left && right && feature && threshold && p0 && p1 && n_node_samples && root && out, "rf_predict_proba: null pointer");
+    PredictArgs a{X, ld, m, d, left, right, feature, threshold, p0, p1, n_node_samples, root, n_trees, max_depth, min_samples_split, out};
+    hipLaunchKernelGGL(rf_predict_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    BBBP_CHECK_LAUNCH();
+    return BBBP_OK;
+}

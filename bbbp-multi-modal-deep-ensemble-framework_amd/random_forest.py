@@ -1,0 +1,495 @@
+"""``sklearn.ensemble.RandomForestClassifier`` and ``sklearn.tree.DecisionTreeClassifier`` for the GPU: two classes, Gini, exact-split
+trees of any depth fitted level by level, many trees in one batch.
+
+The classification stack of the reference (``Models/model_opt_maccs.py:124-200``) searches ``RandomForestClassifier`` over
+``n_estimators in {50, 100, 200, 300}``, ``max_depth in {None, 10, 20, 30}``, ``min_samples_split in {2, 5, 10}`` and ``min_samples_leaf in
+{1, 2, 4}`` under ``GridSearchCV(cv=5, scoring='f1')`` -- 720 forests, about 117 000 trees on about 5 100 rows of 100 features -- and a
+``DecisionTreeClassifier``, the one-tree case without bootstrap and with all features.  The entry points of ``csrc/rf.hip`` carry both:
+
+* a training matrix is cast to float32 (scikit-learn's trees compare float32 features), transposed and every column's rows are sorted
+  stably once (``gradient_boosting._Matrix``); all trees over that matrix share both;
+* ``bbbp_rf_fit`` grows any number of trees side by side, one level per round of six launches; the host reads one word per eight levels;
+* ``bbbp_rf_predict_proba`` walks query rows through the trees in tree order with scikit-learn's forest arithmetic, optionally stopping
+  at limits ``(n_trees, max_depth, min_samples_split)``.
+
+The rules are scikit-learn 1.7's (``ensemble/_forest.py``, ``tree/_splitter.pyx``, ``_criterion.pyx``).  A tree's bootstrap is a vector of
+integer row weights; ``n_node_samples`` and the ``min_samples_*`` rules count distinct rows, class totals use the weights.  With two
+classes the Gini proxy orders candidates like ``(W_R L_1 - W_L R_1)^2 / (W_L W_R)``: exact integers and one float64 division, so a fit has
+no summation order and ``tests/rf_numpy.py`` reproduces it bit for bit.  scikit-learn's per-tree random stream cannot be matched: here
+every random choice is one counter-based hash (``bbbp_rf_hash``) of the seed, the tree's number and the node's path, which makes
+``random_state`` part of the model and has a structural consequence: a subtree depends on its rows, ``min_samples_leaf``, ``max_features``
+and its path alone, so a tree under a larger ``min_samples_split`` or a smaller ``max_depth`` is the pruning of the unlimited tree, and a
+forest of fewer trees is a prefix.  ``grid_search_cv`` grows one forest per fold and distinct ``(min_samples_leaf, max_features)`` and scores
+every other grid point with the predict kernel's limits.  Among equal scores the lowest feature wins, then the lowest position; trees are
+certified (``tests/rf_replay.py``), not compared with scikit-learn's.
+
+A tree's probabilities are scikit-learn 1.7's: the leaf's stored class shares ``value`` (already divided by the node's weight when the
+tree was built; ``tree_.predict`` returns them as they are), summed over trees in tree order in float64 and divided by the number of trees.
+
+Out of scope (each is refused by name): more than two classes, ``criterion != "gini"``, ``sample_weight``, ``class_weight``,
+``max_samples``, ``max_leaf_nodes``, ``ccp_alpha``, ``min_impurity_decrease != 0``, fractional ``min_samples_*``, ``oob_score``, more than
+8 192 rows or 1 024 features, regression forests, more than one GPU.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import numbers
+
+import numpy as np
+import torch
+
+from . import _dense, _lib
+from .gradient_boosting import _Matrix, _is_int
+from .linear_model import _binary_targets
+
+MAX_ROWS, MAX_FEATURES = 8192, 1024                # BBBP_RF_FIT_MAX_N, BBBP_RF_FIT_MAX_D
+UNLIMITED = 1 << 30                                # max_depth=None for the kernels: depth is limited by the rows alone
+MEMORY_BUDGET = 8 << 30                            # bytes of work areas and node slots one batch of trees may take
+GRID_KEYS = ("n_estimators", "max_depth", "min_samples_split", "min_samples_leaf", "max_features")
+_SKLEARN_DEFAULTS = dict(criterion="gini", class_weight=None, max_samples=None, max_leaf_nodes=None, ccp_alpha=0.0, min_impurity_decrease=0.0,
+                         oob_score=False, min_weight_fraction_leaf=0.0, warm_start=False, n_jobs=None, verbose=0, monotonic_cst=None, splitter="best")
+_TREE_KEYS = ("left", "right", "feature", "threshold", "value", "n_node_samples", "root")
+
+
+def _resolve_max_features(max_features, d, who):
+    """scikit-learn's ``max_features_`` for "sqrt", "log2", None or an int."""
+    if max_features is None:
+        return d
+    if isinstance(max_features, str):
+        if max_features == "sqrt":
+            return max(1, int(np.sqrt(d)))
+        if max_features == "log2":
+            return max(1, int(np.log2(d)))
+        raise ValueError(f"{who}: max_features must be 'sqrt', 'log2', None or an int, got {max_features!r}")
+    if not 1 <= max_features <= d:
+        raise ValueError(f"{who}: max_features = {max_features} outside 1..{d}")
+    return int(max_features)
+
+
+def _check_params(n_estimators, max_depth, min_samples_split, min_samples_leaf, max_features, who="RandomForestClassifier"):
+    if not _is_int(n_estimators) or n_estimators < 1:
+        raise ValueError(f"{who}: n_estimators must be an int >= 1, got {n_estimators!r}")
+    if max_depth is not None and (not _is_int(max_depth) or max_depth < 1):
+        raise ValueError(f"{who}: max_depth must be None or an int >= 1, got {max_depth!r}")
+    if not _is_int(min_samples_split):
+        raise NotImplementedError(f"{who}: min_samples_split must be an int >= 2 (fractions are not supported), got {min_samples_split!r}")
+    if min_samples_split < 2:
+        raise ValueError(f"{who}: min_samples_split must be an int >= 2, got {min_samples_split!r}")
+    if not _is_int(min_samples_leaf):
+        raise NotImplementedError(f"{who}: min_samples_leaf must be an int >= 1 (fractions are not supported), got {min_samples_leaf!r}")
+    if min_samples_leaf < 1:
+        raise ValueError(f"{who}: min_samples_leaf must be an int >= 1, got {min_samples_leaf!r}")
+    if isinstance(max_features, str) or max_features is None:
+        _resolve_max_features(max_features, 1, who)
+    elif not _is_int(max_features):
+        raise NotImplementedError(f"{who}: max_features must be 'sqrt', 'log2', None or an int (fractions are not supported), got {max_features!r}")
+    elif max_features < 1:
+        raise ValueError(f"{who}: max_features must be >= 1, got {max_features!r}")
+
+
+def _check_shape(n, d, who):
+    if n < 2 or d < 1:
+        raise ValueError(f"{who}: need at least two rows and one feature, got shape {(n, d)}")
+    if n > MAX_ROWS:
+        raise ValueError(f"{who}: n = {n} rows, at most {MAX_ROWS} are supported (BBBP_RF_FIT_MAX_N)")
+    if d > MAX_FEATURES:
+        raise ValueError(f"{who}: d = {d} features, at most {MAX_FEATURES} are supported (BBBP_RF_FIT_MAX_D)")
+
+
+def _training_matrix32(X, who):
+    """X as float32 [n, d], numpy (host) or a CUDA tensor, checked for shape and finiteness (``gradient_boosting._training_matrix32`` with
+    this module's limits in the messages)."""
+    if isinstance(X, torch.Tensor):
+        if not X.is_cuda:
+            raise RuntimeError(f"{who}: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
+        if X.dim() != 2:
+            raise ValueError(f"{who}: expected a 2-D [n, d] input, got shape {tuple(X.shape)}")
+        _check_shape(X.shape[0], X.shape[1], who)
+        X32 = X.to(torch.float32)
+        if not bool(torch.isfinite(X32).all()):
+            raise ValueError(f"{who}: X contains NaN, infinity or a value too large for float32")
+        return X32
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError(f"{who}: expected a 2-D [n, d] input, got shape {X.shape}")
+    _check_shape(X.shape[0], X.shape[1], who)
+    with np.errstate(over="ignore"):
+        X32 = np.ascontiguousarray(X, dtype=np.float32)
+    if not np.isfinite(X32).all():
+        raise ValueError(f"{who}: X contains NaN, infinity or a value too large for float32")
+    return X32
+
+
+class _Spec:
+    """One forest to grow: ``n_trees`` trees (numbers 0 .. n_trees - 1) over one matrix under one set of parameters."""
+
+    def __init__(self, mat, t_d, n_trees, max_depth, min_samples_split, min_samples_leaf, max_features, bootstrap, seed):
+        self.mat, self.t, self.T = mat, t_d, int(n_trees)
+        self.max_depth = UNLIMITED if max_depth is None else int(max_depth)
+        self.mss, self.msl, self.mf, self.bootstrap = int(min_samples_split), int(min_samples_leaf), int(max_features), bool(bootstrap)
+        self.seed = int(seed) & ((1 << 64) - 1)
+        L = _lib.lib()
+        self.work_bytes = L.bbbp_rf_fit_work_bytes(mat.n, mat.d, self.mf)
+        self.cap = L.bbbp_rf_fit_tree_capacity(mat.n)
+        if not self.work_bytes or not self.cap:
+            raise ValueError("random_forest: " + L.bbbp_last_error().decode("utf-8", "replace"))
+        self.trees = None                          # the flat host arrays, set by _grow
+
+
+_GROWN = {"trees": 0}                              # trees grown by this process (tests count them)
+
+
+def _grow(specs, budget=None):
+    """``bbbp_rf_fit`` over every tree of every spec, in batches whose work areas and node slots fit ``budget`` bytes.  Sets ``spec.trees``:
+    the flat host arrays in ``ForestGPU.flatten_sklearn``'s convention plus ``n_node_samples`` and the private ``value0``."""
+    budget = MEMORY_BUDGET if budget is None else int(budget)
+    dev = specs[0].mat.XT.device
+    L = _lib.lib()
+    todo = [(si, t) for si, s in enumerate(specs) for t in range(s.T)]
+    per_tree = max(s.work_bytes + s.cap * 40 for s in specs)
+    batch = int(max(1, min(65535, budget // per_tree)))
+    parts = {si: [] for si in range(len(specs))}
+    for lo in range(0, len(todo), batch):
+        chunk = todo[lo:lo + batch]
+        B = len(chunk)
+        cap = max(specs[si].cap for si, _ in chunk)
+        wb = max(specs[si].work_bytes for si, _ in chunk)
+        work = torch.empty(B * wb, dtype=torch.uint8, device=dev)
+        i32 = lambda: torch.empty((B, cap), dtype=torch.int32, device=dev)  # noqa: E731
+        f64 = lambda: torch.empty((B, cap), dtype=torch.float64, device=dev)  # noqa: E731
+        left, right, feature, nns, threshold, value, value0 = i32(), i32(), i32(), i32(), f64(), f64(), f64()
+        n_nodes = torch.empty(B, dtype=torch.int32, device=dev)
+        alive = torch.empty(1, dtype=torch.int32, device=dev)
+        descs = []
+        for b, (si, t) in enumerate(chunk):
+            s = specs[si]
+            descs.append(_lib.RfTree(s.mat.XT.data_ptr(), s.mat.order0.data_ptr(), s.t.data_ptr(), s.mat.n, s.mat.d, s.max_depth, s.mss, s.msl, s.mf,
+                                     int(s.bootstrap), t, s.seed, work.data_ptr() + b * wb, left.data_ptr() + 4 * b * cap, right.data_ptr() + 4 * b * cap,
+                                     feature.data_ptr() + 4 * b * cap, nns.data_ptr() + 4 * b * cap, threshold.data_ptr() + 8 * b * cap,
+                                     value.data_ptr() + 8 * b * cap, value0.data_ptr() + 8 * b * cap, n_nodes.data_ptr() + 4 * b))
+        arr = (_lib.RfTree * B)(*descs)
+        on_device = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+        _lib.check(L.bbbp_rf_fit(_dense.stream(), arr, on_device.data_ptr(), B, alive.data_ptr()), "bbbp_rf_fit")
+        _GROWN["trees"] += B
+        counts_d = n_nodes.to(torch.int64)
+        counts = counts_d.cpu().numpy()
+        if (counts < 1).any():
+            bad = chunk[int(np.argmax(counts < 1))]
+            raise RuntimeError(f"random_forest: the fit kernels reported an index outside its array in tree {bad[1]} (a defect of csrc/rf.hip, "
+                               "not of the data); no model is returned")
+        keep = torch.arange(cap, device=dev)[None, :] < counts_d[:, None]
+        host = [a[keep].cpu().numpy() for a in (left, right, feature, nns, threshold, value, value0)]      # only the slots in use cross the bus
+        ends = np.cumsum(counts)
+        for b, (si, t) in enumerate(chunk):
+            parts[si].append([a[ends[b] - counts[b]:ends[b]] for a in host])
+        del work, on_device
+    for si, s in enumerate(specs):
+        counts = np.array([len(p[0]) for p in parts[si]], dtype=np.int64)
+        root = np.concatenate([[0], np.cumsum(counts)])
+        offs = np.repeat(root[:-1], counts)
+        cat = lambda i: np.concatenate([p[i] for p in parts[si]])  # noqa: E731
+        l, r = cat(0).astype(np.int64), cat(1).astype(np.int64)
+        s.trees = dict(left=np.where(l >= 0, l + offs, -1).astype(np.int32), right=np.where(r >= 0, r + offs, -1).astype(np.int32), feature=cat(2),
+                       threshold=cat(4), value=cat(5), n_node_samples=cat(3), root=root.astype(np.int32), value0=cat(6))
+
+
+def _prune(trees, n_trees, max_depth, min_samples_split):
+    """The first ``n_trees`` trees as they grow under ``max_depth`` and ``min_samples_split``: a node at that depth or with fewer rows becomes a
+    leaf, what hangs below it goes, and the nodes are numbered level by level again."""
+    depth_limit = UNLIMITED if max_depth is None else int(max_depth)
+    left, right, root = trees["left"], trees["right"], trees["root"]
+    out = {k: [] for k in trees if k != "root"}
+    new_root = [0]
+    for t in range(n_trees):
+        level, depth, olds, lefts, rights = np.array([int(root[t])]), 0, [], [], []
+        at = new_root[-1]
+        while len(level):
+            split = (left[level] >= 0) & (trees["n_node_samples"][level] >= min_samples_split) & (depth < depth_limit)
+            first = at + len(level) + 2 * np.cumsum(split) - 2 * split           # the left child's new number
+            olds.append(level)
+            lefts.append(np.where(split, first, -1))
+            rights.append(np.where(split, first + 1, -1))
+            at += len(level)
+            level = np.stack([left[level[split]], right[level[split]]], axis=1).ravel()
+            depth += 1
+        old, nl = np.concatenate(olds), np.concatenate(lefts)
+        leaf = nl < 0
+        out["left"].append(nl.astype(np.int32))
+        out["right"].append(np.concatenate(rights).astype(np.int32))
+        out["feature"].append(np.where(leaf, 0, trees["feature"][old]).astype(np.int32))
+        out["threshold"].append(np.where(leaf, -2.0, trees["threshold"][old]))
+        for k in out:
+            if k not in ("left", "right", "feature", "threshold"):
+                out[k].append(trees[k][old])
+        new_root.append(at)
+    res = {k: np.concatenate(v) for k, v in out.items()}
+    res["root"] = np.asarray(new_root, dtype=np.int32)
+    return res
+
+
+def _check_trees(trees, n_features):
+    """Host-side validation of tree arrays handed to the predict kernel: every index it follows stays inside its arrays."""
+    left, right, feature, root = trees["left"], trees["right"], trees["feature"], trees["root"]
+    n_nodes = len(left)
+    if not all(len(trees[k]) == n_nodes for k in ("right", "feature", "threshold", "value", "n_node_samples")) or root[-1] != n_nodes or root[0] != 0:
+        raise ValueError("random_forest: tree arrays of unequal length")
+    if np.any(np.diff(root) < 1):
+        raise ValueError("random_forest: an empty tree")
+    split = left >= 0
+    if np.any(left[split] >= n_nodes) or np.any(right[split] < 0) or np.any(right[split] >= n_nodes) or np.any(feature < 0) or np.any(feature >= n_features):
+        raise ValueError("random_forest: a child or feature index outside its array")
+
+
+class RandomForestClassifier:
+    """``RandomForestClassifier(n_estimators=100, *, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features="sqrt",
+    bootstrap=True, random_state=0, device="cuda")``: scikit-learn's names for two classes and the Gini criterion.
+
+    ``fit`` takes a numpy array or a CUDA tensor [n, d] (n <= 8 192, d <= 1 024; cast to float32, as scikit-learn's trees do) and labels with
+    two distinct values.  It sets ``classes_``, ``n_features_in_``, ``n_estimators_`` and ``trees_``: ``left``, ``right``, ``feature``, float64
+    ``threshold``, ``value`` (the weighted share of ``classes_[1]`` in every node, inner nodes included), ``n_node_samples`` (distinct rows)
+    and ``root`` in ``ForestGPU.flatten_sklearn``'s convention, nodes numbered level by level.  ``random_state`` must be an int: without the
+    tie-breaking that scikit-learn's generator provides, the seed is part of the model.  ``predict_proba`` returns float64 [m, 2] (numpy for
+    numpy input, a CUDA tensor for a CUDA tensor); ``predict`` takes the larger probability, ties to ``classes_[0]``."""
+
+    _who = "RandomForestClassifier"
+
+    def __init__(self, n_estimators=100, *, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features="sqrt", bootstrap=True,
+                 random_state=0, device="cuda", **other):
+        who = self._who
+        for name, value in other.items():
+            if name not in _SKLEARN_DEFAULTS:
+                raise ValueError(f"{who}: unknown parameter {name}")
+            if value is not _SKLEARN_DEFAULTS[name] and not (isinstance(value, (numbers.Real, str)) and value == _SKLEARN_DEFAULTS[name]):
+                raise NotImplementedError(f"{who}: {name}={value!r} is not supported (only {_SKLEARN_DEFAULTS[name]!r})")
+        _check_params(n_estimators, max_depth, min_samples_split, min_samples_leaf, max_features, who)
+        if not _is_int(random_state):
+            raise ValueError(f"{who}: random_state must be an int (the seed is part of the model), got {random_state!r}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{who}: device {device!r}: trees are fitted on the GPU (no CPU fallback)")
+        self.n_estimators, self.max_depth = int(n_estimators), None if max_depth is None else int(max_depth)
+        self.min_samples_split, self.min_samples_leaf, self.max_features = int(min_samples_split), int(min_samples_leaf), max_features
+        self.bootstrap, self.random_state = bool(bootstrap), int(random_state)
+
+    # ---- fit --------------------------------------------------------------------------------------------------------
+    def fit(self, X, y, sample_weight=None):
+        who = self._who
+        if sample_weight is not None:
+            raise NotImplementedError(f"{who}: sample_weight is not supported")
+        classes, t = _binary_targets(y, None, who)
+        X32 = _training_matrix32(X, who)
+        if X32.shape[0] != len(t):
+            raise ValueError(f"{who}: X has {X32.shape[0]} rows, y has {len(t)}")
+        mf = _resolve_max_features(self.max_features, X32.shape[1], who)
+        with torch.cuda.device(self.device):
+            mat = _Matrix(X32, self.device)
+            spec = _Spec(mat, torch.from_numpy(t).to(self.device), self.n_estimators, self.max_depth, self.min_samples_split, self.min_samples_leaf, mf,
+                         self.bootstrap, self.random_state)
+            _grow([spec])
+            self._adopt(classes, spec)
+        return self
+
+    def _adopt(self, classes, spec, limits=None):
+        """Fitted attributes from a grown forest.  ``limits = (n_estimators, max_depth, min_samples_split)`` materialises the view of the
+        forest under those limits, pruned and renumbered: the model a single fit with those parameters gives."""
+        trees = spec.trees
+        if limits is not None:
+            T, depth, mss = limits
+            if T > spec.T or mss < spec.mss or (UNLIMITED if depth is None else depth) > spec.max_depth:
+                raise ValueError(f"{self._who}: limits {limits} ask for more than the forest was grown with")
+            trees = _prune(trees, int(T), depth, int(mss))
+        self._set_model(classes, {k: trees[k] for k in _TREE_KEYS}, trees["value0"], trees["value"], spec.mat.d)
+
+    def _set_model(self, classes, trees, p0, p1, n_features):
+        _check_trees(trees, n_features)
+        self.classes_, self.trees_, self.n_features_in_ = classes, trees, int(n_features)
+        self.n_estimators_ = len(trees["root"]) - 1
+        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)  # noqa: E731
+        self._dev = {k: to(trees[k], np.float64 if k == "threshold" else np.int32) for k in ("left", "right", "feature", "threshold", "n_node_samples", "root")}
+        self._dev["p0"], self._dev["p1"] = to(p0, np.float64), to(p1, np.float64)
+
+    @classmethod
+    def from_sklearn(cls, fitted, device="cuda"):
+        """Adopt a fitted scikit-learn ``RandomForestClassifier``, ``ExtraTreesClassifier`` or ``DecisionTreeClassifier`` (two classes, one
+        output) for prediction only: ``predict_proba`` equals scikit-learn's (fitted with ``n_jobs=None``) bit for bit."""
+        who = f"{cls.__name__}.from_sklearn"
+        if getattr(fitted, "n_outputs_", 1) != 1 or np.ndim(getattr(fitted, "n_classes_", 0)) != 0 or int(fitted.n_classes_) != 2:
+            raise ValueError(f"{who}: exactly two classes and one output are supported")
+        ests = list(fitted.estimators_) if hasattr(fitted, "estimators_") else [fitted]
+        left, right, feature, threshold, p0, p1, nns, root = [], [], [], [], [], [], [], [0]
+        for est in ests:
+            t, off = est.tree_, root[-1]
+            cl, cr = t.children_left.astype(np.int64), t.children_right.astype(np.int64)
+            left.append(np.where(cl >= 0, cl + off, -1)); right.append(np.where(cr >= 0, cr + off, -1))
+            feature.append(np.where(t.feature >= 0, t.feature, 0)); threshold.append(t.threshold)
+            p0.append(t.value[:, 0, 0]); p1.append(t.value[:, 0, 1]); nns.append(t.n_node_samples)
+            root.append(off + t.node_count)
+        if root[-1] >= 2 ** 31:
+            raise ValueError(f"{who}: forest too large for 32-bit node indices")
+        cat = np.concatenate
+        trees = dict(left=cat(left).astype(np.int32), right=cat(right).astype(np.int32), feature=cat(feature).astype(np.int32),
+                     threshold=cat(threshold).astype(np.float64), value=cat(p1).astype(np.float64), n_node_samples=cat(nns).astype(np.int32),
+                     root=np.asarray(root, dtype=np.int32))
+        self = cls.__new__(cls)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{who}: device {device!r}: prediction runs on the GPU (no CPU fallback)")
+        # the fitting parameters are kept only where this class would accept them: an adopted model predicts, it is not refitted
+        self.n_estimators = len(ests)
+        for name in ("max_depth", "min_samples_split", "min_samples_leaf", "max_features"):
+            v = getattr(fitted, name, None)
+            setattr(self, name, v if (_is_int(v) or (name == "max_features" and isinstance(v, str))) else None)
+        self.bootstrap, self.random_state = bool(getattr(fitted, "bootstrap", False)), None
+        self._set_model(np.asarray(fitted.classes_), trees, cat(p0).astype(np.float64), trees["value"], int(fitted.n_features_in_))
+        return self
+
+    # ---- prediction -------------------------------------------------------------------------------------------------
+    def _queries(self, X):
+        if not hasattr(self, "_dev"):
+            raise RuntimeError("random_forest: not fitted")
+        was_numpy = not isinstance(X, torch.Tensor)
+        if was_numpy:
+            X = np.asarray(X)
+            if X.ndim != 2:
+                raise ValueError(f"random_forest: expected a 2-D [m, d] input, got shape {X.shape}")
+            with np.errstate(over="ignore"):
+                X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
+        elif not X.is_cuda:
+            raise RuntimeError(f"random_forest: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
+        if X.dim() != 2 or X.shape[1] != self.n_features_in_:
+            raise ValueError(f"random_forest: the queries must be [m, {self.n_features_in_}], got shape {tuple(X.shape)}")
+        return X.to(self.device, torch.float32).contiguous(), was_numpy
+
+    def _proba(self, Xq, limits=None):
+        """float64 [m, 2] on the device; ``limits = (n_estimators, max_depth, min_samples_split)`` stops every walk as a fit under them would."""
+        m = Xq.shape[0]
+        out = torch.empty((m, 2), dtype=torch.float64, device=self.device)
+        if m == 0:
+            return out
+        T, depth, mss = (self.n_estimators_, None, 0) if limits is None else limits
+        if not 1 <= T <= self.n_estimators_:
+            raise ValueError(f"random_forest: {T} trees asked of a forest of {self.n_estimators_}")
+        t = self._dev
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().bbbp_rf_predict_proba(_dense.stream(), Xq.data_ptr(), Xq.shape[1], m, Xq.shape[1], t["left"].data_ptr(),
+                                                        t["right"].data_ptr(), t["feature"].data_ptr(), t["threshold"].data_ptr(), t["p0"].data_ptr(),
+                                                        t["p1"].data_ptr(), t["n_node_samples"].data_ptr(), t["root"].data_ptr(), int(T),
+                                                        UNLIMITED if depth is None else int(depth), int(mss), out.data_ptr()), "bbbp_rf_predict_proba")
+        return out
+
+    def predict_proba(self, X):
+        """[m, 2]: the trees' class shares at the leaves, summed in tree order and divided by the number of trees."""
+        Xq, was_numpy = self._queries(X)
+        out = self._proba(Xq)
+        return out.cpu().numpy() if was_numpy else out
+
+    def predict_log_proba(self, X):
+        """log of ``predict_proba`` (scikit-learn's: -inf where a probability is 0)."""
+        Xq, was_numpy = self._queries(X)
+        out = self._proba(Xq)
+        if not was_numpy:
+            return torch.log(out)
+        with np.errstate(divide="ignore"):
+            return np.log(out.cpu().numpy())
+
+    def predict(self, X):
+        """Class labels as a numpy array of ``classes_``' dtype: the larger probability, ties to ``classes_[0]`` (scikit-learn's argmax)."""
+        Xq, _ = self._queries(X)
+        p = self._proba(Xq)
+        return self.classes_[(p[:, 1] > p[:, 0]).cpu().numpy().astype(np.intp)]
+
+
+class DecisionTreeClassifier(RandomForestClassifier):
+    """``DecisionTreeClassifier(*, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features=None, bootstrap=False,
+    random_state=0, device="cuda")``: the same fit with one tree, every row once and all features at every node."""
+
+    _who = "DecisionTreeClassifier"
+
+    def __init__(self, *, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features=None, bootstrap=False, random_state=0, device="cuda",
+                 **other):
+        super().__init__(1, max_depth=max_depth, min_samples_split=min_samples_split, min_samples_leaf=min_samples_leaf, max_features=max_features,
+                         bootstrap=bootstrap, random_state=random_state, device=device, **other)
+
+
+def grid_points(param_grid, who="random_forest.grid_search_cv"):
+    """The grid's points in scikit-learn's order (sorted keys, ``itertools.product``; a list of grids one after the other) and each point's
+    full parameter tuple in ``GRID_KEYS``' order, checked."""
+    from itertools import product
+    points = []
+    for sub in ([param_grid] if isinstance(param_grid, dict) else list(param_grid)):
+        unknown = set(sub) - set(GRID_KEYS)
+        if unknown:
+            raise ValueError(f"{who}: unsupported grid keys {sorted(unknown)}")
+        keys = sorted(sub)
+        points += [dict(zip(keys, vals)) for vals in product(*(sub[k] for k in keys))]
+    if not points:
+        raise ValueError(f"{who}: the grid is empty")
+    defaults = dict(n_estimators=100, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features="sqrt")
+    full = [tuple({**defaults, **pt}[k] for k in GRID_KEYS) for pt in points]
+    for params in full:
+        _check_params(*params, who=who)
+    return points, full
+
+
+def _cv_forests(X32, t_all, folds, full, dev, random_state=0):
+    """One forest per (fold, distinct (min_samples_leaf, max_features)), grown with the largest ``n_estimators``, the smallest
+    ``min_samples_split`` and the largest ``max_depth`` asked of it, all in one call of ``_grow``.  Returns ({(fold, (min_samples_leaf,
+    max_features)): spec}, the folds' test rows on the device)."""
+    widest = {}
+    for T, depth, mss, msl, mf in full:
+        depth = UNLIMITED if depth is None else depth
+        old = widest.get((msl, mf), (0, 0, 1 << 30))
+        widest[(msl, mf)] = (max(old[0], T), max(old[1], depth), min(old[2], mss))
+    specs, queries = {}, []
+    for fi, (tr, te) in enumerate(folds):
+        mat = _Matrix(X32[tr], dev)
+        t_d = torch.from_numpy(t_all[tr]).to(dev)
+        queries.append(torch.from_numpy(X32[te]).to(dev))
+        for (msl, mf), (T, depth, mss) in widest.items():
+            specs[(fi, (msl, mf))] = _Spec(mat, t_d, T, None if depth >= UNLIMITED else depth, mss, msl,
+                                           _resolve_max_features(mf, mat.d, "random_forest.grid_search_cv"), True, random_state)
+    _grow(list(specs.values()))
+    return specs, queries
+
+
+def grid_search_cv(X, y, param_grid, cv: int = 5, device="cuda", random_state=0):
+    """The reference's ``GridSearchCV(RandomForestClassifier(), param_grid, cv=5, scoring='f1')`` (model_opt_maccs.py:124-200) over
+    ``n_estimators``, ``max_depth`` (None allowed), ``min_samples_split``, ``min_samples_leaf`` and ``max_features``.
+
+    Same conventions as ``gradient_boosting.grid_search_cv``: sorted keys, ``itertools.product`` order, scikit-learn's
+    ``StratifiedKFold(cv)``, ``f1_score`` of ``classes_[1]``, the first maximum wins.  Every fold grows one forest per distinct
+    (min_samples_leaf, max_features); every grid point is that forest seen through the predict kernel's limits and equals a single ``fit``
+    on that fold bit for bit; the refit on all rows follows.  Returns (best_params, mean F1 per point, the refitted classifier)."""
+    from sklearn.metrics import f1_score
+    from sklearn.model_selection import StratifiedKFold
+    who = "random_forest.grid_search_cv"
+    points, full = grid_points(param_grid, who)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who}: device {device!r}: trees are fitted on the GPU (no CPU fallback)")
+    X = np.asarray(X)
+    y = np.asarray(y)
+    classes, t_all = _binary_targets(y, X.shape[0] if X.ndim == 2 else None, who)
+    X32 = _training_matrix32(X, who)
+    pos = classes[1]
+    folds = list(StratifiedKFold(n_splits=cv).split(X32, y))
+    f1 = np.zeros((len(points), len(folds)))
+    with torch.cuda.device(dev):
+        specs, queries = _cv_forests(X32, t_all, folds, full, dev, random_state)
+        for (fi, group), spec in specs.items():
+            big = RandomForestClassifier(spec.T, min_samples_leaf=group[0], max_features=group[1], random_state=random_state, device=dev)
+            big._adopt(classes, spec)
+            seen = {}
+            for pi, params in enumerate(full):
+                if params[3:] != group:
+                    continue
+                if params[:3] not in seen:
+                    p = big._proba(queries[fi], params[:3])
+                    seen[params[:3]] = classes[(p[:, 1] > p[:, 0]).cpu().numpy().astype(np.intp)]
+                f1[pi, fi] = f1_score(y[folds[fi][1]], seen[params[:3]], pos_label=pos)
+        del specs, queries
+    scores = [float(v) for v in f1.mean(axis=1)]
+    best = int(np.argmax(scores))
+    T, depth, mss, msl, mf = full[best]
+    fitted = RandomForestClassifier(T, max_depth=depth, min_samples_split=mss, min_samples_leaf=msl, max_features=mf, random_state=random_state,
+                                    device=dev).fit(X32, y)
+    return points[best], scores, fitted

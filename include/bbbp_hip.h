@@ -587,6 +587,49 @@ int bbbp_gbt_staged_decision(void* stream, const float* X, long ld, int m, int d
                              const double* threshold, const double* value, const int* root, int n_trees, double init, double learning_rate,
                              const int* stages, int n_stages, double* out);
 
+/* ---- rf fit: random-forest classification trees fitted by exact split search (csrc/rf.hip) --------------------------------------
+ * RandomForestClassifier and DecisionTreeClassifier of the classification stack (Models/model_opt_maccs.py:124-200): two classes, Gini,
+ * bootstrap rows as integer weights, max_features candidate features per node.  bbbp_amd/random_forest.py composes the classifiers and
+ * grid_search_cv from these.  A descriptor is one tree; trees over one training matrix share XT and order0.  A tree owns capacity =
+ * 2 n - 1 slots of the seven node arrays; nodes are numbered level by level from the root 0, children are tree-relative, -1 marks a
+ * leaf (feature 0, threshold -2 there); value / value0 are the weighted class-1 / class-0 shares of every node, inner nodes included;
+ * n_node_samples counts distinct rows.  Depth is limited by the rows alone.  All random choices come from bbbp_rf_hash: the tree's key
+ * is hash(seed, tree_index), a child's key hash(key, side), bootstrap draw j is hash(hash(key(root), 0xB007), j) mapped to [0, n) by
+ * multiply-high, a node's candidates are the max_features non-constant features with the lowest hash(key, 2 + f). */
+#define BBBP_RF_FIT_MAX_N 8192
+#define BBBP_RF_FIT_MAX_D 1024
+#define BBBP_RF_MAX_WALK 8192            /* steps of one tree walk in the predict kernel; a longer walk yields NaN */
+typedef struct bbbp_rf_tree {
+    const float* XT;                           /* [d][n]: the training matrix, float32, one feature after the other */
+    const int* order0;                         /* [d][n]: per feature the row indices sorted stably by value */
+    const double* y;                           /* [n], 0.0 / 1.0 */
+    int n, d;
+    int max_depth;                             /* >= 1; any value >= n means unlimited */
+    int min_samples_split, min_samples_leaf, max_features, bootstrap;
+    int tree_index;                            /* the tree's number within its forest: a forest of fewer trees is a prefix */
+    unsigned long long seed;
+    void* work;                                /* bbbp_rf_fit_work_bytes(n, d, max_features) bytes, 16-byte aligned; need not be initialised */
+    int* left; int* right; int* feature; int* n_node_samples; double* threshold; double* value; double* value0;      /* [capacity] */
+    int* n_nodes;                              /* [1]: the tree's node count; -1 when an index left its array (a defect) */
+} bbbp_rf_tree;
+/* Node slots per tree, 2 n - 1 (0 with a message outside 2..BBBP_RF_FIT_MAX_N). */
+int bbbp_rf_fit_tree_capacity(int n);
+/* Bytes of a tree's `work` (0 with a message for n < 2, d < 1, n > BBBP_RF_FIT_MAX_N, d > BBBP_RF_FIT_MAX_D or max_features outside 1..d). */
+size_t bbbp_rf_fit_work_bytes(int n, int d, int max_features);
+/* The one hash behind every random choice of a fit: splitmix64's finaliser, mix(mix(a) + 0x9e3779b97f4a7c15 (b + 1)). */
+unsigned long long bbbp_rf_hash(unsigned long long a, unsigned long long b);
+/* Grow every tree, all side by side, one level per round of six launches.  Rounds are enqueued in blocks of eight; after each block the
+ * word *alive_device (device memory, one int) is read back: the only host read before the result.  `trees` is a host array,
+ * `trees_device` the same bytes in device memory.  A tree's numbers do not depend on what else is in the batch. */
+int bbbp_rf_fit(void* stream, const bbbp_rf_tree* trees, const bbbp_rf_tree* trees_device, int n_trees, int* alive_device);
+/* out[q] = (sum over the first n_trees trees, in tree order, of p0[leaf], of p1[leaf]) / n_trees for query rows X [m][d] float32
+ * (scikit-learn's forest arithmetic).  Children are absolute indices into the node arrays, root[t] is tree t's first node; a row goes
+ * left when (double)x[feature] <= threshold.  The walk stops at a node whose depth reaches max_depth or whose n_node_samples is below
+ * min_samples_split (the pruned view of a tree grown without those limits) and after BBBP_RF_MAX_WALK steps. */
+int bbbp_rf_predict_proba(void* stream, const float* X, long ld, int m, int d, const int* left, const int* right, const int* feature,
+                          const double* threshold, const double* p0, const double* p1, const int* n_node_samples, const int* root,
+                          int n_trees, int max_depth, int min_samples_split, double* out);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
