@@ -28,10 +28,21 @@
 //   side       one thread per row: the slot at the next level
 //   partition  one work-group per (feature, tree): every segment stably by side; rows of leaves stay where they are
 // Depth is not known in advance: rounds are enqueued in blocks of RF_BLOCK_ROUNDS, then one word is read that says whether any tree still grows.
+//
+// Regression trees (RandomForestRegressor / DecisionTreeRegressor of the logBB stack, Models/multi_input_data_regression_opt_transformer_cnn_opt.py:
+// 163-165; squared error) grow through the same rounds under a second criterion, chosen per launch by the kernels' template parameter.  The
+// targets arrive as integers q (|q| <= 2^49, the host rounds y to a dyadic grid) held in float64.  A row carries its weight w and w q (int64);
+// a node's S = sum w q (|S| <= 2^62) and W = sum w are exact integers, its value is (double)S / (double)W, its weight W goes to `value0`, and
+// it is a leaf when min q == max q.  The score of a position is scikit-learn's proxy on those sums,
+// (double)S_L (double)S_L / (double)W_L + (double)S_R (double)S_R / (double)W_R: two conversions, two products, two divisions and one add, each
+// rounded to nearest and none contracted, so a regression fit has no summation order either (tests/rfr_numpy.py).  `init`, `stats` and `split`
+// have a regression form; draw, choose, side and partition do not depend on the criterion.
 #include "common.h"
 #include "bbbp_hip.h"
 
+#include <limits.h>
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -40,6 +51,7 @@ constexpr int RF_BLOCK_ROUNDS = 8;            // levels enqueued between two rea
 constexpr unsigned RF_DEAD = 0xffffu;         // slot of a row that is in no node of the level
 constexpr int NODE_LEAF = 0, NODE_ACTIVE = 1;
 constexpr float RF_FEATURE_THRESHOLD = 1e-7f;
+constexpr double RF_MAX_TARGET = 0x1p49;         // |q| of a regression target
 constexpr unsigned long long RF_BOOT = 0xB007ull;          // the stream of a tree's bootstrap draws; features use 2 + f <= 1025, sides 0 and 1
 
 __host__ __device__ inline unsigned long long rf_mix(unsigned long long z) {          // the splitmix64 finaliser
@@ -59,6 +71,7 @@ __host__ __device__ inline int tree_capacity(int n) { return 2 * n - 1; }
 struct Work {                                 // offsets into a tree's `work`, in bytes; all multiples of 16
     size_t order[2], hist, wy, slot, tab_start[2], tab_cnt[2], tab_node[2], tab_key[2], flag, wtot, ndrawn, left_base, sp_rank, sp_feature, sp_thr,
         code, feat, cand_enc, cand_pos, state, total;
+    size_t wq, w16, stot, total_regression;     // a regression tree's rows (w q, w) and node sums S follow the classifier's area: `total` stays
 };
 __host__ __device__ inline Work work_layout(int n, int d, int mf) {
     Work w;
@@ -75,6 +88,8 @@ __host__ __device__ inline Work work_layout(int n, int d, int mf) {
     w.cand_enc = take(N * (size_t)mf * 8); w.cand_pos = take(N * (size_t)mf * 4);
     w.state = take(sizeof(TreeState));
     w.total = at;
+    w.wq = take(N * 8); w.w16 = take(N * 2); w.stot = take(N * 8);
+    w.total_regression = at;
     return w;
 }
 
@@ -82,6 +97,7 @@ struct View {                                 // a tree's work area, typed
     uint16_t *order_a, *order_b; unsigned* hist; unsigned* wy; uint16_t* slot; Table tab_a, tab_b;
     int* flag; unsigned* wtot; int *ndrawn, *left_base, *sp_rank, *sp_feature; double* sp_thr;
     uint16_t *code, *feat; unsigned long long* cand_enc; int* cand_pos; TreeState* st;
+    long long* wq; uint16_t* w16; long long* stot;          // inside `work` for a regression tree only; the Gini kernels never touch them
 };
 __device__ inline View view_of(const bbbp_rf_tree& c) {
     const Work w = work_layout(c.n, c.d, c.max_features);
@@ -96,6 +112,7 @@ __device__ inline View view_of(const bbbp_rf_tree& c) {
     v.code = (uint16_t*)(b + w.code); v.feat = (uint16_t*)(b + w.feat);
     v.cand_enc = (unsigned long long*)(b + w.cand_enc); v.cand_pos = (int*)(b + w.cand_pos);
     v.st = (TreeState*)(b + w.state);
+    v.wq = (long long*)(b + w.wq); v.w16 = (uint16_t*)(b + w.w16); v.stot = (long long*)(b + w.stot);
     return v;
 }
 // Level L reads order buffer L & 1 and table L & 1; `partition` and `choose` write the other one
@@ -120,6 +137,33 @@ __device__ inline void segment_of(const Table& tab, int k, int n_eff, TreeState*
     if (s < 0 || m < 1 || s > n_eff - m) { st->error = 1; s = 0; m = 0; }
 }
 
+// ---- the two criteria's sums: Gini's (weight, weight x class) packed in 32 bits, squared error's (sum of w q in 64 bits, weight) --------------
+struct Sum64 { long long s; unsigned w; };
+template <bool REG> using SumOf = std::conditional_t<REG, Sum64, unsigned>;
+__device__ inline unsigned sum_add(unsigned a, unsigned b) { return a + b; }
+__device__ inline Sum64 sum_add(Sum64 a, Sum64 b) { return Sum64{a.s + b.s, a.w + b.w}; }
+__device__ inline unsigned sum_sub(unsigned a, unsigned b) { return a - b; }
+__device__ inline Sum64 sum_sub(Sum64 a, Sum64 b) { return Sum64{a.s - b.s, a.w - b.w}; }
+__device__ inline unsigned sum_up(unsigned v, int off) { return (unsigned)__shfl_up((int)v, off); }
+__device__ inline Sum64 sum_up(Sum64 v, int off) { return Sum64{__shfl_up(v.s, off), (unsigned)__shfl_up((int)v.w, off)}; }
+// Gini: (W_R L_1 - W_L R_1)^2 / (W_L W_R); false when a side has no weight (cannot happen at a valid position)
+__device__ inline bool score_of(unsigned tot, unsigned left, double& score) {
+    const long long W = tot >> 16, W1 = tot & 0xffffu, WL = left >> 16, L1 = left & 0xffffu, WR = W - WL, R1 = W1 - L1;
+    if (WL <= 0 || WR <= 0) return false;
+    const long long diff = WR * L1 - WL * R1;                                          // |diff| <= 2^26: the square is exact in 64 bits and in a double
+    score = (double)(diff * diff) / (double)(WL * WR);
+    return true;
+}
+// squared error: S_L^2 / W_L + S_R^2 / W_R in float64, seven roundings and no contraction into fused multiply-adds
+__device__ inline bool score_of(Sum64 tot, Sum64 left, double& score) {
+#pragma clang fp contract(off)
+    if (left.w == 0u || left.w >= tot.w) return false;
+    const double SL = (double)left.s, SR = (double)(tot.s - left.s);
+    const double l = SL * SL / (double)left.w, r = SR * SR / (double)(tot.w - left.w);
+    score = l + r;
+    return true;
+}
+
 // ---- init: weights, the compacted orders, the root --------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rf_init_rows_kernel(const bbbp_rf_tree* trees) {
     const bbbp_rf_tree c = trees[blockIdx.y];
@@ -138,7 +182,7 @@ __global__ __launch_bounds__(256) void rf_init_boot_kernel(const bbbp_rf_tree* t
     const unsigned i = (unsigned)__umul64hi(rf_hash(stream, (unsigned long long)j), (unsigned long long)c.n);      // < n
     atomicAdd(&v.hist[i < (unsigned)c.n ? i : 0u], 1u);     // integer counts: the histogram does not depend on the order of the adds
 }
-__global__ __launch_bounds__(RF_SCAN) void rf_init_compact_kernel(const bbbp_rf_tree* trees) {
+template <bool REG> __global__ __launch_bounds__(RF_SCAN) void rf_init_compact_kernel(const bbbp_rf_tree* trees) {
     const bbbp_rf_tree c = trees[blockIdx.y];
     const View v = view_of(c);
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = c.n;
@@ -163,8 +207,16 @@ __global__ __launch_bounds__(RF_SCAN) void rf_init_compact_kernel(const bbbp_rf_
     }
     if (f != 0) return;
     for (int i = tid; i < n; i += RF_SCAN) {
-        const unsigned w = v.hist[i], y1 = c.y[i] > 0.5 ? 1u : 0u;
-        v.wy[i] = (w << 16) | (w * y1);                     // w <= n <= 8192: both halves stay below 2^16 in every partial sum
+        const unsigned w = v.hist[i];
+        if constexpr (REG) {
+            double q = c.y[i];
+            if (!(fabs(q) <= RF_MAX_TARGET)) { v.st->error = 1; q = 0.0; }           // NaN included: no conversion of a value outside int64
+            v.wq[i] = (long long)w * (long long)q;          // w <= n <= 8192 = 2^13: |w q| <= 2^62, and so is every sum over a tree's rows
+            v.w16[i] = (uint16_t)w;
+        } else {
+            const unsigned y1 = c.y[i] > 0.5 ? 1u : 0u;
+            v.wy[i] = (w << 16) | (w * y1);                 // w <= n <= 8192: both halves stay below 2^16 in every partial sum
+        }
         v.slot[i] = w ? (uint16_t)0 : (uint16_t)RF_DEAD;
     }
     if (tid == 0) {
@@ -206,6 +258,51 @@ __global__ __launch_bounds__(256) void rf_stats_kernel(const bbbp_rf_tree* trees
         } else {
             v.flag[k] = NODE_ACTIVE;
             v.st->active = 1;                               // every writer stores the same 1; `choose` clears it for the next level
+        }
+    }
+}
+
+// The regression form: S = sum w q, W = sum w, min q and max q over the node's rows; value = S / W, value0 = W
+__global__ __launch_bounds__(256) void rf_stats_regression_kernel(const bbbp_rf_tree* trees) {
+    const bbbp_rf_tree c = trees[blockIdx.y];
+    const View v = view_of(c);
+    if (v.st->done) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int level = v.st->level, nk = min(v.st->nk, c.n), n_eff = min(v.st->n_eff, c.n), cap = tree_capacity(c.n);
+    const Table tab = table_of(v, level);
+    const uint16_t* src = order_of(v, level);
+    for (int k = blockIdx.x * 4 + wave; k < nk; k += gridDim.x * 4) {
+        int s, m;
+        segment_of(tab, k, n_eff, v.st, s, m);
+        long long S = 0, lo = LLONG_MAX, hi = LLONG_MIN;
+        unsigned W = 0u;
+        for (int p = lane; p < m; p += 64) {
+            const int i = row_of(src, s + p, c.n, v.st);
+            const unsigned w = v.w16[i];
+            const long long wq = v.wq[i], q = w ? wq / (long long)w : 0;               // exact: wq is w times an integer
+            S += wq; W += w;
+            lo = q < lo ? q : lo; hi = q > hi ? q : hi;
+        }
+        for (int off = 32; off >= 1; off >>= 1) {
+            S += __shfl_xor(S, off); W += (unsigned)__shfl_xor((int)W, off);
+            const long long ol = __shfl_xor(lo, off), oh = __shfl_xor(hi, off);
+            lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi;
+        }
+        if (lane != 0) continue;
+        int node = tab.node[k];
+        if ((unsigned)node >= (unsigned)cap || W == 0u) { v.st->error = 1; node = 0; }
+        // scikit-learn's rule is impurity <= EPSILON; here a node is pure when all its targets are one integer (DESIGN.md compares the two)
+        const bool leaf = level >= c.max_depth || m < c.min_samples_split || m < 2 * c.min_samples_leaf || lo == hi;
+        c.n_node_samples[node] = m;
+        c.value[node] = W ? (double)S / (double)W : 0.0;
+        c.value0[node] = (double)W;
+        v.wtot[k] = W; v.stot[k] = S;
+        if (leaf) {
+            v.flag[k] = NODE_LEAF;
+            c.left[node] = -1; c.right[node] = -1; c.feature[node] = 0; c.threshold[node] = -2.0;
+        } else {
+            v.flag[k] = NODE_ACTIVE;
+            v.st->active = 1;
         }
     }
 }
@@ -266,7 +363,8 @@ __global__ __launch_bounds__(256) void rf_draw_kernel(const bbbp_rf_tree* trees)
 }
 
 // ---- split: the best (score, position) per (node, drawn feature) for one feature ----------------------------------------------------------
-__global__ __launch_bounds__(RF_SCAN) void rf_split_kernel(const bbbp_rf_tree* trees) {
+template <bool REG> __global__ __launch_bounds__(RF_SCAN) void rf_split_kernel(const bbbp_rf_tree* trees) {
+    using Sum = SumOf<REG>;
     const bbbp_rf_tree c = trees[blockIdx.y];
     const View v = view_of(c);
     if (v.st->done || !v.st->active) return;
@@ -275,13 +373,19 @@ __global__ __launch_bounds__(RF_SCAN) void rf_split_kernel(const bbbp_rf_tree* t
     const int level = v.st->level, nk = min(v.st->nk, n), n_eff = min(v.st->n_eff, n);
     const Table tab = table_of(v, level);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    unsigned* swy = reinterpret_cast<unsigned*>(smem);                            // [n] (weight, weight x class)
-    uint16_t* sslot = reinterpret_cast<uint16_t*>(swy + n);                       // [n]
-    __shared__ unsigned wave_val[4], carry_s;
+    // staged rows.  Gini: [n] (weight, weight x class) in 32 bits, [n] slots.  Squared error: [n] w q in 64 bits, [n] w, [n] slots
+    unsigned* swy = reinterpret_cast<unsigned*>(smem);
+    long long* swq = reinterpret_cast<long long*>(smem);
+    uint16_t* sw = reinterpret_cast<uint16_t*>(swq + n);
+    uint16_t* sslot = REG ? sw + n : reinterpret_cast<uint16_t*>(swy + n);
+    __shared__ Sum wave_val[4], carry_s;
     __shared__ int wave_flag[4], wave_pos[4];
     __shared__ unsigned long long wave_enc[4];
-    for (int i = tid; i < n; i += RF_SCAN) { swy[i] = v.wy[i]; sslot[i] = v.slot[i]; }
-    if (tid == 0) carry_s = 0u;
+    for (int i = tid; i < n; i += RF_SCAN) {
+        if constexpr (REG) { swq[i] = v.wq[i]; sw[i] = v.w16[i]; } else swy[i] = v.wy[i];
+        sslot[i] = v.slot[i];
+    }
+    if (tid == 0) carry_s = Sum{};
     __syncthreads();
     const uint16_t* src = order_of(v, level) + (long)f * n;
     const float* col = c.XT + (long)f * n;
@@ -293,34 +397,36 @@ __global__ __launch_bounds__(RF_SCAN) void rf_split_kernel(const bbbp_rf_tree* t
         const unsigned k = in ? sslot[i] : RF_DEAD;
         bool act = false;
         int s = 0, m = 0, j = 0;
-        unsigned wt = 0u;
+        Sum wt{};
         if (k != RF_DEAD) {
             if (k >= (unsigned)nk) v.st->error = 1;
             else if (v.flag[k] == NODE_ACTIVE) {
                 j = v.code[(long)k * d + f];
                 if (j > mf) { v.st->error = 1; j = 0; }
-                if (j > 0) { segment_of(tab, (int)k, n_eff, v.st, s, m); act = m > 0 && p >= s && p < s + m; wt = v.wtot[k]; }
+                if (j > 0) { segment_of(tab, (int)k, n_eff, v.st, s, m); act = m > 0 && p >= s && p < s + m;
+                             if constexpr (REG) wt = Sum64{v.stot[k], v.wtot[k]}; else wt = v.wtot[k]; }
             }
         }
-        const unsigned x = act ? swy[i] : 0u;
-        const unsigned carry = carry_s;                     // the inclusive sum at position base - 1, inside its segment
+        Sum x{};
+        if (act) { if constexpr (REG) x = Sum64{swq[i], sw[i]}; else x = swy[i]; }
+        const Sum carry = carry_s;                          // the inclusive sum at position base - 1, inside its segment
         // segmented inclusive scan inside the wave: a segment starts at its node's first position and at every position that is not scored
-        unsigned val = x;
+        Sum val = x;
         int flg = (!act || p == s) ? 1 : 0;
         const int own = flg;
         for (int off = 1; off < 64; off <<= 1) {
-            const unsigned pv = (unsigned)__shfl_up((int)val, off);
+            const Sum pv = sum_up(val, off);
             const int pf = __shfl_up(flg, off);
             if (lane >= off) {
-                if (!flg) val += pv;
+                if (!flg) val = sum_add(val, pv);
                 flg |= pf;
             }
         }
         if (lane == 63) { wave_val[wave] = val; wave_flag[wave] = flg; }
         __syncthreads();
-        unsigned pre = carry;                               // what precedes this wave in its first segment
-        for (int w = 0; w < wave; ++w) pre = wave_flag[w] ? wave_val[w] : pre + wave_val[w];
-        if (!flg) val += pre;
+        Sum pre = carry;                                    // what precedes this wave in its first segment
+        for (int w = 0; w < wave; ++w) pre = wave_flag[w] ? wave_val[w] : sum_add(pre, wave_val[w]);
+        if (!flg) val = sum_add(val, pre);
         if (tid == RF_SCAN - 1) carry_s = val;
         // the candidate between positions p - 1 and p
         unsigned long long enc = 0ull;
@@ -328,14 +434,9 @@ __global__ __launch_bounds__(RF_SCAN) void rf_split_kernel(const bbbp_rf_tree* t
             const int n_l = p - s, n_r = m - n_l;
             const float fv = col[i], fv_prev = col[row_of(src, p - 1, n, v.st)];
             if (fv > fv_prev + RF_FEATURE_THRESHOLD && n_l >= msl && n_r >= msl) {
-                const unsigned left = val - x;              // the exclusive sum: everything in front of p in the segment
-                const long long W = wt >> 16, W1 = wt & 0xffffu, WL = left >> 16, L1 = left & 0xffffu, WR = W - WL, R1 = W1 - L1;
-                if (WL <= 0 || WR <= 0) v.st->error = 1;
-                else {
-                    const long long diff = WR * L1 - WL * R1;                      // |diff| <= 2^26: the square is exact in 64 bits and in a double
-                    const double score = (double)(diff * diff) / (double)(WL * WR);
-                    enc = (unsigned long long)__double_as_longlong(score) + 1ull;  // scores are >= 0: their bits order as integers; 0 = none
-                }
+                double score = 0.0;
+                if (!score_of(wt, sum_sub(val, x), score)) v.st->error = 1;        // the exclusive sum: everything in front of p in the segment
+                else enc = (unsigned long long)__double_as_longlong(score) + 1ull;     // scores are >= 0: their bits order as integers; 0 = none
             }
         }
         // segmented arg-max with the same segments: the lowest position among equal scores
@@ -368,7 +469,7 @@ __global__ __launch_bounds__(RF_SCAN) void rf_split_kernel(const bbbp_rf_tree* t
         __syncthreads();                                    // the next pass may merge into the same slot from another wave
     }
 }
-size_t split_lds_bytes(int n) { return (size_t)n * 6; }
+size_t split_lds_bytes(int n, bool regression) { return (size_t)n * (regression ? 12 : 6); }
 
 // ---- choose: the best drawn feature per node, its threshold and children, the next level's table ---------------------------------------
 __device__ inline void block_scan2(int& a, int& b, int* tmp, int tid) {       // inclusive sums over the 256 threads; tmp: [2][4] ints
@@ -526,7 +627,7 @@ struct PredictArgs {
     const int *left, *right, *feature; const double *threshold, *p0, *p1; const int *n_node_samples, *root;
     int n_trees, max_depth, min_samples_split; double* out;
 };
-__global__ __launch_bounds__(256) void rf_predict_kernel(PredictArgs a) {
+template <bool MEAN> __global__ __launch_bounds__(256) void rf_predict_kernel(PredictArgs a) {         // MEAN: one value per node (p1), out [m]
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.m) return;
     const float* x = a.X + (long)i * a.ld;
@@ -541,11 +642,14 @@ __global__ __launch_bounds__(256) void rf_predict_kernel(PredictArgs a) {
             ++depth;
         }
         const bool lost = l >= 0 && depth >= BBBP_RF_MAX_WALK && depth < a.max_depth;
-        s0 = lost ? __builtin_nan("") : s0 + a.p0[node];    // scikit-learn's forest: the trees' probabilities summed in tree order
+        if constexpr (!MEAN) s0 = lost ? __builtin_nan("") : s0 + a.p0[node];          // scikit-learn's forest: the trees' outputs summed in tree order
         s1 = lost ? __builtin_nan("") : s1 + a.p1[node];
     }
-    a.out[2 * (long)i] = s0 / (double)a.n_trees;
-    a.out[2 * (long)i + 1] = s1 / (double)a.n_trees;
+    if constexpr (MEAN) a.out[i] = s1 / (double)a.n_trees;
+    else {
+        a.out[2 * (long)i] = s0 / (double)a.n_trees;
+        a.out[2 * (long)i + 1] = s1 / (double)a.n_trees;
+    }
 }
 
 int check_tree(const bbbp_rf_tree& c, int q) {
@@ -572,17 +676,28 @@ extern "C" int bbbp_rf_fit_tree_capacity(int n) {
     return tree_capacity(n);
 }
 
+namespace {
+bool check_work_shape(const char* who, int n, int d, int max_features) {
+    if (n < 2 || d < 1) { bbbp_set_error("%s: n >= 2 and d >= 1 must hold, got n %d d %d", who, n, d); return false; }
+    if (n > BBBP_RF_FIT_MAX_N) { bbbp_set_error("%s: n %d exceeds BBBP_RF_FIT_MAX_N %d", who, n, BBBP_RF_FIT_MAX_N); return false; }
+    if (d > BBBP_RF_FIT_MAX_D) { bbbp_set_error("%s: d %d exceeds BBBP_RF_FIT_MAX_D %d", who, d, BBBP_RF_FIT_MAX_D); return false; }
+    if (max_features < 1 || max_features > d) { bbbp_set_error("%s: max_features %d outside 1..d = %d", who, max_features, d); return false; }
+    return true;
+}
+}  // namespace
+
 extern "C" size_t bbbp_rf_fit_work_bytes(int n, int d, int max_features) {
-    if (n < 2 || d < 1) { bbbp_set_error("rf_fit_work_bytes: n >= 2 and d >= 1 must hold, got n %d d %d", n, d); return 0; }
-    if (n > BBBP_RF_FIT_MAX_N) { bbbp_set_error("rf_fit_work_bytes: n %d exceeds BBBP_RF_FIT_MAX_N %d", n, BBBP_RF_FIT_MAX_N); return 0; }
-    if (d > BBBP_RF_FIT_MAX_D) { bbbp_set_error("rf_fit_work_bytes: d %d exceeds BBBP_RF_FIT_MAX_D %d", d, BBBP_RF_FIT_MAX_D); return 0; }
-    if (max_features < 1 || max_features > d) { bbbp_set_error("rf_fit_work_bytes: max_features %d outside 1..d = %d", max_features, d); return 0; }
-    return work_layout(n, d, max_features).total;
+    return check_work_shape("rf_fit_work_bytes", n, d, max_features) ? work_layout(n, d, max_features).total : 0;
+}
+
+extern "C" size_t bbbp_rf_fit_regression_work_bytes(int n, int d, int max_features) {
+    return check_work_shape("rf_fit_regression_work_bytes", n, d, max_features) ? work_layout(n, d, max_features).total_regression : 0;
 }
 
 extern "C" unsigned long long bbbp_rf_hash(unsigned long long a, unsigned long long b) { return rf_hash(a, b); }
 
-extern "C" int bbbp_rf_fit(void* stream, const bbbp_rf_tree* trees, const bbbp_rf_tree* trees_device, int n_trees, int* alive_device) {
+namespace {
+template <bool REG> int fit_trees(void* stream, const bbbp_rf_tree* trees, const bbbp_rf_tree* trees_device, int n_trees, int* alive_device) {
     BBBP_CHECK_ARG(trees && trees_device && alive_device, "rf_fit: null pointer");
     BBBP_CHECK_ARG(n_trees >= 1 && n_trees <= 65535, "rf_fit: n_trees %d outside 1..65535", n_trees);
     int max_n = 0, max_d = 0;
@@ -592,23 +707,23 @@ extern "C" int bbbp_rf_fit(void* stream, const bbbp_rf_tree* trees, const bbbp_r
         max_d = trees[q].d > max_d ? trees[q].d : max_d;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t split_lds = split_lds_bytes(max_n), part_lds = partition_lds_bytes(max_n);
-    if (int rc = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(rf_split_kernel), split_lds)) return rc;
+    const size_t split_lds = split_lds_bytes(max_n, REG), part_lds = partition_lds_bytes(max_n);      // 12 n reaches 96 KB of the CU's 160 KB at n = 8192
+    if (int rc = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(rf_split_kernel<REG>), split_lds)) return rc;
     if (int rc = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(rf_partition_kernel), part_lds)) return rc;
     const unsigned T = (unsigned)n_trees;
     const dim3 rows((unsigned)cdiv(max_n, 256), T), feats((unsigned)max_d, T), nodes((unsigned)clampi(cdiv(max_n, 64), 1, 32), T), one(T);
     hipLaunchKernelGGL(rf_init_rows_kernel, rows, dim3(256), 0, st, trees_device);
     hipLaunchKernelGGL(rf_init_boot_kernel, rows, dim3(256), 0, st, trees_device);
-    hipLaunchKernelGGL(rf_init_compact_kernel, feats, dim3(RF_SCAN), 0, st, trees_device);
+    hipLaunchKernelGGL(rf_init_compact_kernel<REG>, feats, dim3(RF_SCAN), 0, st, trees_device);
     BBBP_CHECK_LAUNCH();
     // a tree of n rows has at most n - 1 levels that split, and one more round to find that nothing is left
     const int max_blocks = max_n / RF_BLOCK_ROUNDS + 2;
     for (int b = 0; b < max_blocks; ++b) {
         BBBP_CHECK_HIP(hipMemsetAsync(alive_device, 0, sizeof(int), st));
         for (int r = 0; r < RF_BLOCK_ROUNDS; ++r) {
-            hipLaunchKernelGGL(rf_stats_kernel, nodes, dim3(256), 0, st, trees_device);
+            hipLaunchKernelGGL(REG ? rf_stats_regression_kernel : rf_stats_kernel, nodes, dim3(256), 0, st, trees_device);
             hipLaunchKernelGGL(rf_draw_kernel, nodes, dim3(256), 0, st, trees_device);
-            hipLaunchKernelGGL(rf_split_kernel, feats, dim3(RF_SCAN), split_lds, st, trees_device);
+            hipLaunchKernelGGL(rf_split_kernel<REG>, feats, dim3(RF_SCAN), split_lds, st, trees_device);
             hipLaunchKernelGGL(rf_choose_kernel, one, dim3(256), 0, st, trees_device, alive_device, r == RF_BLOCK_ROUNDS - 1 ? 1 : 0);
             hipLaunchKernelGGL(rf_side_kernel, rows, dim3(256), 0, st, trees_device);
             hipLaunchKernelGGL(rf_partition_kernel, feats, dim3(RF_SCAN), part_lds, st, trees_device);
@@ -622,6 +737,15 @@ extern "C" int bbbp_rf_fit(void* stream, const bbbp_rf_tree* trees, const bbbp_r
     bbbp_set_error("rf_fit: a tree still grows after %d levels", max_blocks * RF_BLOCK_ROUNDS);
     return BBBP_ERR_HIP;
 }
+}  // namespace
+
+extern "C" int bbbp_rf_fit(void* stream, const bbbp_rf_tree* trees, const bbbp_rf_tree* trees_device, int n_trees, int* alive_device) {
+    return fit_trees<false>(stream, trees, trees_device, n_trees, alive_device);
+}
+
+extern "C" int bbbp_rf_fit_regression(void* stream, const bbbp_rf_tree* trees, const bbbp_rf_tree* trees_device, int n_trees, int* alive_device) {
+    return fit_trees<true>(stream, trees, trees_device, n_trees, alive_device);
+}
 
 extern "C" int bbbp_rf_predict_proba(void* stream, const float* X, long ld, int m, int d, const int* left, const int* right, const int* feature,
                                      const double* threshold, const double* p0, const double* p1, const int* n_node_samples, const int* root,
@@ -632,7 +756,21 @@ extern "C" int bbbp_rf_predict_proba(void* stream, const float* X, long ld, int 
                    max_depth, min_samples_split);
     BBBP_CHECK_ARG(X && left && right && feature && threshold && p0 && p1 && n_node_samples && root && out, "rf_predict_proba: null pointer");
     PredictArgs a{X, ld, m, d, left, right, feature, threshold, p0, p1, n_node_samples, root, n_trees, max_depth, min_samples_split, out};
-    hipLaunchKernelGGL(rf_predict_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(rf_predict_kernel<false>, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    BBBP_CHECK_LAUNCH();
+    return BBBP_OK;
+}
+
+extern "C" int bbbp_rf_predict_mean(void* stream, const float* X, long ld, int m, int d, const int* left, const int* right, const int* feature,
+                                    const double* threshold, const double* value, const int* n_node_samples, const int* root, int n_trees,
+                                    int max_depth, int min_samples_split, double* out) {
+    BBBP_CHECK_ARG(m >= 1 && d >= 1, "rf_predict_mean: m and d must be positive, got m %d d %d", m, d);
+    BBBP_CHECK_ARG(ld >= d, "rf_predict_mean: leading dimension %ld below d %d", ld, d);
+    BBBP_CHECK_ARG(n_trees >= 1 && max_depth >= 0 && min_samples_split >= 0, "rf_predict_mean: n_trees %d, max_depth %d, min_samples_split %d", n_trees,
+                   max_depth, min_samples_split);
+    BBBP_CHECK_ARG(X && left && right && feature && threshold && value && n_node_samples && root && out, "rf_predict_mean: null pointer");
+    PredictArgs a{X, ld, m, d, left, right, feature, threshold, nullptr, value, n_node_samples, root, n_trees, max_depth, min_samples_split, out};
+    hipLaunchKernelGGL(rf_predict_kernel<true>, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     BBBP_CHECK_LAUNCH();
     return BBBP_OK;
 }

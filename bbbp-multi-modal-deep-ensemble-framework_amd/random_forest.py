@@ -26,9 +26,18 @@ certified (``tests/rf_replay.py``), not compared with scikit-learn's.
 A tree's probabilities are scikit-learn 1.7's: the leaf's stored class shares ``value`` (already divided by the node's weight when the
 tree was built; ``tree_.predict`` returns them as they are), summed over trees in tree order in float64 and divided by the number of trees.
 
-Out of scope (each is refused by name): more than two classes, ``criterion != "gini"``, ``sample_weight``, ``class_weight``,
-``max_samples``, ``max_leaf_nodes``, ``ccp_alpha``, ``min_impurity_decrease != 0``, fractional ``min_samples_*``, ``oob_score``, more than
-8 192 rows or 1 024 features, regression forests, more than one GPU.  There is no CPU path.
+Out of scope for the classifiers (each is refused by name): more than two classes, ``criterion != "gini"``, ``sample_weight``,
+``class_weight``, ``max_samples``, ``max_leaf_nodes``, ``ccp_alpha``, ``min_impurity_decrease != 0``, fractional ``min_samples_*``,
+``oob_score``, more than 8 192 rows or 1 024 features, more than one GPU.  There is no CPU path.
+
+``RandomForestRegressor`` and ``DecisionTreeRegressor`` are the logBB stack's forest
+(``Models/multi_input_data_regression_opt_transformer_cnn_opt.py:163-165``: ``RandomForestRegressor(n_estimators=300, max_depth=15,
+random_state=42)`` on the 64 + 128 PCA features, five folds; ``..._20250113.py:394-403`` refits it six times inside ``StackingRegressor``)
+under the squared-error criterion.  They grow through the same rounds (``bbbp_rf_fit_regression``): the targets are rounded once to a
+dyadic grid 49 bits below the binade of ``max |y|`` so that a node's sums are exact 64-bit integers, a candidate's score is scikit-learn's
+proxy ``S_L^2 / W_L + S_R^2 / W_R`` on those sums in seven float64 roundings, and ``tests/rfr_numpy.py`` reproduces a fit bit for bit.
+``fit_regressors`` grows the forests of many ``(X, y)`` problems, the folds and the stacker's refits, in one batch;
+``bbbp_rf_predict_mean`` predicts.  The regressors' docstring lists what they refuse.
 """
 from __future__ import annotations
 
@@ -120,15 +129,16 @@ def _training_matrix32(X, who):
 
 
 class _Spec:
-    """One forest to grow: ``n_trees`` trees (numbers 0 .. n_trees - 1) over one matrix under one set of parameters."""
+    """One forest to grow: ``n_trees`` trees (numbers 0 .. n_trees - 1) over one matrix under one set of parameters.  ``t_d`` holds the class
+    indicator 0.0 / 1.0, or with ``regression`` the integer targets ``q`` of ``_quantise``, as float64 on the device."""
 
-    def __init__(self, mat, t_d, n_trees, max_depth, min_samples_split, min_samples_leaf, max_features, bootstrap, seed):
-        self.mat, self.t, self.T = mat, t_d, int(n_trees)
+    def __init__(self, mat, t_d, n_trees, max_depth, min_samples_split, min_samples_leaf, max_features, bootstrap, seed, regression=False):
+        self.mat, self.t, self.T, self.regression = mat, t_d, int(n_trees), bool(regression)
         self.max_depth = UNLIMITED if max_depth is None else int(max_depth)
         self.mss, self.msl, self.mf, self.bootstrap = int(min_samples_split), int(min_samples_leaf), int(max_features), bool(bootstrap)
         self.seed = int(seed) & ((1 << 64) - 1)
         L = _lib.lib()
-        self.work_bytes = L.bbbp_rf_fit_work_bytes(mat.n, mat.d, self.mf)
+        self.work_bytes = (L.bbbp_rf_fit_regression_work_bytes if self.regression else L.bbbp_rf_fit_work_bytes)(mat.n, mat.d, self.mf)
         self.cap = L.bbbp_rf_fit_tree_capacity(mat.n)
         if not self.work_bytes or not self.cap:
             raise ValueError("random_forest: " + L.bbbp_last_error().decode("utf-8", "replace"))
@@ -139,9 +149,14 @@ _GROWN = {"trees": 0}                              # trees grown by this process
 
 
 def _grow(specs, budget=None):
-    """``bbbp_rf_fit`` over every tree of every spec, in batches whose work areas and node slots fit ``budget`` bytes.  Sets ``spec.trees``:
-    the flat host arrays in ``ForestGPU.flatten_sklearn``'s convention plus ``n_node_samples`` and the private ``value0``."""
+    """``bbbp_rf_fit`` (``bbbp_rf_fit_regression`` for regression specs; one call grows one kind) over every tree of every spec, in batches
+    whose work areas and node slots fit ``budget`` bytes.  Sets ``spec.trees``: the flat host arrays in ``ForestGPU.flatten_sklearn``'s
+    convention plus ``n_node_samples`` and the private ``value0`` (the class-0 share; a regression node's weight)."""
     budget = MEMORY_BUDGET if budget is None else int(budget)
+    regression = specs[0].regression
+    if any(s.regression != regression for s in specs):
+        raise ValueError("random_forest: classification and regression forests cannot grow in one batch")
+    fit_name = "bbbp_rf_fit_regression" if regression else "bbbp_rf_fit"
     dev = specs[0].mat.XT.device
     L = _lib.lib()
     todo = [(si, t) for si, s in enumerate(specs) for t in range(s.T)]
@@ -168,7 +183,7 @@ def _grow(specs, budget=None):
                                      value.data_ptr() + 8 * b * cap, value0.data_ptr() + 8 * b * cap, n_nodes.data_ptr() + 4 * b))
         arr = (_lib.RfTree * B)(*descs)
         on_device = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        _lib.check(L.bbbp_rf_fit(_dense.stream(), arr, on_device.data_ptr(), B, alive.data_ptr()), "bbbp_rf_fit")
+        _lib.check(getattr(L, fit_name)(_dense.stream(), arr, on_device.data_ptr(), B, alive.data_ptr()), fit_name)
         _GROWN["trees"] += B
         counts_d = n_nodes.to(torch.int64)
         counts = counts_d.cpu().numpy()
@@ -237,6 +252,24 @@ def _check_trees(trees, n_features):
     split = left >= 0
     if np.any(left[split] >= n_nodes) or np.any(right[split] < 0) or np.any(right[split] >= n_nodes) or np.any(feature < 0) or np.any(feature >= n_features):
         raise ValueError("random_forest: a child or feature index outside its array")
+
+
+def _query_matrix(model, X, device):
+    """The queries of a fitted classifier or regressor as float32 [m, d] on ``device``, and whether they came as numpy."""
+    if not hasattr(model, "_dev"):
+        raise RuntimeError("random_forest: not fitted")
+    was_numpy = not isinstance(X, torch.Tensor)
+    if was_numpy:
+        X = np.asarray(X)
+        if X.ndim != 2:
+            raise ValueError(f"random_forest: expected a 2-D [m, d] input, got shape {X.shape}")
+        with np.errstate(over="ignore"):
+            X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
+    elif not X.is_cuda:
+        raise RuntimeError(f"random_forest: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
+    if X.dim() != 2 or X.shape[1] != model.n_features_in_:
+        raise ValueError(f"random_forest: the queries must be [m, {model.n_features_in_}], got shape {tuple(X.shape)}")
+    return X.to(device, torch.float32).contiguous(), was_numpy
 
 
 class RandomForestClassifier:
@@ -344,20 +377,7 @@ class RandomForestClassifier:
 
     # ---- prediction -------------------------------------------------------------------------------------------------
     def _queries(self, X):
-        if not hasattr(self, "_dev"):
-            raise RuntimeError("random_forest: not fitted")
-        was_numpy = not isinstance(X, torch.Tensor)
-        if was_numpy:
-            X = np.asarray(X)
-            if X.ndim != 2:
-                raise ValueError(f"random_forest: expected a 2-D [m, d] input, got shape {X.shape}")
-            with np.errstate(over="ignore"):
-                X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
-        elif not X.is_cuda:
-            raise RuntimeError(f"random_forest: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
-        if X.dim() != 2 or X.shape[1] != self.n_features_in_:
-            raise ValueError(f"random_forest: the queries must be [m, {self.n_features_in_}], got shape {tuple(X.shape)}")
-        return X.to(self.device, torch.float32).contiguous(), was_numpy
+        return _query_matrix(self, X, self.device)
 
     def _proba(self, Xq, limits=None):
         """float64 [m, 2] on the device; ``limits = (n_estimators, max_depth, min_samples_split)`` stops every walk as a fit under them would."""
@@ -493,3 +513,233 @@ def grid_search_cv(X, y, param_grid, cv: int = 5, device="cuda", random_state=0)
     fitted = RandomForestClassifier(T, max_depth=depth, min_samples_split=mss, min_samples_leaf=msl, max_features=mf, random_state=random_state,
                                     device=dev).fit(X32, y)
     return points[best], scores, fitted
+
+
+# ---- regression: RandomForestRegressor and DecisionTreeRegressor under the squared-error criterion ---------------------------------------
+TARGET_BITS = 49                                   # |q| <= 2^49: with weights summing to n <= 2^13 every sum of w q stays within 2^62
+_REGRESSOR_DEFAULTS = dict(criterion="squared_error", max_samples=None, max_leaf_nodes=None, ccp_alpha=0.0, min_impurity_decrease=0.0, oob_score=False,
+                           min_weight_fraction_leaf=0.0, warm_start=False, n_jobs=None, verbose=0, monotonic_cst=None, splitter="best")
+
+
+def _quantise(y, n_rows, who):
+    """The targets on their dyadic grid: (q, s) with ``q = rint(y 2^s)`` (integers held in float64, ``|q| <= 2^TARGET_BITS``) and
+    ``s = TARGET_BITS - e``, ``(_, e) = frexp(max |y|)``; ``s = 0`` when all of y is 0."""
+    y = np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y)
+    if y.ndim == 2 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.ndim != 1:
+        raise NotImplementedError(f"{who}: multi-output targets are not supported, got y of shape {y.shape}")
+    try:
+        y = np.ascontiguousarray(y, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: y must be numeric, got dtype {y.dtype}") from None
+    if len(y) != n_rows:
+        raise ValueError(f"{who}: X has {n_rows} rows, y has {len(y)}")
+    if not np.isfinite(y).all():
+        raise ValueError(f"{who}: y contains NaN or infinity")
+    top = float(np.abs(y).max())
+    s = 0 if top == 0.0 else TARGET_BITS - int(np.frexp(top)[1])
+    return np.rint(np.ldexp(y, s)), s
+
+
+class RandomForestRegressor:
+    """``RandomForestRegressor(n_estimators=100, *, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features=1.0, bootstrap=True,
+    random_state=0, device="cuda")``: scikit-learn's names for one output and the squared-error criterion -- the reference's
+    ``RandomForestRegressor(n_estimators=300, max_depth=15, random_state=42)`` (Models/multi_input_data_regression_opt_transformer_cnn_opt.py:163-165).
+
+    ``fit`` takes a numpy array or a CUDA tensor [n, d] (n <= 8 192, d <= 1 024; cast to float32) and finite float64 targets [n].  The targets
+    are rounded once to a dyadic grid, ``y_hat = rint(y 2^s) 2^-s`` with ``2^-s = y_quantum_`` (49 bits below the binade of ``max |y|``: within
+    ``2^-50 2^e`` of y, 7e-15 for ``|y| < 8``), and the model is by definition scikit-learn's tree on ``(X, y_hat)``: every node's sums are
+    exact integers, a candidate's score is ``S_L S_L / W_L + S_R S_R / W_R`` in seven float64 roundings, so a fit has no summation order,
+    ``tests/rfr_numpy.py`` reproduces it bit for bit, and a tree is the same alone, in any batch and run to run.  A node is pure when all its
+    targets are one grid point (scikit-learn: ``impurity <= 2.2e-16``; the rules differ only for nodes whose spread is below about 1e-8).
+    The bootstrap, the per-node feature draw, the valid positions, the thresholds, the tie rule and the numbering are the classifier's, and so
+    are the pruning and prefix properties.  ``max_features`` takes 1.0 or None (all features), "sqrt", "log2" or an int.
+
+    Sets ``n_features_in_``, ``n_estimators_``, ``y_quantum_``, ``trees_`` (``value`` the node mean of ``y_hat``, ``n_node_samples`` distinct
+    rows) and ``weighted_n_node_samples_``.  ``predict`` is scikit-learn's: leaf values summed in tree order in float64, divided by the number
+    of trees; float64 numpy for numpy queries, a CUDA tensor for a CUDA tensor.  ``get_params`` / ``set_params`` make ``sklearn.base.clone``
+    work, so ``ensemble.StackingRegressor`` takes this class as a base learner.
+
+    Out of scope, each refused with a message: more than 1 024 features (the reference's raw [N, 49 319] hstack needs a work layout without
+    a per-tree copy of every column's order), ``criterion != "squared_error"``, ``sample_weight``, ``oob_score``, ``max_samples``,
+    multi-output targets, ``feature_importances_``.  There is no regressor grid search (the reference has none) and no CPU path."""
+
+    _who = "RandomForestRegressor"
+    _params = ("n_estimators", "max_depth", "min_samples_split", "min_samples_leaf", "max_features", "bootstrap", "random_state", "device")
+
+    def __init__(self, n_estimators=100, *, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features=1.0, bootstrap=True,
+                 random_state=0, device="cuda", **other):
+        who = self._who
+        for name, value in other.items():
+            if name not in _REGRESSOR_DEFAULTS:
+                raise ValueError(f"{who}: unknown parameter {name}")
+            if value is not _REGRESSOR_DEFAULTS[name] and not (isinstance(value, (numbers.Real, str)) and value == _REGRESSOR_DEFAULTS[name]):
+                raise NotImplementedError(f"{who}: {name}={value!r} is not supported (only {_REGRESSOR_DEFAULTS[name]!r})")
+        _check_params(n_estimators, max_depth, min_samples_split, min_samples_leaf, self._all_features(max_features), who)
+        if not _is_int(random_state):
+            raise ValueError(f"{who}: random_state must be an int (the seed is part of the model), got {random_state!r}")
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"{who}: device {device!r}: trees are fitted on the GPU (no CPU fallback)")
+        # the parameters are kept as they were given: sklearn.base.clone compares them by identity
+        self.n_estimators, self.max_depth, self.min_samples_split, self.min_samples_leaf = n_estimators, max_depth, min_samples_split, min_samples_leaf
+        self.max_features, self.bootstrap, self.random_state, self.device = max_features, bootstrap, random_state, device
+
+    @staticmethod
+    def _all_features(max_features):
+        """scikit-learn's regressor default ``max_features=1.0`` means every feature, like None."""
+        return None if isinstance(max_features, float) and max_features == 1.0 else max_features
+
+    def get_params(self, deep=True):
+        return {name: getattr(self, name) for name in self._params}
+
+    def set_params(self, **params):
+        unknown = set(params) - set(self._params)
+        if unknown:
+            raise ValueError(f"{self._who}: unknown parameters {sorted(unknown)}")
+        type(self)(**{**self.get_params(), **params})          # the constructor's checks
+        for name, value in params.items():
+            setattr(self, name, value)
+        return self
+
+    def __getattr__(self, name):
+        if name in ("feature_importances_", "oob_score_", "oob_prediction_"):
+            raise AttributeError(f"{self._who}: {name} is not supported")
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    # ---- fit --------------------------------------------------------------------------------------------------------
+    def fit(self, X, y, sample_weight=None):
+        if sample_weight is not None:
+            raise NotImplementedError(f"{self._who}: sample_weight is not supported")
+        _fit_regressors([self], [(X, y)])
+        return self
+
+    def _checked(self, X, y):
+        """(float32 X, the integer targets, the grid's exponent, max_features as a count), validated: no GPU call yet."""
+        who = self._who
+        X32 = _training_matrix32(X, who)
+        q, s = _quantise(y, X32.shape[0], who)
+        return X32, q, s, _resolve_max_features(self._all_features(self.max_features), X32.shape[1], who)
+
+    def _spec(self, X32, q, mf):
+        """The forest this regressor asks for, not yet grown."""
+        dev = torch.device(self.device)
+        return _Spec(_Matrix(X32, dev), torch.from_numpy(q).to(dev), self.n_estimators, self.max_depth, self.min_samples_split, self.min_samples_leaf,
+                     mf, self.bootstrap, self.random_state, regression=True)
+
+    def _adopt(self, spec, s, limits=None):
+        """Fitted attributes from a grown forest whose values are in units of ``2^-s``; ``limits`` as ``RandomForestClassifier._adopt``."""
+        trees = spec.trees
+        if limits is not None:
+            T, depth, mss = limits
+            if T > spec.T or mss < spec.mss or (UNLIMITED if depth is None else depth) > spec.max_depth:
+                raise ValueError(f"{self._who}: limits {limits} ask for more than the forest was grown with")
+            trees = _prune(trees, int(T), depth, int(mss))
+        model = {k: trees[k] for k in _TREE_KEYS}
+        model["value"] = np.ldexp(trees["value"], -s)          # an exact power of two
+        self._set_model(model, spec.mat.d)
+        self.y_quantum_, self.weighted_n_node_samples_ = float(np.ldexp(1.0, -s)), trees["value0"]
+
+    def _set_model(self, trees, n_features):
+        _check_trees(trees, n_features)
+        dev = torch.device(self.device)
+        self.trees_, self.n_features_in_, self.n_estimators_ = trees, int(n_features), len(trees["root"]) - 1
+        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
+        self._dev = {k: to(trees[k], np.float64 if k in ("threshold", "value") else np.int32) for k in _TREE_KEYS}
+
+    @classmethod
+    def from_sklearn(cls, fitted, device="cuda"):
+        """Adopt a fitted scikit-learn ``RandomForestRegressor``, ``ExtraTreesRegressor`` or ``DecisionTreeRegressor`` (one output) for
+        prediction only: ``predict`` equals scikit-learn's (fitted with ``n_jobs=None``) bit for bit."""
+        who = f"{cls.__name__}.from_sklearn"
+        if hasattr(fitted, "classes_") or getattr(fitted, "n_outputs_", 1) != 1:
+            raise ValueError(f"{who}: a fitted regressor with one output is expected")
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"{who}: device {device!r}: prediction runs on the GPU (no CPU fallback)")
+        ests = list(fitted.estimators_) if hasattr(fitted, "estimators_") else [fitted]
+        left, right, feature, threshold, value, nns, root = [], [], [], [], [], [], [0]
+        for est in ests:
+            t, off = est.tree_, root[-1]
+            cl, cr = t.children_left.astype(np.int64), t.children_right.astype(np.int64)
+            left.append(np.where(cl >= 0, cl + off, -1)); right.append(np.where(cr >= 0, cr + off, -1))
+            feature.append(np.where(t.feature >= 0, t.feature, 0)); threshold.append(t.threshold)
+            value.append(t.value[:, 0, 0]); nns.append(t.n_node_samples)
+            root.append(off + t.node_count)
+        if root[-1] >= 2 ** 31:
+            raise ValueError(f"{who}: forest too large for 32-bit node indices")
+        cat = np.concatenate
+        trees = dict(left=cat(left).astype(np.int32), right=cat(right).astype(np.int32), feature=cat(feature).astype(np.int32),
+                     threshold=cat(threshold).astype(np.float64), value=cat(value).astype(np.float64), n_node_samples=cat(nns).astype(np.int32),
+                     root=np.asarray(root, dtype=np.int32))
+        self = cls.__new__(cls)
+        # the fitting parameters are kept only where this class would accept them: an adopted model predicts, it is not refitted
+        self.n_estimators, self.device = len(ests), device
+        for name in ("max_depth", "min_samples_split", "min_samples_leaf", "max_features"):
+            v = getattr(fitted, name, None)
+            setattr(self, name, v if (_is_int(v) or (name == "max_features" and (isinstance(v, str) or v == 1.0))) else None)
+        self.bootstrap, self.random_state = bool(getattr(fitted, "bootstrap", False)), None
+        self._set_model(trees, int(fitted.n_features_in_))
+        return self
+
+    # ---- prediction -------------------------------------------------------------------------------------------------
+    def _queries(self, X):
+        return _query_matrix(self, X, torch.device(self.device))
+
+    def _mean(self, Xq, limits=None):
+        """float64 [m] on the device; ``limits = (n_estimators, max_depth, min_samples_split)`` stops every walk as a fit under them would."""
+        m = Xq.shape[0]
+        out = torch.empty(m, dtype=torch.float64, device=Xq.device)
+        if m == 0:
+            return out
+        T, depth, mss = (self.n_estimators_, None, 0) if limits is None else limits
+        if not 1 <= T <= self.n_estimators_:
+            raise ValueError(f"random_forest: {T} trees asked of a forest of {self.n_estimators_}")
+        t = self._dev
+        with torch.cuda.device(Xq.device):
+            _lib.check(_lib.lib().bbbp_rf_predict_mean(_dense.stream(), Xq.data_ptr(), Xq.shape[1], m, Xq.shape[1], t["left"].data_ptr(),
+                                                       t["right"].data_ptr(), t["feature"].data_ptr(), t["threshold"].data_ptr(), t["value"].data_ptr(),
+                                                       t["n_node_samples"].data_ptr(), t["root"].data_ptr(), int(T),
+                                                       UNLIMITED if depth is None else int(depth), int(mss), out.data_ptr()), "bbbp_rf_predict_mean")
+        return out
+
+    def predict(self, X):
+        """[m] float64: the trees' leaf means summed in tree order and divided by the number of trees."""
+        Xq, was_numpy = self._queries(X)
+        out = self._mean(Xq)
+        return out.cpu().numpy() if was_numpy else out
+
+
+class DecisionTreeRegressor(RandomForestRegressor):
+    """``DecisionTreeRegressor(*, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features=None, bootstrap=False, random_state=0,
+    device="cuda")``: the same fit with one tree, every row once and all features at every node."""
+
+    _who = "DecisionTreeRegressor"
+    _params = RandomForestRegressor._params[1:]
+
+    def __init__(self, *, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features=None, bootstrap=False, random_state=0, device="cuda",
+                 **other):
+        super().__init__(1, max_depth=max_depth, min_samples_split=min_samples_split, min_samples_leaf=min_samples_leaf, max_features=max_features,
+                         bootstrap=bootstrap, random_state=random_state, device=device, **other)
+
+
+def _fit_regressors(regressors, problems):
+    """Grow the forests of ``regressors[i]`` over ``problems[i] = (X, y)`` in one ``_grow`` call and fit every regressor from its own."""
+    checked = [reg._checked(X, y) for reg, (X, y) in zip(regressors, problems)]
+    with torch.cuda.device(torch.device(regressors[0].device)):
+        specs = [reg._spec(X32, q, mf) for reg, (X32, q, _, mf) in zip(regressors, checked)]
+        _grow(specs)
+        for reg, spec, (_, _, s, _) in zip(regressors, specs, checked):
+            reg._adopt(spec, s)
+
+
+def fit_regressors(problems, **params):
+    """``[RandomForestRegressor(**params).fit(X, y) for X, y in problems]`` with every tree of every problem grown in one batch: the
+    reference's five folds of 300 trees and the stacker's six refits are one call.  Each regressor equals its single ``fit`` bit for bit."""
+    problems = list(problems)
+    if not problems:
+        raise ValueError("random_forest.fit_regressors: no problems")
+    regressors = [RandomForestRegressor(**params) for _ in problems]
+    if len({str(torch.device(r.device)) for r in regressors}) != 1:
+        raise ValueError("random_forest.fit_regressors: one device")
+    _fit_regressors(regressors, problems)
+    return regressors

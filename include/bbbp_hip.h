@@ -629,6 +629,21 @@ int bbbp_rf_fit(void* stream, const bbbp_rf_tree* trees, const bbbp_rf_tree* tre
 int bbbp_rf_predict_proba(void* stream, const float* X, long ld, int m, int d, const int* left, const int* right, const int* feature,
                           const double* threshold, const double* p0, const double* p1, const int* n_node_samples, const int* root,
                           int n_trees, int max_depth, int min_samples_split, double* out);
+/* Regression trees under the squared-error criterion (RandomForestRegressor / DecisionTreeRegressor of the logBB stack,
+ * Models/multi_input_data_regression_opt_transformer_cnn_opt.py:163-165): bbbp_rf_fit with the same descriptor, rounds, bootstrap, feature
+ * draw, valid positions, thresholds and numbering.  y [n] holds integers q with |q| <= 2^49 as float64 (the caller rounds its targets to a
+ * dyadic grid, q = rint(y 2^s), and scales the values back by 2^-s).  With S = sum w q (an exact int64) and W = sum w over a node's rows:
+ * value = (double)S / (double)W, value0 = (double)W; a node whose targets are all one integer is a leaf; a position scores
+ * (double)S_L (double)S_L / (double)W_L + (double)S_R (double)S_R / (double)W_R, every operation rounded to nearest, none fused.
+ * `work` takes bbbp_rf_fit_regression_work_bytes(n, d, max_features) bytes: bbbp_rf_fit_work_bytes' plus 18 n for the rows' w q, w and the
+ * nodes' S.  The limits BBBP_RF_FIT_MAX_N / _MAX_D and every argument check are bbbp_rf_fit's and run before any GPU call. */
+size_t bbbp_rf_fit_regression_work_bytes(int n, int d, int max_features);
+int bbbp_rf_fit_regression(void* stream, const bbbp_rf_tree* trees, const bbbp_rf_tree* trees_device, int n_trees, int* alive_device);
+/* out[q] = (sum over the first n_trees trees, in tree order, of value[leaf]) / n_trees, float64 [m] (scikit-learn's regression forest):
+ * bbbp_rf_predict_proba's walk and limits with one value per node. */
+int bbbp_rf_predict_mean(void* stream, const float* X, long ld, int m, int d, const int* left, const int* right, const int* feature,
+                         const double* threshold, const double* value, const int* n_node_samples, const int* root, int n_trees,
+                         int max_depth, int min_samples_split, double* out);
 
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
