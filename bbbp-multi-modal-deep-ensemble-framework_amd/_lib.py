@@ -86,6 +86,12 @@ class SvmDecisionDesc(Structure):
                 ("slices", c_int)]
 
 
+class SvrProblem(Structure):
+    """bbbp_svr_problem (include/bbbp_hip.h)."""
+    _fields_ = [("K", c_void_p), ("ldk", c_long), ("rows", c_void_p), ("t", c_void_p), ("alpha", c_void_p), ("grad", c_void_p), ("diag", c_void_p),
+                ("rho", c_void_p), ("n_iter", c_void_p), ("done", c_void_p), ("n", c_int), ("C", c_double), ("epsilon", c_double), ("tol", c_double)]
+
+
 class LogregProblem(Structure):
     """bbbp_logreg_problem (include/bbbp_hip.h)."""
     _fields_ = [("X", c_void_p), ("x_dtype", c_int), ("ld", c_long), ("n", c_int), ("d", c_int), ("t", c_void_p), ("C", c_double), ("tol", c_double),
@@ -161,7 +167,8 @@ _SIGNATURES = {
     "bbbp_svm_smo": (c_int, [c_void_p, POINTER(SvmProblem), c_int, c_int]),
     "bbbp_svm_decision_workspace_bytes": (c_size_t, [POINTER(SvmDecisionDesc)]),
     "bbbp_svm_decision": (c_int, [c_void_p, POINTER(SvmDecisionDesc), c_void_p, c_size_t]),
-    "bbbp_logreg_state_bytes": (c_size_t, [c_int, c_int]),
+    "bbbp_svr_smo": (c_int, [c_void_p, POINTER(SvrProblem), c_int, c_int]),
+    "bbbp_logreg_state_bytes":(c_size_t, [c_int, c_int]),
     "bbbp_logreg_state_layout": (c_int, [c_int, c_int, POINTER(c_long)]),
     "bbbp_logreg_rounds": (c_int, [c_void_p, POINTER(LogregProblem), c_int, c_int]),
     "bbbp_logreg_eval": (c_int, [c_void_p, POINTER(LogregProblem)]),

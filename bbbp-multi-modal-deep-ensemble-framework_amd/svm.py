@@ -1,4 +1,5 @@
-"""``sklearn.svm.SVC`` for the GPU: binary C-support-vector classification in float64, linear and RBF kernels.
+"""``sklearn.svm.SVC`` and ``sklearn.svm.SVR`` for the GPU: binary C-support-vector classification and epsilon-support-vector regression in
+float64, linear and RBF kernels.
 
 The classification stack of the reference (``Models/model_opt_maccs.py:124-180``) searches ``SVC()`` over ``C in {0.1, 1, 10} x kernel in
 {linear, rbf}`` under ``GridSearchCV(cv=5, scoring='f1')``, behind StandardScaler, ``PCA(100)`` and SMOTE.  Three entry points of
@@ -14,6 +15,11 @@ The classification stack of the reference (``Models/model_opt_maccs.py:124-180``
 
 ``SVC``: ``fit`` / ``decision_function`` / ``predict`` with scikit-learn's attributes and sign convention (a positive decision value means
 ``classes_[1]``); ``grid_search_cv``: the reference's grid, one batch of problems per fold.
+
+``SVR``: epsilon-support-vector regression, the kernel learner of the regression stack
+(``Models/multi_input_data_regression_opt_transformer_cnn_opt_more.py:117-149``), over the same matrix and decision function; its 2n-variable
+dual is ``bbbp_svr_smo`` of ``csrc/svr.hip``, which keeps a problem's state in registers for a whole launch.  ``fit_svr_folds``: the
+reference's five folds in one batch; ``grid_search_cv_svr``: ``GridSearchCV(SVR(), grid)`` with R^2 over unshuffled folds.
 
 Two correct SMO runs of one problem agree to about ``tol``, not to rounding: scikit-learn itself moves by that much between a data set and
 its reversal.  Results here are bit-identical from run to run and do not depend on what else is solved in the same batch.
@@ -35,6 +41,7 @@ from . import _dense, _lib
 
 KERNELS = {"linear": 0, "rbf": 1}          # BBBP_SVM_LINEAR / BBBP_SVM_RBF
 ITERS_PER_LAUNCH = 2000                    # iterations per problem and launch up to ITERS_REFERENCE_N rows: DESIGN.md gives the measured time of one
+SVR_ITERS_PER_LAUNCH = 2000                # the same for bbbp_svr_smo: 5.3 us an iteration at 850 rows, 27 us at 8 000
 ITERS_REFERENCE_N = 8000                   # an iteration reads O(n): beyond this n the count shrinks in proportion, so a launch keeps its length
 
 
@@ -138,11 +145,14 @@ class _Problem:
                                     self.flags.data_ptr() + 4, n, float(C), float(tol))
 
 
-def _solve(problems, max_iter=-1, iters_per_launch=None):
-    """Run ``bbbp_svm_smo`` until every problem is done (or has run ``max_iter`` iterations).  Returns per problem (n_iter, converged)."""
+def _solve(problems, max_iter=-1, iters_per_launch=None, entry="bbbp_svm_smo"):
+    """Run ``bbbp_svm_smo`` (or ``entry``, for ``_SvrProblem``s) until every problem is done (or has run ``max_iter`` iterations).
+    Returns per problem (n_iter, converged)."""
     n_max = max(p.n for p in problems)
-    per = int(iters_per_launch or max(1, ITERS_PER_LAUNCH * ITERS_REFERENCE_N // max(n_max, ITERS_REFERENCE_N)))
+    base = ITERS_PER_LAUNCH if entry == "bbbp_svm_smo" else SVR_ITERS_PER_LAUNCH
+    per = int(iters_per_launch or max(1, base * ITERS_REFERENCE_N // max(n_max, ITERS_REFERENCE_N)))
     L = _lib.lib()
+    kind = type(problems[0].desc)
     state = [[0, False] for _ in problems]
     live = list(range(len(problems)))
     ran = 0
@@ -150,14 +160,37 @@ def _solve(problems, max_iter=-1, iters_per_launch=None):
         step = per if max_iter < 0 else min(per, max_iter - ran)
         if step <= 0:
             break
-        arr = (_lib.SvmProblem * len(live))(*[problems[q].desc for q in live])
-        _lib.check(L.bbbp_svm_smo(_dense.stream(), arr, len(live), step), "bbbp_svm_smo")
+        arr = (kind * len(live))(*[problems[q].desc for q in live])
+        _lib.check(getattr(L, entry)(_dense.stream(), arr, len(live), step), entry)
         ran += step
         flags = torch.stack([problems[q].flags for q in live]).cpu().numpy()      # the host read that ends the launch
         for q, (n_iter, done) in zip(live, flags):
             state[q] = [int(n_iter), bool(done)]
         live = [q for q in live if not state[q][1]]
     return [tuple(s) for s in state]
+
+
+def _decision(model, dev, Xq, slices=0):
+    """``bbbp_svm_decision`` of a fitted ``SVC`` or ``SVR`` on the device matrix Xq: sum_s coef_s k(sv_s, x) + intercept, float64 [m]."""
+    if not hasattr(model, "_sv"):
+        raise RuntimeError("svm: not fitted")
+    m, d = Xq.shape
+    if d != model.n_features_in_:
+        raise ValueError(f"svm: the queries have {d} features, the fit saw {model.n_features_in_}")
+    with torch.cuda.device(dev):
+        qn = _norms(Xq, model._mean_d, "the query set") if m else None
+        out = torch.full((m,), float(model.intercept_[0]), dtype=torch.float64, device=dev)
+        n_sv = model._sv.shape[0]
+        if m == 0 or n_sv == 0:
+            return out
+        rbf = model.kernel == "rbf"
+        desc = _lib.SvmDecisionDesc(m, n_sv, d, KERNELS[model.kernel], float(model._gamma), Xq.data_ptr(), _dense.DT[Xq.dtype], _dense.ld(Xq),
+                                    model._sv.data_ptr(), _dense.DT[model._sv.dtype], _dense.ld(model._sv), model._mean_d.data_ptr() if rbf else None,
+                                    qn.data_ptr() if rbf else None, model._sv_norms.data_ptr() if rbf else None, model._coef_d.data_ptr(),
+                                    float(model.intercept_[0]), out.data_ptr(), int(slices))
+        L = _lib.lib()
+        _dense.launch_with_workspace(L.bbbp_svm_decision_workspace_bytes, L.bbbp_svm_decision, desc, dev, "bbbp_svm_decision")
+    return out
 
 
 class SVC:
@@ -222,25 +255,7 @@ class SVC:
 
     # ---- decision ---------------------------------------------------------------------------------------------------
     def _decision(self, Xq, slices=0):
-        if not hasattr(self, "_sv"):
-            raise RuntimeError("svm: not fitted")
-        m, d = Xq.shape
-        if d != self.n_features_in_:
-            raise ValueError(f"svm: the queries have {d} features, the fit saw {self.n_features_in_}")
-        with torch.cuda.device(self.device):
-            qn = _norms(Xq, self._mean_d, "the query set") if m else None
-            out = torch.full((m,), float(self.intercept_[0]), dtype=torch.float64, device=self.device)
-            n_sv = self._sv.shape[0]
-            if m == 0 or n_sv == 0:
-                return out
-            rbf = self.kernel == "rbf"
-            desc = _lib.SvmDecisionDesc(m, n_sv, d, KERNELS[self.kernel], float(self._gamma), Xq.data_ptr(), _dense.DT[Xq.dtype], _dense.ld(Xq),
-                                        self._sv.data_ptr(), _dense.DT[self._sv.dtype], _dense.ld(self._sv), self._mean_d.data_ptr() if rbf else None,
-                                        qn.data_ptr() if rbf else None, self._sv_norms.data_ptr() if rbf else None, self._coef_d.data_ptr(),
-                                        float(self.intercept_[0]), out.data_ptr(), int(slices))
-            L = _lib.lib()
-            _dense.launch_with_workspace(L.bbbp_svm_decision_workspace_bytes, L.bbbp_svm_decision, desc, self.device, "bbbp_svm_decision")
-        return out
+        return _decision(self, self.device, Xq, slices)
 
     def decision_function(self, X, *, slices=0):
         """f(x) for every row of X.  ``slices`` > 0 forces how many work-groups share a query tile's support vectors (a test hook: the
@@ -329,4 +344,267 @@ def grid_search_cv(X, y, param_grid, cv: int = 5, device="cuda", *, tol=1e-3, ma
     best = int(np.argmax(scores))
     C, kernel, gamma = full[best]
     fitted = SVC(C, kernel, gamma, tol, max_iter, device=dev).fit(X, y)
+    return points[best], scores, fitted
+
+
+# ---- epsilon-support-vector regression ---------------------------------------------------------------------------------------------------
+def _check_epsilon(epsilon, who):
+    if isinstance(epsilon, bool) or not isinstance(epsilon, numbers.Real) or not (0.0 <= float(epsilon) < float("inf")):
+        raise ValueError(f"{who}: epsilon must be a non-negative finite number, got {epsilon!r}")
+
+
+def _targets(y, n, who="SVR"):
+    """y as a float64 numpy vector: real, 1-D, finite, ``n`` long (None: any length)."""
+    if isinstance(y, torch.Tensor):
+        y = y.detach().cpu().numpy()
+    y = np.asarray(y)
+    if y.ndim != 1:
+        raise ValueError(f"{who}: y must be 1-D, got shape {y.shape}")
+    if y.dtype.kind not in "fiub":
+        raise ValueError(f"{who}: y must hold real numbers, got dtype {y.dtype}")
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if not np.isfinite(y).all():
+        raise ValueError(f"{who}: y contains NaN or infinity")
+    if n is not None and len(y) != n:
+        raise ValueError(f"{who}: X has {n} rows, y has {len(y)}")
+    return y
+
+
+class _SvrProblem:
+    """One epsilon-SVR dual problem on the device: state, outputs and the descriptor ``bbbp_svr_smo`` takes.  The solver's first launch
+    sets alpha and the gradient itself: the host initialises the two flags only."""
+
+    def __init__(self, K, t_d, C, epsilon, tol, rows=None):
+        dev = K.device
+        n = t_d.numel()
+        self.K, self.t, self.rows, self.n, self.C, self.epsilon = K, t_d, rows, n, float(C), float(epsilon)
+        self.alpha = torch.empty(2 * n, dtype=torch.float64, device=dev)
+        self.grad = torch.empty(2 * n, dtype=torch.float64, device=dev)
+        self.diag = torch.empty(n, dtype=torch.float64, device=dev)
+        self.rho = torch.empty(1, dtype=torch.float64, device=dev)
+        self.flags = torch.zeros(2, dtype=torch.int32, device=dev)       # n_iter, done
+        self.desc = _lib.SvrProblem(K.data_ptr(), K.stride(0), None if rows is None else rows.data_ptr(), t_d.data_ptr(), self.alpha.data_ptr(),
+                                    self.grad.data_ptr(), self.diag.data_ptr(), self.rho.data_ptr(), self.flags.data_ptr(),
+                                    self.flags.data_ptr() + 4, n, float(C), float(epsilon), float(tol))
+
+
+def _solve_svr(problems, max_iter=-1, iters_per_launch=None):
+    return _solve(problems, max_iter, iters_per_launch, entry="bbbp_svr_smo")
+
+
+class SVR:
+    """``SVR(kernel="rbf", C=1.0, epsilon=0.1, gamma="scale", tol=1e-3, max_iter=-1, *, device="cuda", shrinking=False)``: scikit-learn's
+    names.
+
+    ``fit`` takes a CUDA tensor or a numpy array, float32 or float64, [n, d], and real targets [n].  ``predict`` returns float64 [m]: a
+    numpy array for numpy input, a CUDA tensor for a CUDA tensor; ``predict_device`` always a CUDA tensor.  ``support_`` lists the rows
+    with alpha - alpha* != 0 in ascending order; ``dual_coef_`` [1, n_SV] holds those differences, ``intercept_`` [1] is -rho.
+    ``shrinking`` is accepted and ignored.  ``get_params`` / ``set_params`` make the class clone under ``sklearn.base.clone``, so it serves
+    as a base learner of ``ensemble.StackingRegressor``."""
+
+    _params = ("kernel", "C", "epsilon", "gamma", "tol", "max_iter", "device", "shrinking")
+
+    def __init__(self, kernel="rbf", C=1.0, epsilon=0.1, gamma="scale", tol=1e-3, max_iter=-1, *, device="cuda", shrinking=False, **unsupported):
+        if unsupported:
+            raise ValueError(f"SVR: unsupported parameters {sorted(unsupported)}")
+        _check_params(C, kernel, gamma, tol, max_iter, "SVR")
+        _check_epsilon(epsilon, "SVR")
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"SVR: device {device!r}: the solver runs on the GPU (no CPU fallback)")
+        self.kernel, self.C, self.epsilon, self.gamma, self.tol, self.max_iter = kernel, C, epsilon, gamma, tol, max_iter
+        self.device, self.shrinking = device, shrinking
+
+    def get_params(self, deep=True):
+        return {name: getattr(self, name) for name in self._params}
+
+    def set_params(self, **params):
+        unknown = set(params) - set(self._params)
+        if unknown:
+            raise ValueError(f"SVR: unknown parameters {sorted(unknown)}")
+        type(self)(**{**self.get_params(), **params})          # the constructor's checks
+        for name, value in params.items():
+            setattr(self, name, value)
+        return self
+
+    # ---- fit --------------------------------------------------------------------------------------------------------
+    def fit(self, X, y, sample_weight=None):
+        if sample_weight is not None:
+            raise ValueError("SVR: sample_weight is not supported")
+        t = _targets(y, None)
+        dev = torch.device(self.device)
+        X, _ = _dense.to_device_matrix(X, dev, "svm", allow_row_stride=True)
+        if X.shape[0] != len(t):
+            raise ValueError(f"SVR: X has {X.shape[0]} rows, y has {len(t)}")
+        with torch.cuda.device(dev):
+            g = _resolve_gamma(self.gamma, X)
+            K, mean, norms = kernel_matrix(X, self.kernel, g)
+            pr = _SvrProblem(K, torch.from_numpy(t).to(dev), self.C, self.epsilon, self.tol)
+            (n_iter, done), = _solve_svr([pr], int(self.max_iter))
+            self._adopt(X, g, mean, norms, pr, n_iter, done)
+        return self
+
+    def _adopt(self, X, g, mean, norms, pr, n_iter, done):
+        """Fitted attributes from a solved problem over the rows X (``pr``'s own row order)."""
+        if not done:
+            from sklearn.exceptions import ConvergenceWarning
+            warnings.warn(f"SVR: solver stopped after max_iter={self.max_iter} iterations before reaching tol={self.tol}", ConvergenceWarning)
+        dev = torch.device(self.device)
+        n = pr.n
+        alpha = pr.alpha.cpu().numpy()
+        coef = alpha[:n] - alpha[n:]
+        sup = np.flatnonzero(coef != 0.0)
+        self._gamma, self.n_iter_ = g, n_iter
+        self.support_ = sup.astype(np.int32)
+        self.n_support_ = np.array([len(sup)], dtype=np.int32)
+        self.dual_coef_ = coef[sup][None, :]
+        self.intercept_ = np.array([-float(pr.rho.item())])
+        self.alpha_ = alpha
+        sup_d = torch.from_numpy(sup).to(dev)
+        self._sv = X.index_select(0, sup_d)
+        self._coef_d = torch.from_numpy(np.ascontiguousarray(self.dual_coef_[0])).to(dev)
+        self._mean_d = mean
+        self._sv_norms = None if norms is None else norms.index_select(0, sup_d)
+        self.support_vectors_ = self._sv.cpu().numpy()
+        self.n_features_in_ = X.shape[1]
+        self.fit_status_ = 0 if done else 1
+
+    # ---- predict ----------------------------------------------------------------------------------------------------
+    def _decision(self, Xq, slices=0):
+        return _decision(self, torch.device(self.device), Xq, slices)
+
+    def predict_device(self, X, *, slices=0):
+        """f(x) for every row of X as a float64 CUDA tensor.  ``slices``: ``SVC.decision_function``'s test hook."""
+        if not hasattr(self, "_sv"):
+            raise RuntimeError("svm: not fitted")
+        Xq, _ = _dense.to_device_matrix(X, torch.device(self.device), "svm", allow_row_stride=True)
+        return self._decision(Xq, slices)
+
+    def predict(self, X):
+        if not hasattr(self, "_sv"):
+            raise RuntimeError("svm: not fitted")
+        Xq, was_numpy = _dense.to_device_matrix(X, torch.device(self.device), "svm", allow_row_stride=True)
+        out = self._decision(Xq)
+        return out.cpu().numpy() if was_numpy else out
+
+
+def _svr_point(params, who):
+    """(kernel, C, epsilon, gamma, tol, max_iter) of a parameter dict, checked."""
+    unknown = set(params) - {"kernel", "C", "epsilon", "gamma", "tol", "max_iter", "shrinking"}
+    if unknown:
+        raise ValueError(f"{who}: unsupported parameters {sorted(unknown)}")
+    kernel, C, epsilon, gamma = params.get("kernel", "rbf"), params.get("C", 1.0), params.get("epsilon", 0.1), params.get("gamma", "scale")
+    tol, max_iter = params.get("tol", 1e-3), params.get("max_iter", -1)
+    _check_params(C, kernel, gamma, tol, max_iter, who)
+    _check_epsilon(epsilon, who)
+    return kernel, C, epsilon, gamma, tol, max_iter
+
+
+def _host_matrix(X):
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError(f"svm: expected a 2-D [n, d] input, got shape {X.shape}")
+    return np.ascontiguousarray(X if X.dtype in (np.float32, np.float64) else X.astype(np.float64))
+
+
+def _fold_problems(X_d, t_all, tr, points, K_lin, dev):
+    """The problems of ``points`` = (kernel, C, epsilon, gamma, tol, max_iter) over the training rows ``tr`` of X_d: the points that share a
+    matrix -- the fold's RBF matrix of one gamma, or the shared linear matrix ``K_lin`` through the fold's row list -- stand side by side
+    over it, and equal points share one problem.  Returns (problems, finish): ``finish(solved)`` takes their ``_solve_svr`` results and
+    returns one fitted ``SVR`` per point, each equal to a single fit on those rows bit for bit."""
+    tr_d = torch.from_numpy(np.asarray(tr, dtype=np.int64)).to(dev)
+    Xtr = X_d.index_select(0, tr_d)
+    t_d = torch.from_numpy(np.ascontiguousarray(t_all[tr])).to(dev)
+    rows = tr_d.to(torch.int32) if any(p[0] == "linear" for p in points) else None
+    gammas = {gamma: _resolve_gamma(gamma, Xtr) for gamma in {p[3] for p in points}}
+    key = lambda kernel, C, epsilon, gamma, tol: (kernel, float(C), float(epsilon), gammas[gamma] if kernel == "rbf" else 0.0, float(tol))  # noqa: E731
+    mats, problems, owner = {}, [], {}
+    for kernel, C, epsilon, gamma, tol, _ in points:
+        k = key(kernel, C, epsilon, gamma, tol)
+        if k in owner:
+            continue
+        if kernel == "rbf" and k[3] not in mats:
+            mats[k[3]] = kernel_matrix(Xtr, "rbf", k[3])
+        owner[k] = len(problems)
+        problems.append(_SvrProblem(K_lin, t_d, C, epsilon, tol, rows) if kernel == "linear" else _SvrProblem(mats[k[3]][0], t_d, C, epsilon, tol))
+
+    def finish(solved):
+        models = []
+        for kernel, C, epsilon, gamma, tol, max_iter in points:
+            q = owner[key(kernel, C, epsilon, gamma, tol)]
+            m = SVR(kernel, C, epsilon, gamma, tol, max_iter, device=dev)
+            _, mean, norms = mats[gammas[gamma]] if kernel == "rbf" else (None, None, None)
+            m._adopt(Xtr, gammas[gamma], mean, norms, problems[q], *solved[q])
+            models.append(m)
+        return models
+    return problems, finish
+
+
+def fit_svr_folds(X, y, folds, device="cuda", **params):
+    """The fold loop of the reference's regression stack (multi_input_data_regression_opt_transformer_cnn_opt_more.py:133-149) for its
+    ``SVR``: one model per fold, all folds solved in one batch.  ``folds``: training-row index arrays, or (train, test) pairs as
+    ``KFold.split`` yields them.  An RBF matrix depends on the fold (its mean and ``gamma="scale"``): one per fold; the linear matrix is
+    formed once over all rows and a fold addresses it through its row list.  ``params``: ``SVR``'s.  Every returned model equals
+    ``SVR(**params).fit(X[train], y[train])`` bit for bit."""
+    point = _svr_point(params, "svm.fit_svr_folds")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"svm.fit_svr_folds: device {device!r}: the solver runs on the GPU (no CPU fallback)")
+    X = _host_matrix(X)
+    t = _targets(y, X.shape[0], "svm.fit_svr_folds")
+    trains = [np.asarray(f[0] if isinstance(f, (tuple, list)) and len(f) == 2 and np.ndim(f[0]) == 1 else f, dtype=np.int64) for f in folds]
+    if not trains:
+        raise ValueError("svm.fit_svr_folds: no folds")
+    for tr in trains:
+        if tr.ndim != 1 or len(tr) == 0 or tr.min() < 0 or tr.max() >= X.shape[0]:
+            raise ValueError(f"svm.fit_svr_folds: a fold's training rows must be a non-empty 1-D list of indices below {X.shape[0]}")
+    with torch.cuda.device(dev):
+        X_d = torch.from_numpy(X).to(dev)
+        K_lin = kernel_matrix(X_d, "linear")[0] if point[0] == "linear" else None
+        parts = [_fold_problems(X_d, t, tr, [point], K_lin, dev) for tr in trains]
+        solved = _solve_svr([pr for problems, _ in parts for pr in problems], int(point[5]))      # one problem per fold, all in one batch
+        return [finish([s])[0] for (_, finish), s in zip(parts, solved)]
+
+
+def grid_search_cv_svr(X, y, param_grid, cv: int = 5, device="cuda", *, tol=1e-3, max_iter=-1):
+    """``GridSearchCV(SVR(), param_grid, cv=cv)`` over ``C``, ``epsilon``, ``kernel`` and ``gamma``: scikit-learn's default for a regressor,
+    unshuffled ``KFold(cv)`` and R^2 scoring, sorted keys, ``itertools.product`` order, the first maximum wins; ``param_grid`` is a dict
+    or a list of dicts.  All points of a fold that share a matrix are solved side by side over it (``_fold_problems``), so every point equals
+    a single ``SVR(...).fit`` on that fold bit for bit.  Returns (best_params, mean R^2 per point, the model refitted on all rows with
+    best_params)."""
+    from itertools import product
+    from sklearn.metrics import r2_score
+    from sklearn.model_selection import KFold
+    points = []
+    for sub in ([param_grid] if isinstance(param_grid, dict) else list(param_grid)):
+        unknown = set(sub) - {"C", "epsilon", "kernel", "gamma"}
+        if unknown:
+            raise ValueError(f"svm.grid_search_cv_svr: unsupported grid keys {sorted(unknown)}")
+        keys = sorted(sub)
+        points += [dict(zip(keys, vals)) for vals in product(*(sub[k] for k in keys))]
+    if not points:
+        raise ValueError("svm.grid_search_cv_svr: the grid is empty")
+    full = [_svr_point({**pt, "tol": tol, "max_iter": max_iter}, "svm.grid_search_cv_svr") for pt in points]
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"svm.grid_search_cv_svr: device {device!r}: the solver runs on the GPU (no CPU fallback)")
+    X = _host_matrix(X)
+    t = _targets(y, X.shape[0], "svm.grid_search_cv_svr")
+    folds = list(KFold(n_splits=cv).split(X))
+    r2 = np.zeros((len(points), len(folds)))
+    with torch.cuda.device(dev):
+        X_d = torch.from_numpy(X).to(dev)
+        K_lin = kernel_matrix(X_d, "linear")[0] if any(p[0] == "linear" for p in full) else None
+        for fi, (tr, te) in enumerate(folds):
+            Xte = X_d.index_select(0, torch.from_numpy(te).to(dev))
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")                   # a capped fit warns once more below, in the refit, if it is the chosen one
+                problems, finish = _fold_problems(X_d, t, tr, full, K_lin, dev)
+                models = finish(_solve_svr(problems, int(max_iter)))
+            for pi, m in enumerate(models):
+                r2[pi, fi] = r2_score(t[te], m.predict_device(Xte).cpu().numpy())
+            del models, problems, finish
+    scores = [float(v) for v in r2.mean(axis=1)]
+    best = int(np.argmax(scores))
+    kernel, C, epsilon, gamma, tol, max_iter = full[best]
+    fitted = SVR(kernel, C, epsilon, gamma, tol, max_iter, device=device).fit(X, t)
     return points[best], scores, fitted

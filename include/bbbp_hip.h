@@ -499,6 +499,30 @@ typedef struct bbbp_svm_decision_desc {
 /* 0 with a message in bbbp_last_error() for an invalid descriptor (pointers are not examined) */
 size_t bbbp_svm_decision_workspace_bytes(const bbbp_svm_decision_desc* d);
 int bbbp_svm_decision(void* stream, const bbbp_svm_decision_desc* d, void* workspace, size_t workspace_bytes);
+/* One epsilon-SVR dual problem (csrc/svr.hip; SVR(kernel='rbf', C=1.0, epsilon=0.1) of the regression stack,
+ * Models/multi_input_data_regression_opt_transformer_cnn_opt_more.py:117-149): 2n variables over the n x n matrix, variable k < n with
+ * sign s = +1 and linear term epsilon - t[k], variable k + n with s = -1 and linear term epsilon + t[k];
+ * Q[k][l] = s_k s_l K[r(k mod n)][r(l mod n)] with r = rows (NULL: the identity), every entry of rows indexing a row of K.
+ * State: alpha and grad hold the 2n variables in that order; the launch that finds *n_iter == 0 sets alpha = 0 and grad = the linear term
+ * itself, whatever the arrays hold, so the host initialises only *n_iter = 0 and *done = 0.  diag is scratch of n doubles.
+ * Outputs: *rho, *n_iter (iterations so far), *done (1 once m(alpha) - M(alpha) < tol).  The regression coefficient of row k is
+ * alpha[k] - alpha[k + n] and the intercept -*rho; the kernel matrix and the decision function are the entry points above. */
+typedef struct bbbp_svr_problem {
+    const double* K; long ldk;
+    const int* rows;                           /* [n], nullable */
+    const double* t;                           /* [n] targets */
+    double* alpha; double* grad;               /* [2n] each */
+    double* diag;                              /* [n] */
+    double* rho; int* n_iter; int* done;
+    int n;
+    double C, epsilon, tol;
+} bbbp_svr_problem;
+/* libsvm's epsilon-SVR solver without shrinking (second-order working-set selection, its clipping, tau = 1e-12, ties to the later index of
+ * the 2n ordering), one work-group per problem, called like the classification solver above: at most `iters` iterations per launch of
+ * every problem whose *done is 0.  Up to 4096 rows a launch keeps its state in registers (read once, written once); beyond, in alpha and
+ * grad.  A problem's result does not depend on `iters`, on the others in the batch or on their order, and is bit-identical from call to
+ * call. */
+int bbbp_svr_smo(void* stream, const bbbp_svr_problem* problems, int n_problems, int iters);
 
 /* ---- logreg: batched float64 Newton solver for binary L2 logistic regression (csrc/logreg.hip) ------------------------------
  * LogisticRegression(max_iter=1000) of the classification stack (Models/model_opt_maccs.py:124-180), searched over C in {0.1, 1, 10}.
