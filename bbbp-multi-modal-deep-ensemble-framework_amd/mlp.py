@@ -110,9 +110,14 @@ class GridMLPTrainer:
             if cfg.activation not in _ACT:
                 raise ValueError(f"activation {cfg.activation!r}: the reference grid uses relu and tanh")
             hidden = list(cfg.hidden_layer_sizes)
-            if not 1 <= len(hidden) <= 3 or max(hidden) > 256:
-                raise ValueError("1 to 3 hidden layers of at most 256 units")
+            if not 1 <= len(hidden) <= 3 or max(hidden) > 256 or min(hidden) < 1:
+                raise ValueError("1 to 3 hidden layers of 1 to at most 256 units")
+            if int(cfg.batch_size) < 1 or int(cfg.max_iter) < 1:
+                raise ValueError("batch_size and max_iter must be at least 1")
             rows = np.arange(self.n) if cfg.train_rows is None else np.asarray(cfg.train_rows, dtype=np.int64)
+            # the kernel gathers rows of X by these ids without a bounds check of its own
+            if rows.ndim != 1 or rows.size < 1 or rows.min() < 0 or rows.max() >= self.n:
+                raise ValueError(f"train_rows must be a non-empty vector of row ids in [0, {self.n})")
             n_train = len(rows)
             units = [self.n_features] + hidden + [1]
             # Fits that share (integer random_state, layer sizes, number of training rows) -- in the reference grid all folds, activations,
