@@ -308,6 +308,9 @@ def softmax_fwd(x: torch.Tensor, dropout_p: float = 0.0, seed: int = 0):
 
 def softmax_bwd(dprob: torch.Tensor, prob: torch.Tensor, dropout_p: float = 0.0, seed: int = 0) -> torch.Tensor:
     d = _chk(dprob, "dprob").contiguous().clone()
+    prob = _chk(prob, "prob")
+    if prob.shape != d.shape or not prob.is_contiguous():
+        raise RuntimeError(f"softmax_bwd: prob must be contiguous and shaped like dprob, got {tuple(prob.shape)} vs {tuple(d.shape)}")
     cols = d.shape[-1]
     _lib.check(_lib.lib().bbbp_softmax_bwd(_stream(), d.data_ptr(), prob.data_ptr(), d.numel() // cols, cols, dropout_p, seed),
                "bbbp_softmax_bwd")
@@ -321,10 +324,18 @@ def dropout(x: torch.Tensor, p: float, seed: int) -> torch.Tensor:
     return y
 
 
+def _column_vectors(what: str, cols: int, **vectors) -> None:
+    """The per-column operands of a BatchNorm call: float32 device tensors of ``cols`` contiguous elements (the kernels index them unchecked)."""
+    for name, t in vectors.items():
+        if _chk(t, name).numel() != cols or not t.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must hold {cols} contiguous elements, got shape {tuple(t.shape)} strides {t.stride()}")
+
+
 def batchnorm1d_fwd(x, gamma, beta, running_mean, running_var, training: bool, eps: float = 1e-5, momentum: float = 0.1):
     """Returns (y, save_mean, save_rstd); running stats are updated in place when training."""
     x = _chk(x, "x").contiguous()
     rows, cols = x.shape
+    _column_vectors("batchnorm1d_fwd", cols, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var)
     y = torch.empty_like(x)
     sm = torch.empty(cols, device=x.device, dtype=torch.float32)
     sr = torch.empty(cols, device=x.device, dtype=torch.float32)
@@ -335,8 +346,11 @@ def batchnorm1d_fwd(x, gamma, beta, running_mean, running_var, training: bool, e
 
 
 def batchnorm1d_bwd(dy, x, gamma, save_mean, save_rstd, training: bool):
-    x = x.contiguous(); dy = dy.contiguous()
+    x = _chk(x, "x").contiguous(); dy = _chk(dy, "dy").contiguous()
+    if x.dim() != 2 or dy.shape != x.shape:
+        raise RuntimeError(f"batchnorm1d_bwd: dy and x must be 2-D and shaped alike, got {tuple(dy.shape)} vs {tuple(x.shape)}")
     rows, cols = x.shape
+    _column_vectors("batchnorm1d_bwd", cols, gamma=gamma, save_mean=save_mean, save_rstd=save_rstd)
     dx = torch.empty_like(x)
     dg = torch.empty(cols, device=x.device, dtype=torch.float32)
     db = torch.empty(cols, device=x.device, dtype=torch.float32)
@@ -352,6 +366,8 @@ def bias_act_bwd(dy: torch.Tensor, y: Optional[torch.Tensor], act=None, scale: f
     ldy = 0
     if y is not None:
         ldy = _rowmajor_2d(_chk(y, "y"), "y")[2]
+        if y.shape != dy.shape:
+            raise RuntimeError(f"bias_act_bwd: y must be shaped like dy, got {tuple(y.shape)} vs {tuple(dy.shape)}")
     db = torch.empty(cols, device=dy.device, dtype=torch.float32)
     _lib.check(_lib.lib().bbbp_bias_act_bwd(_stream(), dy.data_ptr(), lddy, _p(y), ldy, db.data_ptr(), rows, cols, ACT[act],
                                             scale), "bbbp_bias_act_bwd")
@@ -362,6 +378,8 @@ def mse(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0):
     """Returns (loss[1], dpred) for loss = mean((pred - target)^2)."""
     pred = _chk(pred, "pred").contiguous().view(-1)
     target = _chk(target, "target").contiguous().view(-1)
+    if target.numel() != pred.numel():
+        raise RuntimeError(f"mse: pred has {pred.numel()} elements, target {target.numel()}")
     loss = torch.empty(1, device=pred.device, dtype=torch.float32)
     dpred = torch.empty_like(pred)
     _lib.check(_lib.lib().bbbp_mse(_stream(), pred.data_ptr(), target.data_ptr(), loss.data_ptr(), dpred.data_ptr(),
