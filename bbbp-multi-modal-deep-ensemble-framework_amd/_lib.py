@@ -176,6 +176,7 @@ _SIGNATURES = {
     "bbbp_gbt_fit_tree_capacity": (c_int, [c_int]),
     "bbbp_gbt_fit_work_bytes": (c_size_t, [c_int, c_int]),
     "bbbp_gbt_fit": (c_int, [c_void_p, POINTER(GbtChain), c_void_p, c_int]),
+    "bbbp_gbr_fit": (c_int, [c_void_p, POINTER(GbtChain), c_void_p, c_int]),
     "bbbp_gbt_staged_decision": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                          c_double, c_double, c_void_p, c_int, c_void_p]),
     "bbbp_rf_fit_tree_capacity": (c_int, [c_int]),

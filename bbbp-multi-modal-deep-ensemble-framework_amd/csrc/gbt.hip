@@ -17,10 +17,16 @@
 //              the threshold, the children; a node without a valid split becomes a leaf
 //   side       one thread per row: the new key
 //   partition  one work-group per (feature, chain): a stable partition of every segment by the new key's last bit
-//   update     one work-group per chain: on a finished tree raw += lr * value[leaf], the stage's log-loss, the next residuals
+//   update     one work-group per chain: on a finished tree raw += lr * value[leaf], the stage's score under the loss, the next residuals
 // Chains of different depth take different numbers of rounds per tree; each keeps its own (tree, level) on the device and a kernel
 // leaves at once for a chain that has nothing to do in it.  Nothing is read back by the host before the last round.
 // Every sum's order depends on the chain's own data alone: a chain's trees are bit-identical alone, in any batch, and run to run.
+//
+// The loss is a template parameter of the kernels that know about it -- init, stats, update, and choose for the leaf it makes of a node
+// without a valid split -- so no row takes a runtime branch on it; split, side and partition are shared.  HalfBinomial is the classifier
+// above (bbbp_gbt_fit).  SquaredError (bbbp_gbr_fit) is GradientBoostingRegressor of the logBB stack's bake-off
+// (Models/multi_input_data_regression_opt_transformer_cnn_opt_more.py:118-125): g = y - raw, stats sums g and g^2 alone, every node's
+// value is sum g / m (scikit-learn skips the leaf update for this loss), the stage score is the mean of (y - raw)^2.
 #include "common.h"
 #include "bbbp_hip.h"
 
@@ -96,6 +102,7 @@ __device__ inline int row_of(const int* src, int p, int n, ChainState* st) {
 }
 __device__ inline bool chain_idle(const bbbp_gbt_chain& c, const ChainState* st) { return st->tree >= c.n_estimators; }
 
+// ---- the loss: a compile-time parameter of the kernels that know about it (init, stats, choose's late leaf, update) ------------------
 // scikit-learn's half-binomial loss and gradient (_loss/_loss.pyx.tp), restated: loss = log1pexp(raw) - y raw, residual = y - expit(raw)
 __device__ inline double log1pexp(double x) {
     if (x <= -37.0) return exp(x);
@@ -104,18 +111,39 @@ __device__ inline double log1pexp(double x) {
     if (x <= 33.3) return x + exp(-x);
     return x;
 }
-__device__ inline double residual(double y, double raw) {
-    if (raw > -37.0) {
-        const double e = exp(-raw);
-        return -(((1.0 - y) - y * e) / (1.0 + e));
+struct HalfBinomial {                         // GradientBoostingClassifier: y in {0, 1}
+    static constexpr bool kNewton = true;     // a leaf's value is one Newton step, mean(g) / mean(p (1 - p)): stats sums p (1 - p) too
+    __device__ static inline double residual(double y, double raw) {
+        if (raw > -37.0) {
+            const double e = exp(-raw);
+            return -(((1.0 - y) - y * e) / (1.0 + e));
+        }
+        return -(exp(raw) - y);
     }
-    return -(exp(raw) - y);
-}
-__device__ inline double leaf_value(double sum_g, double sum_pq, int m) {
-    const double num = sum_g / m, den = sum_pq / m;
-    return fabs(den) < 1e-150 ? 0.0 : num / den;
-}
+    __device__ static inline double row_loss(double y, double raw) {
+#pragma clang fp contract(off)
+        return log1pexp(raw) - y * raw;                     // product and difference rounded separately, as the sum they join
+    }
+    __device__ static inline double leaf_value(double sum_g, double sum_pq, int m) {
+        const double num = sum_g / m, den = sum_pq / m;
+        return fabs(den) < 1e-150 ? 0.0 : num / den;
+    }
+    __device__ static inline double stage_score(double sum, int n) { return 2.0 * (sum / n); }      // scikit-learn's train_score_: twice the mean half-binomial loss
+};
+// scikit-learn's half squared error: residual = y - raw; _update_terminal_regions is skipped, so the tree's own node mean sum g / m, which
+// stats writes into every node, is the update and nothing is summed beside g and g^2; train_score_ is the mean of (y - raw)^2
+struct SquaredError {                         // GradientBoostingRegressor: y real
+    static constexpr bool kNewton = false;
+    __device__ static inline double residual(double y, double raw) { return y - raw; }
+    __device__ static inline double row_loss(double y, double raw) {
+#pragma clang fp contract(off)
+        const double r = y - raw;
+        return r * r;
+    }
+    __device__ static inline double stage_score(double sum, int n) { return sum / n; }
+};
 
+template <class Loss>
 __global__ __launch_bounds__(256) void gbt_init_kernel(const bbbp_gbt_chain* chains) {
     const bbbp_gbt_chain c = chains[blockIdx.y];
     const View v = view_of(c);
@@ -123,11 +151,12 @@ __global__ __launch_bounds__(256) void gbt_init_kernel(const bbbp_gbt_chain* cha
     if (i == 0) *v.st = ChainState{0, 0, 0, 0, 0};
     if (i >= c.n) return;
     c.raw[i] = c.init;
-    v.g[i] = residual(c.y[i], c.init);
+    v.g[i] = Loss::residual(c.y[i], c.init);
     v.key[i] = 0;
 }
 
 // ---- stats: the new nodes' sums and the stop rules ----------------------------------------------------------------------------------
+template <class Loss>
 __global__ __launch_bounds__(256) void gbt_stats_kernel(const bbbp_gbt_chain* chains) {
     const bbbp_gbt_chain c = chains[blockIdx.x];
     const View v = view_of(c);
@@ -153,22 +182,28 @@ __global__ __launch_bounds__(256) void gbt_stats_kernel(const bbbp_gbt_chain* ch
         double sg = 0.0, sq = 0.0, spq = 0.0;
         for (int p = lane; p < m && s + p < c.n; p += 64) {
             const int i = row_of(src, s + p, c.n, v.st);
-            const double g = v.g[i], pr = c.y[i] - g;
-            sg += g; sq += g * g; spq += pr * (1.0 - pr);
+            const double g = v.g[i];
+            sg += g; sq += g * g;
+            if constexpr (Loss::kNewton) {
+                const double pr = c.y[i] - g;
+                spq += pr * (1.0 - pr);
+            }
         }
         for (int off = 32; off >= 1; off >>= 1) {
-            sg += __shfl_xor(sg, off); sq += __shfl_xor(sq, off); spq += __shfl_xor(spq, off);
+            sg += __shfl_xor(sg, off); sq += __shfl_xor(sq, off);
+            if constexpr (Loss::kNewton) spq += __shfl_xor(spq, off);
         }
         if (lane == 0) {
             const double mean = sg / m, impurity = sq / m - mean * mean;
             const bool leaf = level >= c.max_depth || m < c.min_samples_split || m < 2 * c.min_samples_leaf || impurity <= GBT_EPSILON;
             const long node = base + tab->node[k];
-            tab->sum_g[k] = sg; tab->sum_pq[k] = spq;
+            tab->sum_g[k] = sg; tab->sum_pq[k] = spq;           // sum_pq: 0 without a Newton step, and nothing reads it then
             c.n_node_samples[node] = m;
             if (leaf) {
                 tab->flag[k] = KEY_LEAF;
                 c.left[node] = -1; c.right[node] = -1; c.feature[node] = 0; c.threshold[node] = -2.0;
-                c.value[node] = leaf_value(sg, spq, m);
+                if constexpr (Loss::kNewton) c.value[node] = Loss::leaf_value(sg, spq, m);
+                else c.value[node] = mean;
             } else {
                 c.value[node] = mean;
                 ++mine;
@@ -276,6 +311,7 @@ size_t split_lds_bytes(int n) {
 }
 
 // ---- choose: the best feature per node, its threshold and children ------------------------------------------------------------------
+template <class Loss>
 __global__ __launch_bounds__(64) void gbt_choose_kernel(const bbbp_gbt_chain* chains) {
     const bbbp_gbt_chain c = chains[blockIdx.x];
     const View v = view_of(c);
@@ -313,7 +349,7 @@ __global__ __launch_bounds__(64) void gbt_choose_kernel(const bbbp_gbt_chain* ch
     } else if (in) {
         if (flag == KEY_ACTIVE) {                           // no valid split: a leaf after all
             c.left[base + node] = -1; c.right[base + node] = -1; c.feature[base + node] = 0; c.threshold[base + node] = -2.0;
-            c.value[base + node] = leaf_value(tab->sum_g[k], tab->sum_pq[k], m);
+            if constexpr (Loss::kNewton) c.value[base + node] = Loss::leaf_value(tab->sum_g[k], tab->sum_pq[k], m);      // else: stats wrote the mean
         }
         const int keep = flag == KEY_EMPTY ? KEY_EMPTY : KEY_LEAF;
         next->start[2 * k] = s; next->cnt[2 * k] = m; next->node[2 * k] = node; next->flag[2 * k] = keep;
@@ -393,7 +429,8 @@ __global__ __launch_bounds__(GBT_SCAN) void gbt_partition_kernel(const bbbp_gbt_
 }
 size_t partition_lds_bytes(int n) { return (3 * GBT_SPLIT_KEYS + 8) * 4 + (size_t)n; }
 
-// ---- update: a finished tree's raw scores, log-loss and next residuals; every chain's next (tree, level) ------------------------------
+// ---- update: a finished tree's raw scores, the stage's score under the loss and next residuals; every chain's next (tree, level) -------
+template <class Loss>
 __global__ __launch_bounds__(1024) void gbt_update_kernel(const bbbp_gbt_chain* chains) {
     const bbbp_gbt_chain c = chains[blockIdx.x];
     const View v = view_of(c);
@@ -419,8 +456,8 @@ __global__ __launch_bounds__(1024) void gbt_update_kernel(const bbbp_gbt_chain* 
         const double raw = c.raw[i] + step;
         const double y = c.y[i];
         c.raw[i] = raw;
-        loss += log1pexp(raw) - y * raw;
-        v.g[i] = residual(y, raw);
+        loss += Loss::row_loss(y, raw);
+        v.g[i] = Loss::residual(y, raw);
         v.key[i] = 0;
     }
     part[tid] = loss;
@@ -430,7 +467,7 @@ __global__ __launch_bounds__(1024) void gbt_update_kernel(const bbbp_gbt_chain* 
         __syncthreads();
     }
     if (tid == 0) {
-        c.train_score[tree] = 2.0 * (part[0] / c.n);         // scikit-learn's train_score_: twice the mean half-binomial loss
+        c.train_score[tree] = Loss::stage_score(part[0], c.n);
         c.tree_nodes[tree] = v.st->error ? -1 : v.st->n_nodes;       // the error word stays set: every later tree reports it too
         v.st->tree = tree + 1; v.st->level = 0; v.st->final = 0; v.st->n_nodes = 0;
     }
@@ -463,19 +500,51 @@ __global__ __launch_bounds__(256) void gbt_decision_kernel(DecisionArgs a) {
     }
 }
 
-int check_chain(const bbbp_gbt_chain& c, int q) {
-    BBBP_CHECK_ARG(c.n >= 2 && c.d >= 1, "gbt_fit: chain %d: n >= 2 and d >= 1 must hold, got n %d d %d", q, c.n, c.d);
-    BBBP_CHECK_ARG(c.n <= BBBP_GBT_FIT_MAX_N, "gbt_fit: chain %d: n %d exceeds BBBP_GBT_FIT_MAX_N %d", q, c.n, BBBP_GBT_FIT_MAX_N);
-    BBBP_CHECK_ARG(c.d <= BBBP_GBT_FIT_MAX_D, "gbt_fit: chain %d: d %d exceeds BBBP_GBT_FIT_MAX_D %d", q, c.d, BBBP_GBT_FIT_MAX_D);
-    BBBP_CHECK_ARG(c.max_depth >= 1 && c.max_depth <= BBBP_GBT_FIT_MAX_DEPTH, "gbt_fit: chain %d: max_depth %d outside 1..%d", q, c.max_depth, BBBP_GBT_FIT_MAX_DEPTH);
-    BBBP_CHECK_ARG(c.n_estimators >= 1 && c.n_estimators <= BBBP_GBT_FIT_MAX_TREES, "gbt_fit: chain %d: n_estimators %d outside 1..%d", q, c.n_estimators,
+int check_chain(const char* who, const bbbp_gbt_chain& c, int q) {
+    BBBP_CHECK_ARG(c.n >= 2 && c.d >= 1, "%s: chain %d: n >= 2 and d >= 1 must hold, got n %d d %d", who, q, c.n, c.d);
+    BBBP_CHECK_ARG(c.n <= BBBP_GBT_FIT_MAX_N, "%s: chain %d: n %d exceeds BBBP_GBT_FIT_MAX_N %d", who, q, c.n, BBBP_GBT_FIT_MAX_N);
+    BBBP_CHECK_ARG(c.d <= BBBP_GBT_FIT_MAX_D, "%s: chain %d: d %d exceeds BBBP_GBT_FIT_MAX_D %d", who, q, c.d, BBBP_GBT_FIT_MAX_D);
+    BBBP_CHECK_ARG(c.max_depth >= 1 && c.max_depth <= BBBP_GBT_FIT_MAX_DEPTH, "%s: chain %d: max_depth %d outside 1..%d", who, q, c.max_depth, BBBP_GBT_FIT_MAX_DEPTH);
+    BBBP_CHECK_ARG(c.n_estimators >= 1 && c.n_estimators <= BBBP_GBT_FIT_MAX_TREES, "%s: chain %d: n_estimators %d outside 1..%d", who, q, c.n_estimators,
                    BBBP_GBT_FIT_MAX_TREES);
-    BBBP_CHECK_ARG(c.min_samples_split >= 2, "gbt_fit: chain %d: min_samples_split %d must be >= 2", q, c.min_samples_split);
-    BBBP_CHECK_ARG(c.min_samples_leaf >= 1, "gbt_fit: chain %d: min_samples_leaf %d must be >= 1", q, c.min_samples_leaf);
-    BBBP_CHECK_ARG(c.learning_rate > 0.0 && c.learning_rate < INFINITY, "gbt_fit: chain %d: learning_rate must be positive and finite", q);
-    BBBP_CHECK_ARG(c.init == c.init && fabs(c.init) < INFINITY, "gbt_fit: chain %d: init must be finite", q);
+    BBBP_CHECK_ARG(c.min_samples_split >= 2, "%s: chain %d: min_samples_split %d must be >= 2", who, q, c.min_samples_split);
+    BBBP_CHECK_ARG(c.min_samples_leaf >= 1, "%s: chain %d: min_samples_leaf %d must be >= 1", who, q, c.min_samples_leaf);
+    BBBP_CHECK_ARG(c.learning_rate > 0.0 && c.learning_rate < INFINITY, "%s: chain %d: learning_rate must be positive and finite", who, q);
+    BBBP_CHECK_ARG(c.init == c.init && fabs(c.init) < INFINITY, "%s: chain %d: init must be finite", who, q);
     BBBP_CHECK_ARG(c.XT && c.order0 && c.y && c.work && c.left && c.right && c.feature && c.n_node_samples && c.threshold && c.value && c.tree_nodes &&
-                       c.train_score && c.raw, "gbt_fit: chain %d: null pointer", q);
+                       c.train_score && c.raw, "%s: chain %d: null pointer", who, q);
+    return BBBP_OK;
+}
+
+template <class Loss>
+int fit_chains(const char* who, void* stream, const bbbp_gbt_chain* chains, const bbbp_gbt_chain* chains_device, int n_chains) {
+    BBBP_CHECK_ARG(chains && chains_device, "%s: null pointer", who);
+    BBBP_CHECK_ARG(n_chains >= 1 && n_chains <= 65535, "%s: n_chains %d outside 1..65535", who, n_chains);
+    int max_n = 0, max_d = 0;
+    long rounds = 0;
+    for (int q = 0; q < n_chains; ++q) {
+        if (int rc = check_chain(who, chains[q], q)) return rc;
+        max_n = chains[q].n > max_n ? chains[q].n : max_n;
+        max_d = chains[q].d > max_d ? chains[q].d : max_d;
+        const long r = (long)chains[q].n_estimators * (chains[q].max_depth + 1);
+        rounds = r > rounds ? r : rounds;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t split_lds = split_lds_bytes(max_n), part_lds = partition_lds_bytes(max_n);
+    if (int rc = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gbt_split_kernel), split_lds)) return rc;
+    if (int rc = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gbt_partition_kernel), part_lds)) return rc;
+    const dim3 rows((unsigned)cdiv(max_n, 256), (unsigned)n_chains), feats((unsigned)max_d, (unsigned)n_chains), one((unsigned)n_chains);
+    hipLaunchKernelGGL(gbt_init_kernel<Loss>, rows, dim3(256), 0, st, chains_device);
+    BBBP_CHECK_LAUNCH();
+    for (long r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(gbt_stats_kernel<Loss>, one, dim3(256), 0, st, chains_device);
+        hipLaunchKernelGGL(gbt_split_kernel, feats, dim3(GBT_SCAN), split_lds, st, chains_device);
+        hipLaunchKernelGGL(gbt_choose_kernel<Loss>, one, dim3(64), 0, st, chains_device);
+        hipLaunchKernelGGL(gbt_side_kernel, rows, dim3(256), 0, st, chains_device);
+        hipLaunchKernelGGL(gbt_partition_kernel, feats, dim3(GBT_SCAN), part_lds, st, chains_device);
+        hipLaunchKernelGGL(gbt_update_kernel<Loss>, one, dim3(1024), 0, st, chains_device);
+        BBBP_CHECK_LAUNCH();
+    }
     return BBBP_OK;
 }
 
@@ -497,34 +566,11 @@ extern "C" size_t bbbp_gbt_fit_work_bytes(int n, int d) {
 }
 
 extern "C" int bbbp_gbt_fit(void* stream, const bbbp_gbt_chain* chains, const bbbp_gbt_chain* chains_device, int n_chains) {
-    BBBP_CHECK_ARG(chains && chains_device, "gbt_fit: null pointer");
-    BBBP_CHECK_ARG(n_chains >= 1 && n_chains <= 65535, "gbt_fit: n_chains %d outside 1..65535", n_chains);
-    int max_n = 0, max_d = 0;
-    long rounds = 0;
-    for (int q = 0; q < n_chains; ++q) {
-        if (int rc = check_chain(chains[q], q)) return rc;
-        max_n = chains[q].n > max_n ? chains[q].n : max_n;
-        max_d = chains[q].d > max_d ? chains[q].d : max_d;
-        const long r = (long)chains[q].n_estimators * (chains[q].max_depth + 1);
-        rounds = r > rounds ? r : rounds;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t split_lds = split_lds_bytes(max_n), part_lds = partition_lds_bytes(max_n);
-    if (int rc = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gbt_split_kernel), split_lds)) return rc;
-    if (int rc = bbbp_ensure_dyn_lds(reinterpret_cast<const void*>(gbt_partition_kernel), part_lds)) return rc;
-    const dim3 rows((unsigned)cdiv(max_n, 256), (unsigned)n_chains), feats((unsigned)max_d, (unsigned)n_chains), one((unsigned)n_chains);
-    hipLaunchKernelGGL(gbt_init_kernel, rows, dim3(256), 0, st, chains_device);
-    BBBP_CHECK_LAUNCH();
-    for (long r = 0; r < rounds; ++r) {
-        hipLaunchKernelGGL(gbt_stats_kernel, one, dim3(256), 0, st, chains_device);
-        hipLaunchKernelGGL(gbt_split_kernel, feats, dim3(GBT_SCAN), split_lds, st, chains_device);
-        hipLaunchKernelGGL(gbt_choose_kernel, one, dim3(64), 0, st, chains_device);
-        hipLaunchKernelGGL(gbt_side_kernel, rows, dim3(256), 0, st, chains_device);
-        hipLaunchKernelGGL(gbt_partition_kernel, feats, dim3(GBT_SCAN), part_lds, st, chains_device);
-        hipLaunchKernelGGL(gbt_update_kernel, one, dim3(1024), 0, st, chains_device);
-        BBBP_CHECK_LAUNCH();
-    }
-    return BBBP_OK;
+    return fit_chains<HalfBinomial>("gbt_fit", stream, chains, chains_device, n_chains);
+}
+
+extern "C" int bbbp_gbr_fit(void* stream, const bbbp_gbt_chain* chains, const bbbp_gbt_chain* chains_device, int n_chains) {
+    return fit_chains<SquaredError>("gbr_fit", stream, chains, chains_device, n_chains);
 }
 
 extern "C" int bbbp_gbt_staged_decision(void* stream, const float* X, long ld, int m, int d, const int* left, const int* right, const int* feature,

@@ -22,6 +22,14 @@ certified instead (``tests/gbt_replay.py``).  Results are bit-identical for a pr
 Out of scope (each is refused by name): more than two classes, other losses and criteria, ``subsample < 1``, ``max_features``,
 ``sample_weight``, ``init`` estimators, ``n_iter_no_change``, ``max_leaf_nodes``, ``ccp_alpha``, ``min_impurity_decrease != 0``,
 ``max_depth > 7``, more than 8 192 rows or 1 024 features, more than one GPU.  There is no CPU path.
+
+``GradientBoostingRegressor`` is the logBB stack's boosted learner (``Models/multi_input_data_regression_opt_transformer_cnn_opt_more.py:118-125``:
+``GradientBoostingRegressor(n_estimators=200, learning_rate=0.1, max_depth=5, random_state=42)`` per fold) under the squared error.  It
+grows through the same rounds with the loss swapped at compile time (``bbbp_gbr_fit``): ``g = y - raw`` from ``init_ = mean(y)``, a node's
+value is ``sum g / m`` in leaves and split nodes alike, ``train_score_`` is the mean of ``(y - raw)^2``.  It shares the matrix, the chain,
+the query path and the staged kernel with the classifier; ``fit_regressors`` fits the five folds and the refit in one batch.  Its trees
+are certified by ``tests/gbr_replay.py``; on continuous features, where exact ties arise only between candidates that part the rows the
+same way, its training-row predictions also agree with scikit-learn's to a few ulp.  The regressor's docstring lists what it refuses.
 """
 from __future__ import annotations
 
@@ -117,7 +125,8 @@ class _Matrix:
 
 
 class _Chain:
-    """One model to fit: its outputs, its work area and the descriptor ``bbbp_gbt_fit`` takes.  Nothing needs initialising."""
+    """One model to fit: its outputs, its work area and the descriptor ``bbbp_gbt_fit`` and ``bbbp_gbr_fit`` take (``t_d``: the 0.0 / 1.0
+    labels or the regression targets, float64 on the device).  Nothing needs initialising."""
 
     def __init__(self, mat, t_d, init, n_estimators, learning_rate, max_depth, min_samples_split, min_samples_leaf):
         L, dev = _lib.lib(), mat.XT.device
@@ -156,12 +165,13 @@ class _Chain:
                     root=root.astype(np.int32))
 
 
-def _fit_chains(chains):
-    """``bbbp_gbt_fit`` over all chains in one batch: the descriptors go to the device once, nothing is read back here."""
+def _fit_chains(chains, entry="bbbp_gbt_fit"):
+    """``entry`` (``bbbp_gbt_fit``: the log-loss, ``bbbp_gbr_fit``: the squared error) over all chains in one batch: the descriptors go to
+    the device once, nothing is read back here."""
     dev = chains[0].work.device
     arr = (_lib.GbtChain * len(chains))(*[c.desc for c in chains])
     on_device = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-    _lib.check(_lib.lib().bbbp_gbt_fit(_dense.stream(), arr, on_device.data_ptr(), len(chains)), "bbbp_gbt_fit")
+    _lib.check(getattr(_lib.lib(), entry)(_dense.stream(), arr, on_device.data_ptr(), len(chains)), entry)
     return on_device                                   # kept alive by the caller until the results are read
 
 
@@ -178,7 +188,61 @@ def _check_trees(trees, n_features):
         raise ValueError("gradient_boosting: a child or feature index outside its array")
 
 
-class GradientBoostingClassifier:
+def _sklearn_trees(fitted):
+    """A fitted scikit-learn booster's trees (one column of ``estimators_``) as the flat host arrays of ``trees_``, and its feature count."""
+    shim = types.SimpleNamespace(estimators_=list(fitted.estimators_[:, 0]), n_features_in_=fitted.n_features_in_, n_outputs_=1)
+    left, right, feature, threshold, value, root, d = ForestGPU.flatten_sklearn(shim)
+    nns = np.concatenate([e.tree_.n_node_samples for e in shim.estimators_])
+    return dict(left=left.astype(np.int32), right=right.astype(np.int32), feature=feature.astype(np.int32), threshold=threshold, value=value,
+                n_node_samples=nns.astype(np.int32), root=root.astype(np.int32)), d
+
+
+class _BoostedTrees:
+    """What the classifier and the regressor share once a model is there: its trees on the device, the query path and the staged raw
+    scores of ``bbbp_gbt_staged_decision``.  ``self.device`` is anything ``torch.device`` takes."""
+
+    def _set_trees(self, trees, init, learning_rate, n_features):
+        _check_trees(trees, n_features)
+        dev = torch.device(self.device)
+        self.trees_, self.init_, self.n_features_in_ = trees, float(init), int(n_features)
+        self.n_estimators_ = len(trees["root"]) - 1
+        self._lr = float(learning_rate)
+        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
+        self._dev = {k: to(trees[k], np.float64 if k in ("threshold", "value") else np.int32) for k in ("left", "right", "feature", "threshold", "value", "root")}
+
+    def _queries(self, X):
+        if not hasattr(self, "_dev"):
+            raise RuntimeError("gradient_boosting: not fitted")
+        was_numpy = not isinstance(X, torch.Tensor)
+        if was_numpy:
+            X = np.asarray(X)
+            if X.ndim != 2:
+                raise ValueError(f"gradient_boosting: expected a 2-D [m, d] input, got shape {X.shape}")
+            with np.errstate(over="ignore"):
+                X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
+        elif not X.is_cuda:
+            raise RuntimeError(f"gradient_boosting: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
+        if X.dim() != 2 or X.shape[1] != self.n_features_in_:
+            raise ValueError(f"gradient_boosting: the queries must be [m, {self.n_features_in_}], got shape {tuple(X.shape)}")
+        return X.to(torch.device(self.device), torch.float32).contiguous(), was_numpy
+
+    def _staged(self, Xq, stages):
+        """Raw scores [len(stages), m] after ``stages`` trees each (ascending, within 1..n_estimators_)."""
+        m, dev = Xq.shape[0], torch.device(self.device)
+        out = torch.empty((len(stages), m), dtype=torch.float64, device=dev)
+        if m == 0:
+            return out
+        stages_d = torch.tensor(list(stages), dtype=torch.int32, device=dev)
+        t = self._dev
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().bbbp_gbt_staged_decision(_dense.stream(), Xq.data_ptr(), Xq.shape[1], m, Xq.shape[1], t["left"].data_ptr(),
+                                                           t["right"].data_ptr(), t["feature"].data_ptr(), t["threshold"].data_ptr(), t["value"].data_ptr(),
+                                                           t["root"].data_ptr(), self.n_estimators_, self.init_, self._lr, stages_d.data_ptr(), len(stages),
+                                                           out.data_ptr()), "bbbp_gbt_staged_decision")
+        return out
+
+
+class GradientBoostingClassifier(_BoostedTrees):
     """``GradientBoostingClassifier(n_estimators=100, learning_rate=0.1, max_depth=3, min_samples_split=2, min_samples_leaf=1, *,
     device="cuda")``: scikit-learn's names for two classes and the log-loss.
 
@@ -236,12 +300,8 @@ class GradientBoostingClassifier:
         self._train_raw = chain.raw.cpu().numpy() if T == chain.T else None       # the training rows' raw scores after the last stage (tests)
 
     def _set_model(self, classes, trees, init, learning_rate, n_features):
-        _check_trees(trees, n_features)
-        self.classes_, self.trees_, self.init_, self.n_features_in_ = classes, trees, float(init), int(n_features)
-        self.n_estimators_ = len(trees["root"]) - 1
-        self._lr = float(learning_rate)
-        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)  # noqa: E731
-        self._dev = {k: to(trees[k], np.float64 if k in ("threshold", "value") else np.int32) for k in ("left", "right", "feature", "threshold", "value", "root")}
+        self._set_trees(trees, init, learning_rate, n_features)
+        self.classes_ = classes
 
     @classmethod
     def from_sklearn(cls, fitted, device="cuda"):
@@ -254,13 +314,9 @@ class GradientBoostingClassifier:
         if not isinstance(fitted.init_, DummyClassifier) or fitted.init_.strategy != "prior":
             raise NotImplementedError("GradientBoostingClassifier.from_sklearn: init estimators are not supported (only init=None, the prior)")
         self = cls(1, float(fitted.learning_rate), device=device)
-        shim = types.SimpleNamespace(estimators_=list(fitted.estimators_[:, 0]), n_features_in_=fitted.n_features_in_, n_outputs_=1)
-        left, right, feature, threshold, value, root, d = ForestGPU.flatten_sklearn(shim)
-        nns = np.concatenate([e.tree_.n_node_samples for e in shim.estimators_])
-        trees = dict(left=left.astype(np.int32), right=right.astype(np.int32), feature=feature.astype(np.int32), threshold=threshold, value=value,
-                     n_node_samples=nns.astype(np.int32), root=root.astype(np.int32))
+        trees, d = _sklearn_trees(fitted)
         init = float(logit(np.clip(np.float64(fitted.init_.class_prior_[1]), EPS32, 1.0 - EPS32)))
-        self.n_estimators = len(root) - 1
+        self.n_estimators = len(trees["root"]) - 1
         # the fitting parameters are kept only where this class would accept them (scikit-learn allows None and fractions): an adopted
         # model predicts, it is not refitted
         for name in ("max_depth", "min_samples_split", "min_samples_leaf"):
@@ -271,37 +327,6 @@ class GradientBoostingClassifier:
         return self
 
     # ---- decision ---------------------------------------------------------------------------------------------------
-    def _queries(self, X):
-        if not hasattr(self, "_dev"):
-            raise RuntimeError("gradient_boosting: not fitted")
-        was_numpy = not isinstance(X, torch.Tensor)
-        if was_numpy:
-            X = np.asarray(X)
-            if X.ndim != 2:
-                raise ValueError(f"gradient_boosting: expected a 2-D [m, d] input, got shape {X.shape}")
-            with np.errstate(over="ignore"):
-                X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
-        elif not X.is_cuda:
-            raise RuntimeError(f"gradient_boosting: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
-        if X.dim() != 2 or X.shape[1] != self.n_features_in_:
-            raise ValueError(f"gradient_boosting: the queries must be [m, {self.n_features_in_}], got shape {tuple(X.shape)}")
-        return X.to(self.device, torch.float32).contiguous(), was_numpy
-
-    def _staged(self, Xq, stages):
-        """Raw scores [len(stages), m] after ``stages`` trees each (ascending, within 1..n_estimators_)."""
-        m = Xq.shape[0]
-        out = torch.empty((len(stages), m), dtype=torch.float64, device=self.device)
-        if m == 0:
-            return out
-        stages_d = torch.tensor(list(stages), dtype=torch.int32, device=self.device)
-        t = self._dev
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().bbbp_gbt_staged_decision(_dense.stream(), Xq.data_ptr(), Xq.shape[1], m, Xq.shape[1], t["left"].data_ptr(),
-                                                           t["right"].data_ptr(), t["feature"].data_ptr(), t["threshold"].data_ptr(), t["value"].data_ptr(),
-                                                           t["root"].data_ptr(), self.n_estimators_, self.init_, self._lr, stages_d.data_ptr(), len(stages),
-                                                           out.data_ptr()), "bbbp_gbt_staged_decision")
-        return out
-
     def decision_function(self, X):
         """The raw score of every row after all stages; positive means ``classes_[1]``."""
         Xq, was_numpy = self._queries(X)
@@ -413,3 +438,189 @@ def grid_search_cv(X, y, param_grid, cv: int = 5, device="cuda"):
     best = int(np.argmax(scores))
     fitted = GradientBoostingClassifier(*full[best], device=dev).fit(X32, y)
     return points[best], scores, fitted
+
+
+# ---- regression: GradientBoostingRegressor under the squared error ---------------------------------------------------------------------
+_REGRESSOR_DEFAULTS = dict(criterion="friedman_mse", subsample=1.0, max_features=None, init=None, alpha=0.9, n_iter_no_change=None, max_leaf_nodes=None,
+                           ccp_alpha=0.0, min_impurity_decrease=0.0, min_weight_fraction_leaf=0.0, warm_start=False)
+_REGRESSOR_IGNORED = ("verbose", "tol", "validation_fraction")      # accepted with any value: none changes the model (the last two act only with n_iter_no_change)
+# The largest |y - mean(y)| a fit takes.  The split score squares n_r S_l - n_l S_r, at most 2 n^2 max |g| in size: with n <= 8 192 its square
+# stays below 2^54 (1e140)^2 < 1.8e296 in the first stage, and so do sum g^2 <= n (1e140)^2 and (y - raw)^2.  That leaves the square twelve
+# orders of magnitude, the residuals six, should a learning rate make them grow from stage to stage instead of shrink
+MAX_TARGET_SPREAD = 1e140
+
+
+def _regression_targets(y, n_rows, who):
+    """The targets as finite float64 [n] on the host, unrounded, and their mean (scikit-learn's ``DummyRegressor`` constant, ``np.average``)."""
+    y = np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y)
+    if y.ndim == 2 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.ndim != 1:
+        raise NotImplementedError(f"{who}: more than one output column is not supported, got y of shape {y.shape}")
+    try:
+        y = np.ascontiguousarray(y, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: y must be numeric, got dtype {y.dtype}") from None
+    if len(y) != n_rows:
+        raise ValueError(f"{who}: X has {n_rows} rows, y has {len(y)}")
+    if not np.isfinite(y).all():
+        raise ValueError(f"{who}: y contains NaN or infinity")
+    with np.errstate(over="ignore", invalid="ignore"):
+        init = float(np.average(y))
+        spread = float(np.abs(y - init).max())
+    if not np.isfinite(init) or not spread <= MAX_TARGET_SPREAD:
+        raise ValueError(f"{who}: the targets are too large: |y - mean| must not exceed {MAX_TARGET_SPREAD:g}, beyond which the split score, and "
+                         "further out (y - mean)^2 itself, overflows float64")
+    return y, init
+
+
+class GradientBoostingRegressor(_BoostedTrees):
+    """``GradientBoostingRegressor(n_estimators=100, *, learning_rate=0.1, max_depth=3, min_samples_split=2, min_samples_leaf=1,
+    loss="squared_error", random_state=None, device="cuda")``: scikit-learn's names for one output and the squared error -- the reference's
+    ``GradientBoostingRegressor(n_estimators=200, learning_rate=0.1, max_depth=5, random_state=42)`` of the logBB stack's bake-off
+    (Models/multi_input_data_regression_opt_transformer_cnn_opt_more.py:118-125).
+
+    ``fit`` takes a numpy array or a CUDA tensor [n, d] (n <= 8 192, d <= 1 024; cast to float32) and finite float64 targets [n] or [n, 1],
+    which reach the kernels unrounded.  Raw scores start at ``init_ = np.average(y)``; a stage fits one ``friedman_mse`` tree to ``g = y - raw``
+    through the classifier's rounds (``bbbp_gbr_fit``), a node's value is ``sum g / m`` -- scikit-learn leaves this loss's leaves as the tree
+    made them -- and ``raw += learning_rate * value[leaf]``.  Sets ``n_estimators_``, ``n_features_in_``, ``init_``, ``train_score_`` (the mean
+    of ``(y - raw)^2`` after each stage) and ``trees_`` in the classifier's convention.  ``predict`` returns float64 [m] (numpy for numpy
+    queries, a CUDA tensor for a CUDA tensor), ``staged_predict`` yields it after every stage, ``predict_device`` is ``predict`` for the
+    device-resident features of ``ensemble.screen(boosters=...)``.  ``random_state`` is accepted and unused: among equal computed scores
+    the lowest feature wins, then the lowest position, so trees are certified (``tests/gbr_replay.py``), not compared with scikit-learn's.
+    ``get_params`` / ``set_params`` make ``sklearn.base.clone`` work, so ``ensemble.StackingRegressor`` takes this class as a base learner.
+
+    Out of scope, each refused by name: other losses (``huber``, ``absolute_error``, ``quantile``) and ``alpha``, ``criterion !=
+    "friedman_mse"``, ``subsample < 1``, ``max_features``, ``init`` estimators, ``n_iter_no_change``, ``max_leaf_nodes``, ``ccp_alpha``,
+    ``min_impurity_decrease != 0``, ``warm_start``, ``sample_weight``, more than one output column, non-finite targets, targets further
+    than 1e140 from their mean (``MAX_TARGET_SPREAD``: beyond it the split score overflows float64), ``max_depth > 7`` or None, fractional
+    limits, more than 8 192 rows or 1 024 features.  ``verbose``, ``tol`` and ``validation_fraction`` are accepted and ignored: they do not
+    change the model.  There is no regressor grid search (the reference has none) and no CPU path."""
+
+    _who = "GradientBoostingRegressor"
+    _params = ("n_estimators", "learning_rate", "max_depth", "min_samples_split", "min_samples_leaf", "loss", "random_state", "device")
+
+    def __init__(self, n_estimators=100, *, learning_rate=0.1, max_depth=3, min_samples_split=2, min_samples_leaf=1, loss="squared_error",
+                 random_state=None, device="cuda", **other):
+        who = self._who
+        if loss != "squared_error":
+            raise NotImplementedError(f"{who}: loss={loss!r} is not supported (only 'squared_error')")
+        for name, value in other.items():
+            if name in _REGRESSOR_IGNORED:
+                continue
+            if name not in _REGRESSOR_DEFAULTS:
+                raise ValueError(f"{who}: unknown parameter {name}")
+            if value is not _REGRESSOR_DEFAULTS[name] and not (isinstance(value, (numbers.Real, str)) and value == _REGRESSOR_DEFAULTS[name]):
+                raise NotImplementedError(f"{who}: {name}={value!r} is not supported (only {_REGRESSOR_DEFAULTS[name]!r})")
+        _check_params(n_estimators, learning_rate, max_depth, min_samples_split, min_samples_leaf, who)
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"{who}: device {device!r}: trees are fitted on the GPU (no CPU fallback)")
+        # the parameters are kept as they were given: sklearn.base.clone compares them by identity
+        self.n_estimators, self.learning_rate, self.max_depth = n_estimators, learning_rate, max_depth
+        self.min_samples_split, self.min_samples_leaf, self.loss = min_samples_split, min_samples_leaf, loss
+        self.random_state, self.device = random_state, device          # random_state: accepted and unused, the tie rule is fixed
+
+    def get_params(self, deep=True):
+        return {name: getattr(self, name) for name in self._params}
+
+    def set_params(self, **params):
+        unknown = set(params) - set(self._params)
+        if unknown:
+            raise ValueError(f"{self._who}: unknown parameters {sorted(unknown)}")
+        type(self)(**params)           # the constructor's checks, on what is being set alone: every parameter is judged by itself, and an
+        for name, value in params.items():      # adopted model may hold a None where scikit-learn's value was not an int
+            setattr(self, name, value)
+        return self
+
+    # ---- fit --------------------------------------------------------------------------------------------------------
+    def fit(self, X, y, sample_weight=None):
+        if sample_weight is not None:
+            raise NotImplementedError(f"{self._who}: sample_weight is not supported")
+        _fit_regressors([self], [(X, y)])
+        return self
+
+    def _checked(self, X, y):
+        """(float32 X, the float64 targets, their mean), validated: no GPU call yet."""
+        X32 = _training_matrix32(X, self._who)
+        return (X32,) + _regression_targets(y, X32.shape[0], self._who)
+
+    def _chain(self, X32, y, init):
+        """The chain this regressor asks for, not yet fitted."""
+        dev = torch.device(self.device)
+        return _Chain(_Matrix(X32, dev), torch.from_numpy(y).to(dev), init, self.n_estimators, self.learning_rate, self.max_depth, self.min_samples_split,
+                      self.min_samples_leaf)
+
+    def _adopt(self, chain):
+        """Fitted attributes from a fitted chain."""
+        self._set_trees(chain.trees(), chain.init, chain.learning_rate, chain.mat.d)
+        self.train_score_ = chain.train_score.cpu().numpy().copy()
+        self._train_raw = chain.raw.cpu().numpy()              # the training rows' raw scores after the last stage (tests)
+
+    @classmethod
+    def from_sklearn(cls, fitted, device="cuda"):
+        """Adopt a fitted scikit-learn ``GradientBoostingRegressor`` (``loss="squared_error"``, ``init=None``) for prediction only: ``predict``
+        and every stage of ``staged_predict`` equal scikit-learn's bit for bit.  ``max_depth``, ``min_samples_split`` and ``min_samples_leaf``
+        are kept where they are ints and None otherwise; ``set_params`` works on an adopted model, but ``sklearn.base.clone`` of one that
+        holds such a None is refused, like any unfitted regressor with that value (an adopted model predicts, it is not refitted)."""
+        from sklearn.dummy import DummyRegressor
+        who = f"{cls.__name__}.from_sklearn"
+        if hasattr(fitted, "classes_") or getattr(fitted, "loss", None) != "squared_error" or fitted.estimators_.shape[1] != 1:
+            raise NotImplementedError(f"{who}: a fitted regressor with loss='squared_error' and one output is expected")
+        if not isinstance(fitted.init_, DummyRegressor) or fitted.init_.strategy != "mean":
+            raise NotImplementedError(f"{who}: init estimators are not supported (only init=None, the mean)")
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"{who}: device {device!r}: prediction runs on the GPU (no CPU fallback)")
+        trees, d = _sklearn_trees(fitted)
+        self = cls.__new__(cls)
+        # the fitting parameters are kept only where this class would accept them (scikit-learn allows None and fractions): an adopted
+        # model predicts, it is not refitted
+        self.n_estimators, self.learning_rate, self.loss, self.random_state, self.device = len(trees["root"]) - 1, float(fitted.learning_rate), "squared_error", None, device
+        for name in ("max_depth", "min_samples_split", "min_samples_leaf"):
+            setattr(self, name, getattr(fitted, name) if _is_int(getattr(fitted, name)) else None)
+        self._set_trees(trees, float(np.ravel(fitted.init_.constant_)[0]), float(fitted.learning_rate), d)
+        self.train_score_ = np.asarray(fitted.train_score_, dtype=np.float64).copy()
+        self._train_raw = None
+        return self
+
+    # ---- prediction -------------------------------------------------------------------------------------------------
+    def predict(self, X):
+        """[m] float64: ``init_`` plus ``learning_rate * value[leaf]`` of every tree in stage order."""
+        Xq, was_numpy = self._queries(X)
+        out = self._staged(Xq, [self.n_estimators_])[0]
+        return out.cpu().numpy() if was_numpy else out
+
+    def staged_predict(self, X):
+        """Yields the predictions [m] after 1, 2, ... trees (computed in one pass over the trees)."""
+        Xq, was_numpy = self._queries(X)
+        out = self._staged(Xq, range(1, self.n_estimators_ + 1))
+        out = out.cpu().numpy() if was_numpy else out
+        for s in range(self.n_estimators_):
+            yield out[s]
+
+    def predict_device(self, X):
+        """``predict`` for a CUDA tensor [m, d]: float64 [m] on the device (what ``ensemble.screen`` asks of its ``boosters``)."""
+        if not isinstance(X, torch.Tensor):
+            raise TypeError(f"{self._who}.predict_device: expected a CUDA (HIP) tensor, got {type(X).__name__}")
+        return self.predict(X)
+
+
+def _fit_regressors(regressors, problems):
+    """Fit the chains of ``regressors[i]`` over ``problems[i] = (X, y)`` in one ``bbbp_gbr_fit`` batch and every regressor from its own."""
+    checked = [reg._checked(X, y) for reg, (X, y) in zip(regressors, problems)]
+    with torch.cuda.device(torch.device(regressors[0].device)):
+        chains = [reg._chain(*c) for reg, c in zip(regressors, checked)]
+        keep = _fit_chains(chains, "bbbp_gbr_fit")
+        for reg, chain in zip(regressors, chains):
+            reg._adopt(chain)
+        del keep
+
+
+def fit_regressors(problems, **params):
+    """``[GradientBoostingRegressor(**params).fit(X, y) for X, y in problems]`` with every problem's chain in one batch: the bake-off's
+    five folds and the refit are one call.  Each regressor equals its single ``fit`` bit for bit."""
+    problems = list(problems)
+    if not problems:
+        raise ValueError("gradient_boosting.fit_regressors: no problems")
+    regressors = [GradientBoostingRegressor(**params) for _ in problems]
+    _fit_regressors(regressors, problems)
+    return regressors

@@ -603,6 +603,13 @@ size_t bbbp_gbt_fit_work_bytes(int n, int d);
  * `chains` is a host array, `chains_device` the same bytes in device memory (the kernels read their descriptors there).  A chain's
  * numbers do not depend on what else is in the batch. */
 int bbbp_gbt_fit(void* stream, const bbbp_gbt_chain* chains, const bbbp_gbt_chain* chains_device, int n_chains);
+/* The same fit under the squared error: GradientBoostingRegressor of the logBB stack's bake-off
+ * (Models/multi_input_data_regression_opt_transformer_cnn_opt_more.py:118-125).  Same descriptor, limits, work area and tree capacity;
+ * the fields read: y the float64 targets (any finite values), init their mean, value = sum g / m in every node, split node and leaf
+ * alike, with g = y - raw (scikit-learn skips the leaf update for this loss: the tree's own node mean is the step), train_score[t] the
+ * mean of (y - raw)^2 after stage t.  Messages carry the prefix gbr_fit.  The stats, split, choose, side and partition rules, the tie
+ * rule and the determinism are bbbp_gbt_fit's; bbbp_gbt_staged_decision predicts. */
+int bbbp_gbr_fit(void* stream, const bbbp_gbt_chain* chains, const bbbp_gbt_chain* chains_device, int n_chains);
 /* out[s][q] = init + sum over the first stages[s] trees, in tree order, of learning_rate * value[leaf] (scikit-learn's predict_stages
  * order, product and sum rounded separately) for query rows X [m][d] float32: one pass over the trees.  Children are absolute indices
  * into the node arrays, root[t] is tree t's first node; `stages` (device, [n_stages]) ascends strictly within 1..n_trees; a row goes
