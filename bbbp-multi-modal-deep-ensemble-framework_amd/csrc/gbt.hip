@@ -29,6 +29,7 @@
 // value is sum g / m (scikit-learn skips the leaf update for this loss), the stage score is the mean of (y - raw)^2.
 #include "common.h"
 #include "bbbp_hip.h"
+#include "tree_fit.h"
 
 #include <math.h>
 
@@ -57,19 +58,18 @@ struct Work {                                 // offsets into a chain's `work`, 
 };
 __host__ __device__ inline Work work_layout(int n, int d) {
     Work w;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { size_t o = at; at += (bytes + 15) / 16 * 16; return o; };
-    w.order[0] = take((size_t)d * n * 4);
-    w.order[1] = take((size_t)d * n * 4);
-    w.key = take((size_t)n);
-    w.g = take((size_t)n * 8);
-    w.tab[0] = take(sizeof(KeyTab));
-    w.tab[1] = take(sizeof(KeyTab));
-    w.split = take(sizeof(SplitTab));
-    w.cand_enc = take((size_t)d * GBT_SPLIT_KEYS * 8);
-    w.cand_pos = take((size_t)d * GBT_SPLIT_KEYS * 4);
-    w.state = take(sizeof(ChainState));
-    w.total = at;
+    Area a;
+    w.order[0] = a.take((size_t)d * n * 4);
+    w.order[1] = a.take((size_t)d * n * 4);
+    w.key = a.take((size_t)n);
+    w.g = a.take((size_t)n * 8);
+    w.tab[0] = a.take(sizeof(KeyTab));
+    w.tab[1] = a.take(sizeof(KeyTab));
+    w.split = a.take(sizeof(SplitTab));
+    w.cand_enc = a.take((size_t)d * GBT_SPLIT_KEYS * 8);
+    w.cand_pos = a.take((size_t)d * GBT_SPLIT_KEYS * 4);
+    w.state = a.take(sizeof(ChainState));
+    w.total = a.at;
     return w;
 }
 
@@ -92,14 +92,7 @@ __device__ inline View view_of(const bbbp_gbt_chain& c) {
 __device__ inline const int* order_src(const bbbp_gbt_chain& c, const View& v, int level) { return level == 0 ? c.order0 : (((level - 1) & 1) ? v.order_b : v.order_a); }
 __device__ inline int* order_dst(const View& v, int level) { return (level & 1) ? v.order_b : v.order_a; }
 __device__ inline KeyTab* tab_of(const View& v, int level) { return (level & 1) ? v.tab_b : v.tab_a; }       // selects, not indexed arrays: no scratch
-// A row index read from an order array, kept inside [0, n): a wrong order never gives a wild address.  It cannot happen while the kernels
-// are right; if it does, the chain's error word is set (every writer stores the same 1) and `update` reports it as tree_nodes[t] = -1
-__device__ inline int row_of(const int* src, int p, int n, ChainState* st) {
-    const int i = src[p];
-    if ((unsigned)i < (unsigned)n) return i;
-    st->error = 1;
-    return 0;
-}
+// row_of (tree_fit.h) sets the chain's error word, which `update` reports as tree_nodes[t] = -1
 __device__ inline bool chain_idle(const bbbp_gbt_chain& c, const ChainState* st) { return st->tree >= c.n_estimators; }
 
 // ---- the loss: a compile-time parameter of the kernels that know about it (init, stats, choose's late leaf, update) ------------------
@@ -201,7 +194,7 @@ __global__ __launch_bounds__(256) void gbt_stats_kernel(const bbbp_gbt_chain* ch
             c.n_node_samples[node] = m;
             if (leaf) {
                 tab->flag[k] = KEY_LEAF;
-                c.left[node] = -1; c.right[node] = -1; c.feature[node] = 0; c.threshold[node] = -2.0;
+                make_leaf(c, node);
                 if constexpr (Loss::kNewton) c.value[node] = Loss::leaf_value(sg, spq, m);
                 else c.value[node] = mean;
             } else {
@@ -260,21 +253,14 @@ __global__ __launch_bounds__(GBT_SCAN) void gbt_split_kernel(const bbbp_gbt_chai
         const double x = act ? sg[i] : 0.0;
         const double carry = slot[GBT_SCAN];                // the inclusive sum at position base - 1
         // segmented inclusive scan inside the wave: a segment starts at its node's first position (and at every position past the end)
+        const auto add = [](double a, double b) { return a + b; };
         double val = x;
         int flg = (!in || p == s) ? 1 : 0;
-        for (int off = 1; off < 64; off <<= 1) {
-            const double pv = __shfl_up(val, off);
-            const int pf = __shfl_up(flg, off);
-            if (lane >= off) {
-                if (!flg) val = pv + val;
-                flg |= pf;
-            }
-        }
+        wave_segmented_scan(val, flg, add);
         if (lane == 63) { wave_val[wave] = val; wave_flag[wave] = flg; }
         if (tid < GBT_SPLIT_KEYS) { pass_enc[tid] = 0ull; pass_pos[tid] = 0x7fffffff; }
         __syncthreads();
-        double pre = carry;                                 // what precedes this wave in its first segment
-        for (int w = 0; w < wave; ++w) pre = wave_flag[w] ? wave_val[w] : pre + wave_val[w];
+        const double pre = block_segment_prefix(carry, wave_val, wave_flag, add);
         if (!flg) val = pre + val;
         slot[1 + tid] = val;
         if (tid == 0) slot[0] = carry;
@@ -289,7 +275,7 @@ __global__ __launch_bounds__(GBT_SCAN) void gbt_split_kernel(const bbbp_gbt_chai
                 const double s_l = slot[tid], s_r = ksum[k] - s_l;
                 const double diff = (double)n_r * s_l - (double)n_l * s_r;
                 const double score = diff * diff / ((double)n_l * (double)n_r);
-                enc = (unsigned long long)__double_as_longlong(score) + 1ull;      // scores are >= 0: their bits order as integers; 0 = none
+                enc = encode_score(score);
                 atomicMax(&pass_enc[k], enc);
             }
         }
@@ -338,8 +324,7 @@ __global__ __launch_bounds__(64) void gbt_choose_kernel(const bbbp_gbt_chain* ch
     if (split) {
         const int* src = order_src(c, v, level) + (long)bf * n;
         const float a = c.XT[(long)bf * n + row_of(src, bp - 1, n, v.st)], b = c.XT[(long)bf * n + row_of(src, bp, n, v.st)];
-        double thr = (double)a / 2.0 + (double)b / 2.0;
-        if (thr == (double)b) thr = (double)a;
+        const double thr = split_threshold(a, b);
         n_left = bp - s;
         const int lc = n_nodes + 2 * rank, rc = lc + 1;
         c.left[base + node] = lc; c.right[base + node] = rc; c.feature[base + node] = bf; c.threshold[base + node] = thr;
@@ -348,7 +333,7 @@ __global__ __launch_bounds__(64) void gbt_choose_kernel(const bbbp_gbt_chain* ch
         next->start[2 * k + 1] = s + n_left; next->cnt[2 * k + 1] = m - n_left; next->node[2 * k + 1] = rc; next->flag[2 * k + 1] = KEY_ACTIVE;
     } else if (in) {
         if (flag == KEY_ACTIVE) {                           // no valid split: a leaf after all
-            c.left[base + node] = -1; c.right[base + node] = -1; c.feature[base + node] = 0; c.threshold[base + node] = -2.0;
+            make_leaf(c, base + node);
             if constexpr (Loss::kNewton) c.value[base + node] = Loss::leaf_value(tab->sum_g[k], tab->sum_pq[k], m);      // else: stats wrote the mean
         }
         const int keep = flag == KEY_EMPTY ? KEY_EMPTY : KEY_LEAF;
@@ -386,7 +371,7 @@ __global__ __launch_bounds__(GBT_SCAN) void gbt_partition_kernel(const bbbp_gbt_
     const bbbp_gbt_chain c = chains[blockIdx.y];
     const View v = view_of(c);
     if (chain_idle(c, v.st) || v.st->final) return;
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = c.n;
+    const int f = blockIdx.x, tid = threadIdx.x, n = c.n;
     if (f >= c.d) return;                                   // the grid is sized for the widest chain of the batch
     const int level = v.st->level, nk = 1 << level;
     const KeyTab* tab = tab_of(v, level);
@@ -411,13 +396,7 @@ __global__ __launch_bounds__(GBT_SCAN) void gbt_partition_kernel(const bbbp_gbt_
         const int i = in ? row_of(src, p, n, v.st) : 0;
         const int key = in ? skey[i] : 0;
         const bool left = in && !(key & 1);
-        const unsigned long long ballot = __ballot(left);
-        int* wc = wave_cnt + (it & 1) * 4;
-        if (lane == 0) wc[wave] = __popcll(ballot);
-        __syncthreads();
-        int lefts = before + __popcll(ballot & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; ++w) lefts += wc[w];
-        before += wc[0] + wc[1] + wc[2] + wc[3];
+        const int lefts = block_rank_before(left, wave_cnt + (it & 1) * 4, before);
         if (in) {
             const int k = (key >> 1) & (GBT_SPLIT_KEYS - 1);
             const int in_seg = lefts - kbase[k];                      // rows of this segment going left in front of p

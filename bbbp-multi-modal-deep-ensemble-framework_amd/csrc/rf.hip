@@ -39,6 +39,7 @@
 // have a regression form; draw, choose, side and partition do not depend on the criterion.
 #include "common.h"
 #include "bbbp_hip.h"
+#include "tree_fit.h"
 
 #include <limits.h>
 #include <math.h>
@@ -75,21 +76,20 @@ struct Work {                                 // offsets into a tree's `work`, i
 };
 __host__ __device__ inline Work work_layout(int n, int d, int mf) {
     Work w;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { size_t o = at; at += (bytes + 15) / 16 * 16; return o; };
+    Area a;
     const size_t N = (size_t)n;
-    w.order[0] = take((size_t)d * N * 2); w.order[1] = take((size_t)d * N * 2);
-    w.hist = take(N * 4); w.wy = take(N * 4); w.slot = take(N * 2);
-    w.tab_start[0] = take(N * 4); w.tab_cnt[0] = take(N * 4); w.tab_node[0] = take(N * 4); w.tab_key[0] = take(N * 8);      // no loop: an indexed
-    w.tab_start[1] = take(N * 4); w.tab_cnt[1] = take(N * 4); w.tab_node[1] = take(N * 4); w.tab_key[1] = take(N * 8);      // member goes to scratch
-    w.flag = take(N * 4); w.wtot = take(N * 4); w.ndrawn = take(N * 4); w.left_base = take(N * 4);
-    w.sp_rank = take(N * 4); w.sp_feature = take(N * 4); w.sp_thr = take(N * 8);
-    w.code = take(N * (size_t)d * 2); w.feat = take(N * (size_t)mf * 2);
-    w.cand_enc = take(N * (size_t)mf * 8); w.cand_pos = take(N * (size_t)mf * 4);
-    w.state = take(sizeof(TreeState));
-    w.total = at;
-    w.wq = take(N * 8); w.w16 = take(N * 2); w.stot = take(N * 8);
-    w.total_regression = at;
+    w.order[0] = a.take((size_t)d * N * 2); w.order[1] = a.take((size_t)d * N * 2);
+    w.hist = a.take(N * 4); w.wy = a.take(N * 4); w.slot = a.take(N * 2);
+    w.tab_start[0] = a.take(N * 4); w.tab_cnt[0] = a.take(N * 4); w.tab_node[0] = a.take(N * 4); w.tab_key[0] = a.take(N * 8);      // no loop: an indexed
+    w.tab_start[1] = a.take(N * 4); w.tab_cnt[1] = a.take(N * 4); w.tab_node[1] = a.take(N * 4); w.tab_key[1] = a.take(N * 8);      // member goes to scratch
+    w.flag = a.take(N * 4); w.wtot = a.take(N * 4); w.ndrawn = a.take(N * 4); w.left_base = a.take(N * 4);
+    w.sp_rank = a.take(N * 4); w.sp_feature = a.take(N * 4); w.sp_thr = a.take(N * 8);
+    w.code = a.take(N * (size_t)d * 2); w.feat = a.take(N * (size_t)mf * 2);
+    w.cand_enc = a.take(N * (size_t)mf * 8); w.cand_pos = a.take(N * (size_t)mf * 4);
+    w.state = a.take(sizeof(TreeState));
+    w.total = a.at;
+    w.wq = a.take(N * 8); w.w16 = a.take(N * 2); w.stot = a.take(N * 8);
+    w.total_regression = a.at;
     return w;
 }
 
@@ -123,14 +123,7 @@ __device__ inline Table table_of(const View& v, int level) {
     const bool b = level & 1;
     return Table{pick(b, v.tab_a.start, v.tab_b.start), pick(b, v.tab_a.cnt, v.tab_b.cnt), pick(b, v.tab_a.node, v.tab_b.node), pick(b, v.tab_a.key, v.tab_b.key)};
 }
-// A row index read from an order array, kept inside [0, n): a wrong order never gives a wild address.  It cannot happen while the kernels are
-// right; if it does, the tree's error word is set (every writer stores the same 1) and `choose` reports it as n_nodes = -1
-__device__ inline int row_of(const uint16_t* src, int p, int n, TreeState* st) {
-    const int i = src[p];
-    if (i < n) return i;
-    st->error = 1;
-    return 0;
-}
+// row_of (tree_fit.h) sets the tree's error word, which `choose` reports as n_nodes = -1
 // A node's segment, kept inside [0, n_eff): s >= 0, m >= 1, s + m <= n_eff, or the empty segment and the error word
 __device__ inline void segment_of(const Table& tab, int k, int n_eff, TreeState* st, int& s, int& m) {
     s = tab.start[k]; m = tab.cnt[k];
@@ -144,8 +137,7 @@ __device__ inline unsigned sum_add(unsigned a, unsigned b) { return a + b; }
 __device__ inline Sum64 sum_add(Sum64 a, Sum64 b) { return Sum64{a.s + b.s, a.w + b.w}; }
 __device__ inline unsigned sum_sub(unsigned a, unsigned b) { return a - b; }
 __device__ inline Sum64 sum_sub(Sum64 a, Sum64 b) { return Sum64{a.s - b.s, a.w - b.w}; }
-__device__ inline unsigned sum_up(unsigned v, int off) { return (unsigned)__shfl_up((int)v, off); }
-__device__ inline Sum64 sum_up(Sum64 v, int off) { return Sum64{__shfl_up(v.s, off), (unsigned)__shfl_up((int)v.w, off)}; }
+__device__ inline Sum64 lane_up(Sum64 v, int off) { return Sum64{__shfl_up(v.s, off), (unsigned)__shfl_up((int)v.w, off)}; }
 // Gini: (W_R L_1 - W_L R_1)^2 / (W_L W_R); false when a side has no weight (cannot happen at a valid position)
 __device__ inline bool score_of(unsigned tot, unsigned left, double& score) {
     const long long W = tot >> 16, W1 = tot & 0xffffu, WL = left >> 16, L1 = left & 0xffffu, WR = W - WL, R1 = W1 - L1;
@@ -185,7 +177,7 @@ __global__ __launch_bounds__(256) void rf_init_boot_kernel(const bbbp_rf_tree* t
 template <bool REG> __global__ __launch_bounds__(RF_SCAN) void rf_init_compact_kernel(const bbbp_rf_tree* trees) {
     const bbbp_rf_tree c = trees[blockIdx.y];
     const View v = view_of(c);
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = c.n;
+    const int f = blockIdx.x, tid = threadIdx.x, n = c.n;
     if (f >= c.d) return;                                   // the grid is sized for the widest tree of the batch
     __shared__ int wave_cnt[2][4];
     const int* src = c.order0 + (long)f * n;
@@ -196,13 +188,7 @@ template <bool REG> __global__ __launch_bounds__(RF_SCAN) void rf_init_compact_k
         int i = p < n ? src[p] : 0;
         if ((unsigned)i >= (unsigned)n) { v.st->error = 1; i = 0; }
         const bool keep = p < n && v.hist[i] > 0u;
-        const unsigned long long ballot = __ballot(keep);
-        int* wc = wave_cnt[it & 1];
-        if (lane == 0) wc[wave] = __popcll(ballot);
-        __syncthreads();
-        int to = before + __popcll(ballot & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; ++w) to += wc[w];
-        before += wc[0] + wc[1] + wc[2] + wc[3];
+        const int to = block_rank_before(keep, wave_cnt[it & 1], before);
         if (keep) dst[to] = (uint16_t)i;                    // to < n: it counts kept rows in front of p
     }
     if (f != 0) return;
@@ -227,7 +213,7 @@ template <bool REG> __global__ __launch_bounds__(RF_SCAN) void rf_init_compact_k
 }
 
 // ---- stats: the level's nodes: totals, n_node_samples, value, the stop rules ------------------------------------------------------------
-__global__ __launch_bounds__(256) void rf_stats_kernel(const bbbp_rf_tree* trees) {
+template <bool REG> __global__ __launch_bounds__(256) void rf_stats_kernel(const bbbp_rf_tree* trees) {
     const bbbp_rf_tree c = trees[blockIdx.y];
     const View v = view_of(c);
     if (v.st->done) return;
@@ -238,71 +224,52 @@ __global__ __launch_bounds__(256) void rf_stats_kernel(const bbbp_rf_tree* trees
     for (int k = blockIdx.x * 4 + wave; k < nk; k += gridDim.x * 4) {
         int s, m;
         segment_of(tab, k, n_eff, v.st, s, m);
-        unsigned acc = 0u;
-        for (int p = lane; p < m; p += 64) acc += v.wy[row_of(src, s + p, c.n, v.st)];
-        for (int off = 32; off >= 1; off >>= 1) acc += (unsigned)__shfl_xor((int)acc, off);
-        if (lane != 0) continue;
-        const unsigned W = acc >> 16, W1 = acc & 0xffffu;
+        bool bad, pure;
+        double value, value0;
+        if constexpr (REG) {                                // S = sum w q, W = sum w, min q and max q over the node's rows; value = S / W, value0 = W
+            long long S = 0, lo = LLONG_MAX, hi = LLONG_MIN;
+            unsigned W = 0u;
+            for (int p = lane; p < m; p += 64) {
+                const int i = row_of(src, s + p, c.n, v.st);
+                const unsigned w = v.w16[i];
+                const long long wq = v.wq[i], q = w ? wq / (long long)w : 0;               // exact: wq is w times an integer
+                S += wq; W += w;
+                lo = q < lo ? q : lo; hi = q > hi ? q : hi;
+            }
+            for (int off = 32; off >= 1; off >>= 1) {
+                S += __shfl_xor(S, off); W += (unsigned)__shfl_xor((int)W, off);
+                const long long ol = __shfl_xor(lo, off), oh = __shfl_xor(hi, off);
+                lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi;
+            }
+            if (lane != 0) continue;
+            // scikit-learn's rule is impurity <= EPSILON; here a node is pure when all its targets are one integer (DESIGN.md compares the two)
+            bad = W == 0u; pure = lo == hi;
+            value = W ? (double)S / (double)W : 0.0; value0 = (double)W;
+            v.wtot[k] = W; v.stot[k] = S;
+        } else {
+            unsigned acc = 0u;
+            for (int p = lane; p < m; p += 64) acc += v.wy[row_of(src, s + p, c.n, v.st)];
+            for (int off = 32; off >= 1; off >>= 1) acc += (unsigned)__shfl_xor((int)acc, off);
+            if (lane != 0) continue;
+            const unsigned W = acc >> 16, W1 = acc & 0xffffu;
+            // scikit-learn's impurity <= EPSILON: with integer weights W <= 8192 the Gini impurity is 0 for a pure node and at least
+            // (2 W - 2) / W^2 > 2.4e-4 otherwise
+            bad = W == 0u || W1 > W; pure = W1 == 0u || W1 == W;
+            value = W ? (double)W1 / (double)W : 0.0; value0 = W ? (double)(W - W1) / (double)W : 0.0;
+            v.wtot[k] = acc;
+        }
         int node = tab.node[k];
-        if ((unsigned)node >= (unsigned)cap || W == 0u || W1 > W) { v.st->error = 1; node = 0; }
-        // scikit-learn's impurity <= EPSILON: with integer weights W <= 8192 the Gini impurity is 0 for a pure node and at least
-        // (2 W - 2) / W^2 > 2.4e-4 otherwise
-        const bool leaf = level >= c.max_depth || m < c.min_samples_split || m < 2 * c.min_samples_leaf || W1 == 0u || W1 == W;
+        if ((unsigned)node >= (unsigned)cap || bad) { v.st->error = 1; node = 0; }
+        const bool leaf = level >= c.max_depth || m < c.min_samples_split || m < 2 * c.min_samples_leaf || pure;
         c.n_node_samples[node] = m;
-        c.value[node] = W ? (double)W1 / (double)W : 0.0;
-        c.value0[node] = W ? (double)(W - W1) / (double)W : 0.0;
-        v.wtot[k] = acc;
+        c.value[node] = value;
+        c.value0[node] = value0;
         if (leaf) {
             v.flag[k] = NODE_LEAF;
-            c.left[node] = -1; c.right[node] = -1; c.feature[node] = 0; c.threshold[node] = -2.0;
+            make_leaf(c, node);
         } else {
             v.flag[k] = NODE_ACTIVE;
             v.st->active = 1;                               // every writer stores the same 1; `choose` clears it for the next level
-        }
-    }
-}
-
-// The regression form: S = sum w q, W = sum w, min q and max q over the node's rows; value = S / W, value0 = W
-__global__ __launch_bounds__(256) void rf_stats_regression_kernel(const bbbp_rf_tree* trees) {
-    const bbbp_rf_tree c = trees[blockIdx.y];
-    const View v = view_of(c);
-    if (v.st->done) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int level = v.st->level, nk = min(v.st->nk, c.n), n_eff = min(v.st->n_eff, c.n), cap = tree_capacity(c.n);
-    const Table tab = table_of(v, level);
-    const uint16_t* src = order_of(v, level);
-    for (int k = blockIdx.x * 4 + wave; k < nk; k += gridDim.x * 4) {
-        int s, m;
-        segment_of(tab, k, n_eff, v.st, s, m);
-        long long S = 0, lo = LLONG_MAX, hi = LLONG_MIN;
-        unsigned W = 0u;
-        for (int p = lane; p < m; p += 64) {
-            const int i = row_of(src, s + p, c.n, v.st);
-            const unsigned w = v.w16[i];
-            const long long wq = v.wq[i], q = w ? wq / (long long)w : 0;               // exact: wq is w times an integer
-            S += wq; W += w;
-            lo = q < lo ? q : lo; hi = q > hi ? q : hi;
-        }
-        for (int off = 32; off >= 1; off >>= 1) {
-            S += __shfl_xor(S, off); W += (unsigned)__shfl_xor((int)W, off);
-            const long long ol = __shfl_xor(lo, off), oh = __shfl_xor(hi, off);
-            lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi;
-        }
-        if (lane != 0) continue;
-        int node = tab.node[k];
-        if ((unsigned)node >= (unsigned)cap || W == 0u) { v.st->error = 1; node = 0; }
-        // scikit-learn's rule is impurity <= EPSILON; here a node is pure when all its targets are one integer (DESIGN.md compares the two)
-        const bool leaf = level >= c.max_depth || m < c.min_samples_split || m < 2 * c.min_samples_leaf || lo == hi;
-        c.n_node_samples[node] = m;
-        c.value[node] = W ? (double)S / (double)W : 0.0;
-        c.value0[node] = (double)W;
-        v.wtot[k] = W; v.stot[k] = S;
-        if (leaf) {
-            v.flag[k] = NODE_LEAF;
-            c.left[node] = -1; c.right[node] = -1; c.feature[node] = 0; c.threshold[node] = -2.0;
-        } else {
-            v.flag[k] = NODE_ACTIVE;
-            v.st->active = 1;
         }
     }
 }
@@ -411,22 +378,14 @@ template <bool REG> __global__ __launch_bounds__(RF_SCAN) void rf_split_kernel(c
         if (act) { if constexpr (REG) x = Sum64{swq[i], sw[i]}; else x = swy[i]; }
         const Sum carry = carry_s;                          // the inclusive sum at position base - 1, inside its segment
         // segmented inclusive scan inside the wave: a segment starts at its node's first position and at every position that is not scored
+        const auto add = [](Sum a, Sum b) { return sum_add(a, b); };
         Sum val = x;
         int flg = (!act || p == s) ? 1 : 0;
         const int own = flg;
-        for (int off = 1; off < 64; off <<= 1) {
-            const Sum pv = sum_up(val, off);
-            const int pf = __shfl_up(flg, off);
-            if (lane >= off) {
-                if (!flg) val = sum_add(val, pv);
-                flg |= pf;
-            }
-        }
+        wave_segmented_scan(val, flg, add);
         if (lane == 63) { wave_val[wave] = val; wave_flag[wave] = flg; }
         __syncthreads();
-        Sum pre = carry;                                    // what precedes this wave in its first segment
-        for (int w = 0; w < wave; ++w) pre = wave_flag[w] ? wave_val[w] : sum_add(pre, wave_val[w]);
-        if (!flg) val = sum_add(val, pre);
+        if (!flg) val = sum_add(val, block_segment_prefix(carry, wave_val, wave_flag, add));
         if (tid == RF_SCAN - 1) carry_s = val;
         // the candidate between positions p - 1 and p
         unsigned long long enc = 0ull;
@@ -436,7 +395,7 @@ template <bool REG> __global__ __launch_bounds__(RF_SCAN) void rf_split_kernel(c
             if (fv > fv_prev + RF_FEATURE_THRESHOLD && n_l >= msl && n_r >= msl) {
                 double score = 0.0;
                 if (!score_of(wt, sum_sub(val, x), score)) v.st->error = 1;        // the exclusive sum: everything in front of p in the segment
-                else enc = (unsigned long long)__double_as_longlong(score) + 1ull;     // scores are >= 0: their bits order as integers; 0 = none
+                else enc = encode_score(score);
             }
         }
         // segmented arg-max with the same segments: the lowest position among equal scores
@@ -522,8 +481,7 @@ __global__ __launch_bounds__(256) void rf_choose_kernel(const bbbp_rf_tree* tree
         if (split) {
             const uint16_t* src = order_of(v, level) + (long)bf * n;
             const float a = c.XT[(long)bf * n + row_of(src, bp - 1, n, v.st)], b = c.XT[(long)bf * n + row_of(src, bp, n, v.st)];
-            double thr = (double)a / 2.0 + (double)b / 2.0;
-            if (thr == (double)b) thr = (double)a;
+            const double thr = split_threshold(a, b);
             const int lc = st.n_nodes + 2 * r, rc = lc + 1;
             if (rc >= cap || 2 * r + 1 >= n) { v.st->error = 1; v.sp_rank[k] = -1; }      // cannot happen: a level's nodes are non-empty and disjoint
             else {
@@ -536,7 +494,7 @@ __global__ __launch_bounds__(256) void rf_choose_kernel(const bbbp_rf_tree* tree
             }
         } else if (k < nk) {
             v.sp_rank[k] = -1;
-            if (on) { c.left[node] = -1; c.right[node] = -1; c.feature[node] = 0; c.threshold[node] = -2.0; }       // no valid split: a leaf after all
+            if (on) make_leaf(c, node);                     // no valid split: a leaf after all
         }
         // the running totals: the last thread's inclusive sums
         __syncthreads();
@@ -580,7 +538,7 @@ __global__ __launch_bounds__(RF_SCAN) void rf_partition_kernel(const bbbp_rf_tre
     const bbbp_rf_tree c = trees[blockIdx.y];
     const View v = view_of(c);
     if (v.st->done) return;
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = c.n;
+    const int f = blockIdx.x, tid = threadIdx.x, n = c.n;
     if (f >= c.d) return;                                   // the grid is sized for the widest tree of the batch
     const int level = v.st->level - 1, nk_new = min(v.st->nk, n), n_eff = min(v.st->n_eff, n);
     if (level < 0) return;
@@ -600,13 +558,7 @@ __global__ __launch_bounds__(RF_SCAN) void rf_partition_kernel(const bbbp_rf_tre
         unsigned cs = in ? sslot[i] : RF_DEAD;
         if (cs != RF_DEAD && cs >= (unsigned)nk_new) { v.st->error = 1; cs = RF_DEAD; }
         const bool moving = cs != RF_DEAD, left = moving && !(cs & 1u);
-        const unsigned long long ballot = __ballot(left);
-        int* wc = wave_cnt[it & 1];
-        if (lane == 0) wc[wave] = __popcll(ballot);
-        __syncthreads();
-        int lefts = before + __popcll(ballot & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; ++w) lefts += wc[w];
-        before += wc[0] + wc[1] + wc[2] + wc[3];
+        const int lefts = block_rank_before(left, wave_cnt[it & 1], before);
         if (in) {
             int to = p;                                               // a row of a leaf stays where it is
             if (moving) {
@@ -721,7 +673,7 @@ template <bool REG> int fit_trees(void* stream, const bbbp_rf_tree* trees, const
     for (int b = 0; b < max_blocks; ++b) {
         BBBP_CHECK_HIP(hipMemsetAsync(alive_device, 0, sizeof(int), st));
         for (int r = 0; r < RF_BLOCK_ROUNDS; ++r) {
-            hipLaunchKernelGGL(REG ? rf_stats_regression_kernel : rf_stats_kernel, nodes, dim3(256), 0, st, trees_device);
+            hipLaunchKernelGGL(rf_stats_kernel<REG>, nodes, dim3(256), 0, st, trees_device);
             hipLaunchKernelGGL(rf_draw_kernel, nodes, dim3(256), 0, st, trees_device);
             hipLaunchKernelGGL(rf_split_kernel<REG>, feats, dim3(RF_SCAN), split_lds, st, trees_device);
             hipLaunchKernelGGL(rf_choose_kernel, one, dim3(256), 0, st, trees_device, alive_device, r == RF_BLOCK_ROUNDS - 1 ? 1 : 0);

@@ -30,28 +30,26 @@ value is ``sum g / m`` in leaves and split nodes alike, ``train_score_`` is the 
 the query path and the staged kernel with the classifier; ``fit_regressors`` fits the five folds and the refit in one batch.  Its trees
 are certified by ``tests/gbr_replay.py``; on continuous features, where exact ties arise only between candidates that part the rows the
 same way, its training-row predictions also agree with scikit-learn's to a few ulp.  The regressor's docstring lists what it refuses.
+
+The training matrix (``Matrix``), the input checks, the flattening of scikit-learn's trees and the small uploads are shared with
+``random_forest`` and live in ``_tree_host.py``; the kernels' shared device code is ``csrc/tree_fit.h``.
 """
 from __future__ import annotations
 
 import numbers
-import types
 
 import numpy as np
 import torch
 
-from . import _dense, _lib
+from . import _dense, _lib, _tree_host
+from ._tree_host import Matrix as _Matrix, is_int as _is_int          # shared with random_forest: they live in _tree_host.py
 from .linear_model import _binary_targets
-from .trees import ForestGPU
 
 MAX_ROWS, MAX_FEATURES, MAX_DEPTH, MAX_TREES = 8192, 1024, 7, 10000        # BBBP_GBT_FIT_MAX_*
 GRID_KEYS = ("n_estimators", "learning_rate", "max_depth", "min_samples_split", "min_samples_leaf")
 EPS32 = float(np.finfo(np.float32).eps)
 _SKLEARN_DEFAULTS = dict(loss="log_loss", criterion="friedman_mse", subsample=1.0, max_features=None, init=None, n_iter_no_change=None,
                          max_leaf_nodes=None, ccp_alpha=0.0, min_impurity_decrease=0.0, min_weight_fraction_leaf=0.0, warm_start=False)
-
-
-def _is_int(v):
-    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
 
 
 def _check_params(n_estimators, learning_rate, max_depth, min_samples_split, min_samples_leaf, who="GradientBoostingClassifier"):
@@ -75,53 +73,14 @@ def _check_params(n_estimators, learning_rate, max_depth, min_samples_split, min
         raise ValueError(f"{who}: min_samples_leaf must be an int >= 1, got {min_samples_leaf!r}")
 
 
-def _check_shape(n, d, who):
-    if n < 2 or d < 1:
-        raise ValueError(f"{who}: need at least two rows and one feature, got shape {(n, d)}")
-    if n > MAX_ROWS:
-        raise ValueError(f"{who}: n = {n} rows, at most {MAX_ROWS} are supported (BBBP_GBT_FIT_MAX_N)")
-    if d > MAX_FEATURES:
-        raise ValueError(f"{who}: d = {d} features, at most {MAX_FEATURES} are supported (BBBP_GBT_FIT_MAX_D)")
-
-
 def _training_matrix32(X, who):
-    """X as float32 [n, d], numpy (host) or a CUDA tensor, checked for shape and finiteness; a numpy input never touches the GPU here."""
-    if isinstance(X, torch.Tensor):
-        if not X.is_cuda:
-            raise RuntimeError(f"{who}: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
-        if X.dim() != 2:
-            raise ValueError(f"{who}: expected a 2-D [n, d] input, got shape {tuple(X.shape)}")
-        _check_shape(X.shape[0], X.shape[1], who)
-        X32 = X.to(torch.float32)
-        if not bool(torch.isfinite(X32).all()):
-            raise ValueError(f"{who}: X contains NaN, infinity or a value too large for float32")
-        return X32
-    X = np.asarray(X)
-    if X.ndim != 2:
-        raise ValueError(f"{who}: expected a 2-D [n, d] input, got shape {X.shape}")
-    _check_shape(X.shape[0], X.shape[1], who)
-    with np.errstate(over="ignore"):
-        X32 = np.ascontiguousarray(X, dtype=np.float32)
-    if not np.isfinite(X32).all():
-        raise ValueError(f"{who}: X contains NaN, infinity or a value too large for float32")
-    return X32
+    return _tree_host.training_matrix32(X, who, MAX_ROWS, MAX_FEATURES, "BBBP_GBT_FIT_MAX")
 
 
 def _prior_logit(t):
     """scikit-learn's initial raw score for ``init=None``: the logit of the positive class's share, clipped to [eps32, 1 - eps32]."""
     from scipy.special import logit
     return float(logit(np.clip(np.float64(np.mean(t)), EPS32, 1.0 - EPS32)))
-
-
-class _Matrix:
-    """One training matrix on the device: float32 by columns, and every column's rows sorted stably by value (``torch.sort``: done once
-    per matrix, outside the hot path)."""
-
-    def __init__(self, X32, device):
-        X32 = X32 if isinstance(X32, torch.Tensor) else torch.from_numpy(X32)
-        self.XT = X32.to(device).t().contiguous()
-        self.order0 = torch.sort(self.XT, dim=1, stable=True).indices.to(torch.int32).contiguous()
-        self.d, self.n = self.XT.shape
 
 
 class _Chain:
@@ -157,12 +116,10 @@ class _Chain:
                                "(a defect of csrc/gbt.hip, not of the data); no model is returned")
         root = np.concatenate([[0], np.cumsum(counts)])
         keep = (np.arange(self.cap)[None, :] < counts[:, None]).ravel()
-        offs = np.repeat(root[:-1], counts)
         pick = lambda a: a.cpu().numpy()[keep]  # noqa: E731
-        left, right = pick(self.left).astype(np.int64), pick(self.right).astype(np.int64)
-        return dict(left=np.where(left >= 0, left + offs, -1).astype(np.int32), right=np.where(right >= 0, right + offs, -1).astype(np.int32),
-                    feature=pick(self.feature), threshold=pick(self.threshold), value=pick(self.value), n_node_samples=pick(self.nns),
-                    root=root.astype(np.int32))
+        left, right = _tree_host.rebase_children(pick(self.left), pick(self.right), np.repeat(root[:-1], counts))
+        return dict(left=left, right=right, feature=pick(self.feature), threshold=pick(self.threshold), value=pick(self.value),
+                    n_node_samples=pick(self.nns), root=root.astype(np.int32))
 
 
 def _fit_chains(chains, entry="bbbp_gbt_fit"):
@@ -170,31 +127,15 @@ def _fit_chains(chains, entry="bbbp_gbt_fit"):
     the device once, nothing is read back here."""
     dev = chains[0].work.device
     arr = (_lib.GbtChain * len(chains))(*[c.desc for c in chains])
-    on_device = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    on_device = _tree_host.upload(arr, dev)
     _lib.check(getattr(_lib.lib(), entry)(_dense.stream(), arr, on_device.data_ptr(), len(chains)), entry)
     return on_device                                   # kept alive by the caller until the results are read
 
 
-def _check_trees(trees, n_features):
-    """Host-side validation of tree arrays handed to the decision kernel: every index it follows stays inside its arrays."""
-    left, right, feature, root = trees["left"], trees["right"], trees["feature"], trees["root"]
-    n_nodes = len(left)
-    if not (len(right) == len(feature) == len(trees["threshold"]) == len(trees["value"]) == n_nodes) or root[-1] != n_nodes or root[0] != 0:
-        raise ValueError("gradient_boosting: tree arrays of unequal length")
-    if np.any(np.diff(root) < 1):
-        raise ValueError("gradient_boosting: an empty tree")
-    split = left >= 0
-    if np.any(left[split] >= n_nodes) or np.any(right[split] < 0) or np.any(right[split] >= n_nodes) or np.any(feature < 0) or np.any(feature >= n_features):
-        raise ValueError("gradient_boosting: a child or feature index outside its array")
-
-
 def _sklearn_trees(fitted):
     """A fitted scikit-learn booster's trees (one column of ``estimators_``) as the flat host arrays of ``trees_``, and its feature count."""
-    shim = types.SimpleNamespace(estimators_=list(fitted.estimators_[:, 0]), n_features_in_=fitted.n_features_in_, n_outputs_=1)
-    left, right, feature, threshold, value, root, d = ForestGPU.flatten_sklearn(shim)
-    nns = np.concatenate([e.tree_.n_node_samples for e in shim.estimators_])
-    return dict(left=left.astype(np.int32), right=right.astype(np.int32), feature=feature.astype(np.int32), threshold=threshold, value=value,
-                n_node_samples=nns.astype(np.int32), root=root.astype(np.int32)), d
+    trees, (value,) = _tree_host.sklearn_trees(fitted.estimators_[:, 0])
+    return {**trees, "value": value}, int(fitted.n_features_in_)
 
 
 class _BoostedTrees:
@@ -202,29 +143,14 @@ class _BoostedTrees:
     scores of ``bbbp_gbt_staged_decision``.  ``self.device`` is anything ``torch.device`` takes."""
 
     def _set_trees(self, trees, init, learning_rate, n_features):
-        _check_trees(trees, n_features)
-        dev = torch.device(self.device)
+        _tree_host.check_trees(trees, n_features, "gradient_boosting", ("right", "feature", "threshold", "value"))
         self.trees_, self.init_, self.n_features_in_ = trees, float(init), int(n_features)
         self.n_estimators_ = len(trees["root"]) - 1
         self._lr = float(learning_rate)
-        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
-        self._dev = {k: to(trees[k], np.float64 if k in ("threshold", "value") else np.int32) for k in ("left", "right", "feature", "threshold", "value", "root")}
+        self._dev = _tree_host.to_device(trees, ("left", "right", "feature", "threshold", "value", "root"), ("threshold", "value"), torch.device(self.device))
 
     def _queries(self, X):
-        if not hasattr(self, "_dev"):
-            raise RuntimeError("gradient_boosting: not fitted")
-        was_numpy = not isinstance(X, torch.Tensor)
-        if was_numpy:
-            X = np.asarray(X)
-            if X.ndim != 2:
-                raise ValueError(f"gradient_boosting: expected a 2-D [m, d] input, got shape {X.shape}")
-            with np.errstate(over="ignore"):
-                X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
-        elif not X.is_cuda:
-            raise RuntimeError(f"gradient_boosting: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
-        if X.dim() != 2 or X.shape[1] != self.n_features_in_:
-            raise ValueError(f"gradient_boosting: the queries must be [m, {self.n_features_in_}], got shape {tuple(X.shape)}")
-        return X.to(torch.device(self.device), torch.float32).contiguous(), was_numpy
+        return _tree_host.query_matrix(self, X, torch.device(self.device), "gradient_boosting")
 
     def _staged(self, Xq, stages):
         """Raw scores [len(stages), m] after ``stages`` trees each (ascending, within 1..n_estimators_)."""
@@ -256,11 +182,7 @@ class GradientBoostingClassifier(_BoostedTrees):
 
     def __init__(self, n_estimators=100, learning_rate=0.1, max_depth=3, min_samples_split=2, min_samples_leaf=1, *, device="cuda", random_state=None,
                  verbose=0, **other):
-        for name, value in other.items():
-            if name not in _SKLEARN_DEFAULTS:
-                raise ValueError(f"GradientBoostingClassifier: unknown parameter {name}")
-            if value is not _SKLEARN_DEFAULTS[name] and not (isinstance(value, (numbers.Real, str)) and value == _SKLEARN_DEFAULTS[name]):
-                raise NotImplementedError(f"GradientBoostingClassifier: {name}={value!r} is not supported (only {_SKLEARN_DEFAULTS[name]!r})")
+        _tree_host.refuse_non_defaults("GradientBoostingClassifier", other, _SKLEARN_DEFAULTS)
         _check_params(n_estimators, learning_rate, max_depth, min_samples_split, min_samples_leaf)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -364,21 +286,8 @@ class GradientBoostingClassifier(_BoostedTrees):
 def grid_points(param_grid, who="gradient_boosting.grid_search_cv"):
     """The grid's points in scikit-learn's order (sorted keys, ``itertools.product``; a list of grids one after the other) and each point's
     full parameter tuple (n_estimators, learning_rate, max_depth, min_samples_split, min_samples_leaf), checked."""
-    from itertools import product
-    points = []
-    for sub in ([param_grid] if isinstance(param_grid, dict) else list(param_grid)):
-        unknown = set(sub) - set(GRID_KEYS)
-        if unknown:
-            raise ValueError(f"{who}: unsupported grid keys {sorted(unknown)}")
-        keys = sorted(sub)
-        points += [dict(zip(keys, vals)) for vals in product(*(sub[k] for k in keys))]
-    if not points:
-        raise ValueError(f"{who}: the grid is empty")
     defaults = dict(n_estimators=100, learning_rate=0.1, max_depth=3, min_samples_split=2, min_samples_leaf=1)
-    full = [tuple({**defaults, **pt}[k] for k in GRID_KEYS) for pt in points]
-    for params in full:
-        _check_params(*params, who=who)
-    return points, full
+    return _tree_host.grid_points(param_grid, GRID_KEYS, defaults, _check_params, who)
 
 
 def _cv_chains(X32, t_all, folds, full, dev):
@@ -452,19 +361,7 @@ MAX_TARGET_SPREAD = 1e140
 
 def _regression_targets(y, n_rows, who):
     """The targets as finite float64 [n] on the host, unrounded, and their mean (scikit-learn's ``DummyRegressor`` constant, ``np.average``)."""
-    y = np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y)
-    if y.ndim == 2 and y.shape[1] == 1:
-        y = y[:, 0]
-    if y.ndim != 1:
-        raise NotImplementedError(f"{who}: more than one output column is not supported, got y of shape {y.shape}")
-    try:
-        y = np.ascontiguousarray(y, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: y must be numeric, got dtype {y.dtype}") from None
-    if len(y) != n_rows:
-        raise ValueError(f"{who}: X has {n_rows} rows, y has {len(y)}")
-    if not np.isfinite(y).all():
-        raise ValueError(f"{who}: y contains NaN or infinity")
+    y = _tree_host.targets_1d(y, n_rows, who, "more than one output column is not supported")
     with np.errstate(over="ignore", invalid="ignore"):
         init = float(np.average(y))
         spread = float(np.abs(y - init).max())
@@ -505,13 +402,7 @@ class GradientBoostingRegressor(_BoostedTrees):
         who = self._who
         if loss != "squared_error":
             raise NotImplementedError(f"{who}: loss={loss!r} is not supported (only 'squared_error')")
-        for name, value in other.items():
-            if name in _REGRESSOR_IGNORED:
-                continue
-            if name not in _REGRESSOR_DEFAULTS:
-                raise ValueError(f"{who}: unknown parameter {name}")
-            if value is not _REGRESSOR_DEFAULTS[name] and not (isinstance(value, (numbers.Real, str)) and value == _REGRESSOR_DEFAULTS[name]):
-                raise NotImplementedError(f"{who}: {name}={value!r} is not supported (only {_REGRESSOR_DEFAULTS[name]!r})")
+        _tree_host.refuse_non_defaults(who, other, _REGRESSOR_DEFAULTS, _REGRESSOR_IGNORED)
         _check_params(n_estimators, learning_rate, max_depth, min_samples_split, min_samples_leaf, who)
         if torch.device(device).type != "cuda":
             raise RuntimeError(f"{who}: device {device!r}: trees are fitted on the GPU (no CPU fallback)")

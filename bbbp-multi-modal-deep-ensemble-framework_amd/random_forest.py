@@ -7,7 +7,7 @@ The classification stack of the reference (``Models/model_opt_maccs.py:124-200``
 ``DecisionTreeClassifier``, the one-tree case without bootstrap and with all features.  The entry points of ``csrc/rf.hip`` carry both:
 
 * a training matrix is cast to float32 (scikit-learn's trees compare float32 features), transposed and every column's rows are sorted
-  stably once (``gradient_boosting._Matrix``); all trees over that matrix share both;
+  stably once (``_tree_host.Matrix``); all trees over that matrix share both;
 * ``bbbp_rf_fit`` grows any number of trees side by side, one level per round of six launches; the host reads one word per eight levels;
 * ``bbbp_rf_predict_proba`` walks query rows through the trees in tree order with scikit-learn's forest arithmetic, optionally stopping
   at limits ``(n_trees, max_depth, min_samples_split)``.
@@ -38,16 +38,17 @@ dyadic grid 49 bits below the binade of ``max |y|`` so that a node's sums are ex
 proxy ``S_L^2 / W_L + S_R^2 / W_R`` on those sums in seven float64 roundings, and ``tests/rfr_numpy.py`` reproduces a fit bit for bit.
 ``fit_regressors`` grows the forests of many ``(X, y)`` problems, the folds and the stacker's refits, in one batch;
 ``bbbp_rf_predict_mean`` predicts.  The regressors' docstring lists what they refuse.
+
+The training matrix (``Matrix``), the input checks, the flattening of scikit-learn's trees and the small uploads are shared with
+``gradient_boosting`` and live in ``_tree_host.py``; the kernels' shared device code is ``csrc/tree_fit.h``.
 """
 from __future__ import annotations
-
-import numbers
 
 import numpy as np
 import torch
 
-from . import _dense, _lib
-from .gradient_boosting import _Matrix, _is_int
+from . import _dense, _lib, _tree_host
+from ._tree_host import Matrix as _Matrix, is_int as _is_int          # shared with gradient_boosting: they live in _tree_host.py
 from .linear_model import _binary_targets
 
 MAX_ROWS, MAX_FEATURES = 8192, 1024                # BBBP_RF_FIT_MAX_N, BBBP_RF_FIT_MAX_D
@@ -95,37 +96,8 @@ def _check_params(n_estimators, max_depth, min_samples_split, min_samples_leaf, 
         raise ValueError(f"{who}: max_features must be >= 1, got {max_features!r}")
 
 
-def _check_shape(n, d, who):
-    if n < 2 or d < 1:
-        raise ValueError(f"{who}: need at least two rows and one feature, got shape {(n, d)}")
-    if n > MAX_ROWS:
-        raise ValueError(f"{who}: n = {n} rows, at most {MAX_ROWS} are supported (BBBP_RF_FIT_MAX_N)")
-    if d > MAX_FEATURES:
-        raise ValueError(f"{who}: d = {d} features, at most {MAX_FEATURES} are supported (BBBP_RF_FIT_MAX_D)")
-
-
 def _training_matrix32(X, who):
-    """X as float32 [n, d], numpy (host) or a CUDA tensor, checked for shape and finiteness (``gradient_boosting._training_matrix32`` with
-    this module's limits in the messages)."""
-    if isinstance(X, torch.Tensor):
-        if not X.is_cuda:
-            raise RuntimeError(f"{who}: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
-        if X.dim() != 2:
-            raise ValueError(f"{who}: expected a 2-D [n, d] input, got shape {tuple(X.shape)}")
-        _check_shape(X.shape[0], X.shape[1], who)
-        X32 = X.to(torch.float32)
-        if not bool(torch.isfinite(X32).all()):
-            raise ValueError(f"{who}: X contains NaN, infinity or a value too large for float32")
-        return X32
-    X = np.asarray(X)
-    if X.ndim != 2:
-        raise ValueError(f"{who}: expected a 2-D [n, d] input, got shape {X.shape}")
-    _check_shape(X.shape[0], X.shape[1], who)
-    with np.errstate(over="ignore"):
-        X32 = np.ascontiguousarray(X, dtype=np.float32)
-    if not np.isfinite(X32).all():
-        raise ValueError(f"{who}: X contains NaN, infinity or a value too large for float32")
-    return X32
+    return _tree_host.training_matrix32(X, who, MAX_ROWS, MAX_FEATURES, "BBBP_RF_FIT_MAX")
 
 
 class _Spec:
@@ -182,7 +154,7 @@ def _grow(specs, budget=None):
                                      feature.data_ptr() + 4 * b * cap, nns.data_ptr() + 4 * b * cap, threshold.data_ptr() + 8 * b * cap,
                                      value.data_ptr() + 8 * b * cap, value0.data_ptr() + 8 * b * cap, n_nodes.data_ptr() + 4 * b))
         arr = (_lib.RfTree * B)(*descs)
-        on_device = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+        on_device = _tree_host.upload(arr, dev)
         _lib.check(getattr(L, fit_name)(_dense.stream(), arr, on_device.data_ptr(), B, alive.data_ptr()), fit_name)
         _GROWN["trees"] += B
         counts_d = n_nodes.to(torch.int64)
@@ -200,11 +172,10 @@ def _grow(specs, budget=None):
     for si, s in enumerate(specs):
         counts = np.array([len(p[0]) for p in parts[si]], dtype=np.int64)
         root = np.concatenate([[0], np.cumsum(counts)])
-        offs = np.repeat(root[:-1], counts)
         cat = lambda i: np.concatenate([p[i] for p in parts[si]])  # noqa: E731
-        l, r = cat(0).astype(np.int64), cat(1).astype(np.int64)
-        s.trees = dict(left=np.where(l >= 0, l + offs, -1).astype(np.int32), right=np.where(r >= 0, r + offs, -1).astype(np.int32), feature=cat(2),
-                       threshold=cat(4), value=cat(5), n_node_samples=cat(3), root=root.astype(np.int32), value0=cat(6))
+        left, right = _tree_host.rebase_children(cat(0), cat(1), np.repeat(root[:-1], counts))
+        s.trees = dict(left=left, right=right, feature=cat(2), threshold=cat(4), value=cat(5), n_node_samples=cat(3), root=root.astype(np.int32),
+                       value0=cat(6))
 
 
 def _prune(trees, n_trees, max_depth, min_samples_split):
@@ -241,35 +212,25 @@ def _prune(trees, n_trees, max_depth, min_samples_split):
     return res
 
 
+def _limited(spec, limits, who):
+    """A grown forest's trees, or with ``limits = (n_estimators, max_depth, min_samples_split)`` their view under those limits, pruned and
+    renumbered: what a single fit with those parameters gives."""
+    if limits is None:
+        return spec.trees
+    T, depth, mss = limits
+    if T > spec.T or mss < spec.mss or (UNLIMITED if depth is None else depth) > spec.max_depth:
+        raise ValueError(f"{who}: limits {limits} ask for more than the forest was grown with")
+    return _prune(spec.trees, int(T), depth, int(mss))
+
+
 def _check_trees(trees, n_features):
-    """Host-side validation of tree arrays handed to the predict kernel: every index it follows stays inside its arrays."""
-    left, right, feature, root = trees["left"], trees["right"], trees["feature"], trees["root"]
-    n_nodes = len(left)
-    if not all(len(trees[k]) == n_nodes for k in ("right", "feature", "threshold", "value", "n_node_samples")) or root[-1] != n_nodes or root[0] != 0:
-        raise ValueError("random_forest: tree arrays of unequal length")
-    if np.any(np.diff(root) < 1):
-        raise ValueError("random_forest: an empty tree")
-    split = left >= 0
-    if np.any(left[split] >= n_nodes) or np.any(right[split] < 0) or np.any(right[split] >= n_nodes) or np.any(feature < 0) or np.any(feature >= n_features):
-        raise ValueError("random_forest: a child or feature index outside its array")
+    _tree_host.check_trees(trees, n_features, "random_forest", ("right", "feature", "threshold", "value", "n_node_samples"))
 
 
-def _query_matrix(model, X, device):
-    """The queries of a fitted classifier or regressor as float32 [m, d] on ``device``, and whether they came as numpy."""
-    if not hasattr(model, "_dev"):
-        raise RuntimeError("random_forest: not fitted")
-    was_numpy = not isinstance(X, torch.Tensor)
-    if was_numpy:
-        X = np.asarray(X)
-        if X.ndim != 2:
-            raise ValueError(f"random_forest: expected a 2-D [m, d] input, got shape {X.shape}")
-        with np.errstate(over="ignore"):
-            X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
-    elif not X.is_cuda:
-        raise RuntimeError(f"random_forest: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
-    if X.dim() != 2 or X.shape[1] != model.n_features_in_:
-        raise ValueError(f"random_forest: the queries must be [m, {model.n_features_in_}], got shape {tuple(X.shape)}")
-    return X.to(device, torch.float32).contiguous(), was_numpy
+def _flat_sklearn(fitted, value_columns, who):
+    """A fitted scikit-learn forest's or single tree's trees as flat trees without ``value``, the values asked for, and the number of trees."""
+    ests = list(fitted.estimators_) if hasattr(fitted, "estimators_") else [fitted]
+    return _tree_host.sklearn_trees(ests, value_columns, who + ": ") + (len(ests),)
 
 
 class RandomForestClassifier:
@@ -288,11 +249,7 @@ class RandomForestClassifier:
     def __init__(self, n_estimators=100, *, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features="sqrt", bootstrap=True,
                  random_state=0, device="cuda", **other):
         who = self._who
-        for name, value in other.items():
-            if name not in _SKLEARN_DEFAULTS:
-                raise ValueError(f"{who}: unknown parameter {name}")
-            if value is not _SKLEARN_DEFAULTS[name] and not (isinstance(value, (numbers.Real, str)) and value == _SKLEARN_DEFAULTS[name]):
-                raise NotImplementedError(f"{who}: {name}={value!r} is not supported (only {_SKLEARN_DEFAULTS[name]!r})")
+        _tree_host.refuse_non_defaults(who, other, _SKLEARN_DEFAULTS)
         _check_params(n_estimators, max_depth, min_samples_split, min_samples_leaf, max_features, who)
         if not _is_int(random_state):
             raise ValueError(f"{who}: random_state must be an int (the seed is part of the model), got {random_state!r}")
@@ -324,21 +281,15 @@ class RandomForestClassifier:
     def _adopt(self, classes, spec, limits=None):
         """Fitted attributes from a grown forest.  ``limits = (n_estimators, max_depth, min_samples_split)`` materialises the view of the
         forest under those limits, pruned and renumbered: the model a single fit with those parameters gives."""
-        trees = spec.trees
-        if limits is not None:
-            T, depth, mss = limits
-            if T > spec.T or mss < spec.mss or (UNLIMITED if depth is None else depth) > spec.max_depth:
-                raise ValueError(f"{self._who}: limits {limits} ask for more than the forest was grown with")
-            trees = _prune(trees, int(T), depth, int(mss))
+        trees = _limited(spec, limits, self._who)
         self._set_model(classes, {k: trees[k] for k in _TREE_KEYS}, trees["value0"], trees["value"], spec.mat.d)
 
     def _set_model(self, classes, trees, p0, p1, n_features):
         _check_trees(trees, n_features)
         self.classes_, self.trees_, self.n_features_in_ = classes, trees, int(n_features)
         self.n_estimators_ = len(trees["root"]) - 1
-        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)  # noqa: E731
-        self._dev = {k: to(trees[k], np.float64 if k == "threshold" else np.int32) for k in ("left", "right", "feature", "threshold", "n_node_samples", "root")}
-        self._dev["p0"], self._dev["p1"] = to(p0, np.float64), to(p1, np.float64)
+        self._dev = _tree_host.to_device({**trees, "p0": p0, "p1": p1}, ("left", "right", "feature", "threshold", "n_node_samples", "root", "p0", "p1"),
+                                         ("threshold", "p0", "p1"), self.device)
 
     @classmethod
     def from_sklearn(cls, fitted, device="cuda"):
@@ -347,37 +298,23 @@ class RandomForestClassifier:
         who = f"{cls.__name__}.from_sklearn"
         if getattr(fitted, "n_outputs_", 1) != 1 or np.ndim(getattr(fitted, "n_classes_", 0)) != 0 or int(fitted.n_classes_) != 2:
             raise ValueError(f"{who}: exactly two classes and one output are supported")
-        ests = list(fitted.estimators_) if hasattr(fitted, "estimators_") else [fitted]
-        left, right, feature, threshold, p0, p1, nns, root = [], [], [], [], [], [], [], [0]
-        for est in ests:
-            t, off = est.tree_, root[-1]
-            cl, cr = t.children_left.astype(np.int64), t.children_right.astype(np.int64)
-            left.append(np.where(cl >= 0, cl + off, -1)); right.append(np.where(cr >= 0, cr + off, -1))
-            feature.append(np.where(t.feature >= 0, t.feature, 0)); threshold.append(t.threshold)
-            p0.append(t.value[:, 0, 0]); p1.append(t.value[:, 0, 1]); nns.append(t.n_node_samples)
-            root.append(off + t.node_count)
-        if root[-1] >= 2 ** 31:
-            raise ValueError(f"{who}: forest too large for 32-bit node indices")
-        cat = np.concatenate
-        trees = dict(left=cat(left).astype(np.int32), right=cat(right).astype(np.int32), feature=cat(feature).astype(np.int32),
-                     threshold=cat(threshold).astype(np.float64), value=cat(p1).astype(np.float64), n_node_samples=cat(nns).astype(np.int32),
-                     root=np.asarray(root, dtype=np.int32))
+        trees, (p0, p1), n_trees = _flat_sklearn(fitted, (0, 1), who)
         self = cls.__new__(cls)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError(f"{who}: device {device!r}: prediction runs on the GPU (no CPU fallback)")
         # the fitting parameters are kept only where this class would accept them: an adopted model predicts, it is not refitted
-        self.n_estimators = len(ests)
+        self.n_estimators = n_trees
         for name in ("max_depth", "min_samples_split", "min_samples_leaf", "max_features"):
             v = getattr(fitted, name, None)
             setattr(self, name, v if (_is_int(v) or (name == "max_features" and isinstance(v, str))) else None)
         self.bootstrap, self.random_state = bool(getattr(fitted, "bootstrap", False)), None
-        self._set_model(np.asarray(fitted.classes_), trees, cat(p0).astype(np.float64), trees["value"], int(fitted.n_features_in_))
+        self._set_model(np.asarray(fitted.classes_), {**trees, "value": p1}, p0, p1, int(fitted.n_features_in_))
         return self
 
     # ---- prediction -------------------------------------------------------------------------------------------------
     def _queries(self, X):
-        return _query_matrix(self, X, self.device)
+        return _tree_host.query_matrix(self, X, self.device, "random_forest")
 
     def _proba(self, Xq, limits=None):
         """float64 [m, 2] on the device; ``limits = (n_estimators, max_depth, min_samples_split)`` stops every walk as a fit under them would."""
@@ -433,21 +370,8 @@ class DecisionTreeClassifier(RandomForestClassifier):
 def grid_points(param_grid, who="random_forest.grid_search_cv"):
     """The grid's points in scikit-learn's order (sorted keys, ``itertools.product``; a list of grids one after the other) and each point's
     full parameter tuple in ``GRID_KEYS``' order, checked."""
-    from itertools import product
-    points = []
-    for sub in ([param_grid] if isinstance(param_grid, dict) else list(param_grid)):
-        unknown = set(sub) - set(GRID_KEYS)
-        if unknown:
-            raise ValueError(f"{who}: unsupported grid keys {sorted(unknown)}")
-        keys = sorted(sub)
-        points += [dict(zip(keys, vals)) for vals in product(*(sub[k] for k in keys))]
-    if not points:
-        raise ValueError(f"{who}: the grid is empty")
     defaults = dict(n_estimators=100, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features="sqrt")
-    full = [tuple({**defaults, **pt}[k] for k in GRID_KEYS) for pt in points]
-    for params in full:
-        _check_params(*params, who=who)
-    return points, full
+    return _tree_host.grid_points(param_grid, GRID_KEYS, defaults, _check_params, who)
 
 
 def _cv_forests(X32, t_all, folds, full, dev, random_state=0):
@@ -524,19 +448,7 @@ _REGRESSOR_DEFAULTS = dict(criterion="squared_error", max_samples=None, max_leaf
 def _quantise(y, n_rows, who):
     """The targets on their dyadic grid: (q, s) with ``q = rint(y 2^s)`` (integers held in float64, ``|q| <= 2^TARGET_BITS``) and
     ``s = TARGET_BITS - e``, ``(_, e) = frexp(max |y|)``; ``s = 0`` when all of y is 0."""
-    y = np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y)
-    if y.ndim == 2 and y.shape[1] == 1:
-        y = y[:, 0]
-    if y.ndim != 1:
-        raise NotImplementedError(f"{who}: multi-output targets are not supported, got y of shape {y.shape}")
-    try:
-        y = np.ascontiguousarray(y, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: y must be numeric, got dtype {y.dtype}") from None
-    if len(y) != n_rows:
-        raise ValueError(f"{who}: X has {n_rows} rows, y has {len(y)}")
-    if not np.isfinite(y).all():
-        raise ValueError(f"{who}: y contains NaN or infinity")
+    y = _tree_host.targets_1d(y, n_rows, who, "multi-output targets are not supported")
     top = float(np.abs(y).max())
     s = 0 if top == 0.0 else TARGET_BITS - int(np.frexp(top)[1])
     return np.rint(np.ldexp(y, s)), s
@@ -571,11 +483,7 @@ class RandomForestRegressor:
     def __init__(self, n_estimators=100, *, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features=1.0, bootstrap=True,
                  random_state=0, device="cuda", **other):
         who = self._who
-        for name, value in other.items():
-            if name not in _REGRESSOR_DEFAULTS:
-                raise ValueError(f"{who}: unknown parameter {name}")
-            if value is not _REGRESSOR_DEFAULTS[name] and not (isinstance(value, (numbers.Real, str)) and value == _REGRESSOR_DEFAULTS[name]):
-                raise NotImplementedError(f"{who}: {name}={value!r} is not supported (only {_REGRESSOR_DEFAULTS[name]!r})")
+        _tree_host.refuse_non_defaults(who, other, _REGRESSOR_DEFAULTS)
         _check_params(n_estimators, max_depth, min_samples_split, min_samples_leaf, self._all_features(max_features), who)
         if not _is_int(random_state):
             raise ValueError(f"{who}: random_state must be an int (the seed is part of the model), got {random_state!r}")
@@ -629,12 +537,7 @@ class RandomForestRegressor:
 
     def _adopt(self, spec, s, limits=None):
         """Fitted attributes from a grown forest whose values are in units of ``2^-s``; ``limits`` as ``RandomForestClassifier._adopt``."""
-        trees = spec.trees
-        if limits is not None:
-            T, depth, mss = limits
-            if T > spec.T or mss < spec.mss or (UNLIMITED if depth is None else depth) > spec.max_depth:
-                raise ValueError(f"{self._who}: limits {limits} ask for more than the forest was grown with")
-            trees = _prune(trees, int(T), depth, int(mss))
+        trees = _limited(spec, limits, self._who)
         model = {k: trees[k] for k in _TREE_KEYS}
         model["value"] = np.ldexp(trees["value"], -s)          # an exact power of two
         self._set_model(model, spec.mat.d)
@@ -642,10 +545,8 @@ class RandomForestRegressor:
 
     def _set_model(self, trees, n_features):
         _check_trees(trees, n_features)
-        dev = torch.device(self.device)
         self.trees_, self.n_features_in_, self.n_estimators_ = trees, int(n_features), len(trees["root"]) - 1
-        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
-        self._dev = {k: to(trees[k], np.float64 if k in ("threshold", "value") else np.int32) for k in _TREE_KEYS}
+        self._dev = _tree_host.to_device(trees, _TREE_KEYS, ("threshold", "value"), torch.device(self.device))
 
     @classmethod
     def from_sklearn(cls, fitted, device="cuda"):
@@ -656,34 +557,20 @@ class RandomForestRegressor:
             raise ValueError(f"{who}: a fitted regressor with one output is expected")
         if torch.device(device).type != "cuda":
             raise RuntimeError(f"{who}: device {device!r}: prediction runs on the GPU (no CPU fallback)")
-        ests = list(fitted.estimators_) if hasattr(fitted, "estimators_") else [fitted]
-        left, right, feature, threshold, value, nns, root = [], [], [], [], [], [], [0]
-        for est in ests:
-            t, off = est.tree_, root[-1]
-            cl, cr = t.children_left.astype(np.int64), t.children_right.astype(np.int64)
-            left.append(np.where(cl >= 0, cl + off, -1)); right.append(np.where(cr >= 0, cr + off, -1))
-            feature.append(np.where(t.feature >= 0, t.feature, 0)); threshold.append(t.threshold)
-            value.append(t.value[:, 0, 0]); nns.append(t.n_node_samples)
-            root.append(off + t.node_count)
-        if root[-1] >= 2 ** 31:
-            raise ValueError(f"{who}: forest too large for 32-bit node indices")
-        cat = np.concatenate
-        trees = dict(left=cat(left).astype(np.int32), right=cat(right).astype(np.int32), feature=cat(feature).astype(np.int32),
-                     threshold=cat(threshold).astype(np.float64), value=cat(value).astype(np.float64), n_node_samples=cat(nns).astype(np.int32),
-                     root=np.asarray(root, dtype=np.int32))
+        trees, (value,), n_trees = _flat_sklearn(fitted, (0,), who)
         self = cls.__new__(cls)
         # the fitting parameters are kept only where this class would accept them: an adopted model predicts, it is not refitted
-        self.n_estimators, self.device = len(ests), device
+        self.n_estimators, self.device = n_trees, device
         for name in ("max_depth", "min_samples_split", "min_samples_leaf", "max_features"):
             v = getattr(fitted, name, None)
             setattr(self, name, v if (_is_int(v) or (name == "max_features" and (isinstance(v, str) or v == 1.0))) else None)
         self.bootstrap, self.random_state = bool(getattr(fitted, "bootstrap", False)), None
-        self._set_model(trees, int(fitted.n_features_in_))
+        self._set_model({**trees, "value": value}, int(fitted.n_features_in_))
         return self
 
     # ---- prediction -------------------------------------------------------------------------------------------------
     def _queries(self, X):
-        return _query_matrix(self, X, torch.device(self.device))
+        return _tree_host.query_matrix(self, X, torch.device(self.device), "random_forest")
 
     def _mean(self, Xq, limits=None):
         """float64 [m] on the device; ``limits = (n_estimators, max_depth, min_samples_split)`` stops every walk as a fit under them would."""

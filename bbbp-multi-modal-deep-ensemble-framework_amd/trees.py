@@ -6,14 +6,15 @@ learner inside ``StackingRegressor``).  Fitting stays with scikit-learn (CPU, a 
 screening-scale libraries (ZINC) is what needs the GPU: ``ForestGPU.from_sklearn(rf).predict(X)`` reproduces
 ``rf.predict(X)`` (float32 features, float64 thresholds/values, mean over trees in float64).  The XGBoost learner predicts
 through ``boosters.XGBTrees`` (parity unpinned: package absent); CatBoost stays a precomputed input column of
-``ensemble.StackedEnsemble``.
+``ensemble.StackedEnsemble``.  The flattening of scikit-learn's trees is ``_tree_host.sklearn_trees``, shared with the
+learners that fit on the GPU (``random_forest``, ``gradient_boosting``), whose training ``Matrix`` lives there too.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, _tree_host, ops
 
 
 class ForestGPU:
@@ -29,21 +30,12 @@ class ForestGPU:
     @staticmethod
     def flatten_sklearn(forest):
         """Concatenate the trees of a fitted single-output forest: (left, right, feature, threshold, value, root, n_features).
-        Child indices are rebased to the concatenated arrays, -1 marks a leaf, root[t] is the first node of tree t."""
+        Child indices are rebased to the concatenated arrays, -1 marks a leaf, root[t] is the first node of tree t (``_tree_host.sklearn_trees``,
+        the one flattening the tree learners share)."""
         if getattr(forest, "n_outputs_", 1) != 1:
             raise ValueError("single-output regressors only")
-        left, right, feature, threshold, value, root = [], [], [], [], [], [0]
-        for est in forest.estimators_:
-            t, off = est.tree_, root[-1]
-            cl, cr = t.children_left.astype(np.int64), t.children_right.astype(np.int64)
-            left.append(np.where(cl >= 0, cl + off, -1)); right.append(np.where(cr >= 0, cr + off, -1))
-            feature.append(np.where(t.feature >= 0, t.feature, 0)); threshold.append(t.threshold)
-            value.append(t.value.reshape(t.node_count))
-            root.append(off + t.node_count)
-        if root[-1] >= 2 ** 31:
-            raise ValueError("forest too large for 32-bit node indices")
-        return (np.concatenate(left), np.concatenate(right), np.concatenate(feature), np.concatenate(threshold),
-                np.concatenate(value), np.asarray(root), int(forest.n_features_in_))
+        t, (value,) = _tree_host.sklearn_trees(forest.estimators_)
+        return t["left"], t["right"], t["feature"], t["threshold"], value, t["root"], int(forest.n_features_in_)
 
     @classmethod
     def from_sklearn(cls, forest, device="cuda") -> "ForestGPU":

@@ -40,6 +40,8 @@ No constant here was fitted to any implementation's output.
 """
 import numpy as np
 
+import sklearn_trees
+
 U = 2.0 ** -53
 CG = 4.0
 LD = np.longdouble
@@ -224,21 +226,9 @@ def replay(X, y, trees, init, learning_rate, max_depth, min_samples_split=2, min
 def trees_of_sklearn(fitted):
     """A fitted scikit-learn GradientBoostingClassifier's trees in the flat convention, and its initial raw score."""
     from scipy.special import logit
-    left, right, feature, threshold, value, nns, root = [], [], [], [], [], [], [0]
-    for est in fitted.estimators_[:, 0]:
-        t, off = est.tree_, root[-1]
-        left.append(np.where(t.children_left >= 0, t.children_left + off, -1))
-        right.append(np.where(t.children_right >= 0, t.children_right + off, -1))
-        feature.append(np.where(t.feature >= 0, t.feature, 0))
-        threshold.append(t.threshold)
-        value.append(t.value.reshape(t.node_count))
-        nns.append(t.n_node_samples)
-        root.append(off + t.node_count)
     eps32 = np.finfo(np.float32).eps
     init = float(logit(np.clip(np.float64(fitted.init_.class_prior_[1]), eps32, 1 - eps32)))
-    cat = np.concatenate
-    return dict(left=cat(left).astype(np.int32), right=cat(right).astype(np.int32), feature=cat(feature).astype(np.int32), threshold=cat(threshold),
-                value=cat(value), n_node_samples=cat(nns).astype(np.int32), root=np.asarray(root, dtype=np.int32)), init
+    return sklearn_trees.trees_of_sklearn(fitted), init
 
 
 def make_data(n, d, seed=0, decimals=None, informative=None):

@@ -22,6 +22,7 @@ from fractions import Fraction
 import numpy as np
 
 import rf_numpy as N
+from sklearn_trees import trees_of_sklearn  # noqa: F401  (``value`` is the class-1 share of every node)
 
 
 class ReplayError(AssertionError):
@@ -137,21 +138,3 @@ def replay(X, y, trees, *, max_depth=None, min_samples_split=2, min_samples_leaf
         if visited != hi - lo:
             raise ReplayError("stop", f"tree {t}: {hi - lo} nodes stored, {visited} reached from the root")
     return seen
-
-
-def trees_of_sklearn(fitted):
-    """A fitted scikit-learn forest's or tree's trees in the flat convention; ``value`` is the class-1 share of every node."""
-    ests = list(fitted.estimators_) if hasattr(fitted, "estimators_") else [fitted]
-    left, right, feature, threshold, value, nns, root = [], [], [], [], [], [], [0]
-    for est in ests:
-        t, off = est.tree_, root[-1]
-        left.append(np.where(t.children_left >= 0, t.children_left + off, -1))
-        right.append(np.where(t.children_right >= 0, t.children_right + off, -1))
-        feature.append(np.where(t.feature >= 0, t.feature, 0))
-        threshold.append(t.threshold)
-        value.append(t.value[:, 0, 1])
-        nns.append(t.n_node_samples)
-        root.append(off + t.node_count)
-    cat = np.concatenate
-    return dict(left=cat(left).astype(np.int32), right=cat(right).astype(np.int32), feature=cat(feature).astype(np.int32), threshold=cat(threshold),
-                value=cat(value).astype(np.float64), n_node_samples=cat(nns).astype(np.int32), root=np.asarray(root, dtype=np.int32))

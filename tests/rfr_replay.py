@@ -34,6 +34,7 @@ import numpy as np
 
 import rf_numpy as N
 import rfr_numpy as Q
+from sklearn_trees import trees_of_sklearn  # noqa: F401  (``value`` is every node's mean)
 
 U = Fraction(1, 2 ** 53)
 EPSILON = Fraction(2.220446049250313e-16)
@@ -209,24 +210,6 @@ def replay(X, y, trees, *, max_depth=None, min_samples_split=2, min_samples_leaf
         if visited != hi - lo:
             raise ReplayError("stop", f"tree {t}: {hi - lo} nodes stored, {visited} reached from the root")
     return seen
-
-
-def trees_of_sklearn(fitted):
-    """A fitted scikit-learn regression forest's or tree's trees in the flat convention; ``value`` is every node's mean."""
-    ests = list(fitted.estimators_) if hasattr(fitted, "estimators_") else [fitted]
-    left, right, feature, threshold, value, nns, root = [], [], [], [], [], [], [0]
-    for est in ests:
-        t, off = est.tree_, root[-1]
-        left.append(np.where(t.children_left >= 0, t.children_left + off, -1))
-        right.append(np.where(t.children_right >= 0, t.children_right + off, -1))
-        feature.append(np.where(t.feature >= 0, t.feature, 0))
-        threshold.append(t.threshold)
-        value.append(t.value[:, 0, 0])
-        nns.append(t.n_node_samples)
-        root.append(off + t.node_count)
-    cat = np.concatenate
-    return dict(left=cat(left).astype(np.int32), right=cat(right).astype(np.int32), feature=cat(feature).astype(np.int32), threshold=cat(threshold),
-                value=cat(value).astype(np.float64), n_node_samples=cat(nns).astype(np.int32), root=np.asarray(root, dtype=np.int32))
 
 
 def bootstrap_weights_of_sklearn(forest, n):

@@ -155,7 +155,7 @@ def _batch(dev, X, y, param_list):
     """Grow the forests of ``param_list`` (n_trees, max_depth, min_samples_split, min_samples_leaf, max_features, bootstrap, seed) over one
     matrix in one batch: per forest its flat trees."""
     from bbbp_amd import random_forest as F
-    from bbbp_amd.gradient_boosting import _Matrix
+    from bbbp_amd._tree_host import Matrix as _Matrix
     X32 = np.ascontiguousarray(X, dtype=np.float32)
     t = (y == np.unique(y)[1]).astype(np.float64)
     mat = _Matrix(X32, dev)
@@ -181,7 +181,7 @@ def test_determinism_alone_in_a_batch_reversed_and_again(dev):
     assert _same(clf.trees_, {k: alone[k] for k in clf.trees_})
     # a small memory budget splits the same forest into batches of one tree
     from bbbp_amd import random_forest as F
-    from bbbp_amd.gradient_boosting import _Matrix
+    from bbbp_amd._tree_host import Matrix as _Matrix
     mat = _Matrix(np.ascontiguousarray(X, dtype=np.float32), dev)
     spec = F._Spec(mat, torch.from_numpy((y == 1).astype(np.float64)).to(dev), *mine)
     F._grow([spec], budget=1)

@@ -96,7 +96,7 @@ def _batch(dev, X, y, param_list):
     """Grow the regression forests of ``param_list`` (n_trees, max_depth, min_samples_split, min_samples_leaf, max_features, bootstrap, seed)
     over one matrix in one batch: per forest its flat trees, values in grid units."""
     from bbbp_amd import random_forest as F
-    from bbbp_amd.gradient_boosting import _Matrix
+    from bbbp_amd._tree_host import Matrix as _Matrix
     mat = _Matrix(np.ascontiguousarray(X, dtype=np.float32), dev)
     q, _ = F._quantise(y, len(y), "test")
     t_d = torch.from_numpy(q).to(dev)
