@@ -138,6 +138,12 @@ _SIGNATURES = {
     "bbbp_set_fused_encoder": (c_int, [c_int]),
     "bbbp_set_fold_outproj": (c_int, [c_int]),
     "bbbp_set_flash_attention": (c_int, [c_int]),
+    "bbbp_attention_supported": (c_int, [c_int, c_int, c_int]),
+    "bbbp_attention_keep_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "bbbp_attention_fwd": (c_int, [c_void_p, _FP, _FP, _FP, c_int, c_int, c_int, c_float, c_float, c_uint64, c_void_p]),
+    "bbbp_attention_bwd": (c_int, [c_void_p, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_float, c_float, c_uint64, c_void_p]),
+    "bbbp_attention_b3_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "bbbp_attention_b3_fwd": (c_int, [c_void_p, _FP, _FP, c_int, c_int, c_int, c_float, c_void_p, c_size_t]),
     "bbbp_set_gemm_split_bf16": (c_int, [c_int]),
     "bbbp_set_gemm_fold_reduce": (c_int, [c_int]),
     "bbbp_gemm_split_bf16_phases": (c_int, [POINTER(c_uint64)]),

@@ -15,6 +15,7 @@
 //             operand.  No atomics: every output element has one owner, results are bit-reproducible.
 #include "common.h"
 #include "bbbp_hip.h"
+#include "attention_b3.h"
 #include <stdlib.h>
 
 namespace {
@@ -63,8 +64,8 @@ __device__ __forceinline__ void head_to_lds(float* s, int DP, const float* g, in
 
 // S^T tile [16 keys x 16 queries] = X[key rows kbase ..][d] * Y[query rows qbase ..][d]^T over d < 4 * NS (zero-padded rows)
 template <int NS>
-__device__ __forceinline__ f32x4 tile_xyT(const float* X, int kbase, const float* Y, int qbase, int DP, int q, int kq) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+__device__ __forceinline__ f32x4 tile_xyT(const float* X, int kbase, const float* Y, int qbase, int DP, int q, int kq,
+                                          f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f}) {
 #pragma unroll
     for (int s = 0; s < NS; ++s)
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(X[(kbase + q) * DP + 4 * s + kq], Y[(qbase + q) * DP + 4 * s + kq], acc, 0, 0, 0);
@@ -295,8 +296,10 @@ __global__ __launch_bounds__(NTH) void attn_small_bwd1_kernel(AttnParams P) {
 
     // Vector work per pair is what is left to save (the f32 MFMA and the vector ALU share a SIMD's FMA lanes): the softmax scale and
     // log2(e) are folded into the saved logsumexp and one multiply per score (exp2 of a difference), the scale of dS into the K^T / Q^T
-    // operands of dQ^T / dK^T, and ragged tiles need no selects -- a padded key's K row is zero, so its dS reaches dQ^T through a zero
-    // operand and its dV^T / dK^T columns are never stored; a padded query has logsumexp = +inf, i.e. probability 0.
+    // operands of dQ^T / dK^T, and ragged tiles need no selects -- a padded key's dV^T / dK^T columns are never stored, and in the one
+    // ragged tile (the last) its S^T score starts the MFMA chain at -inf instead of 0 (`pen`), i.e. probability 0: its K row is zero, but a
+    // score of 0 would leave exp2(0 - lse) = +inf for a query whose logsumexp is below -88, and inf x (the zero K^T operand) = NaN in every
+    // dQ^T row of that query.  A padded query has logsumexp = +inf, i.e. probability 0.
     const float LOG2E = 1.4426950408889634f;
     const float sc2 = P.scale * LOG2E;
     f32x4 dv[NKT], dk[NKT];                                      // dV^T, dK^T [d = 4 kq + r][key = q] of the wave's key tiles
@@ -308,6 +311,13 @@ __global__ __launch_bounds__(NTH) void attn_small_bwd1_kernel(AttnParams P) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) ak[i][r] = (kt < ntile && q < D) ? P.scale * sK[(kt * 16 + 4 * kq + r) * DP + q] : 0.f;
     }
+    // the ragged tile's initial S^T accumulator: 0 for its real keys (the chain's bits are unchanged), -inf for padded ones.  Every other
+    // tile keeps the chain that starts from the literal 0 behind a wave-uniform branch: one accumulator per tile held across the sweep
+    // (16 more registers) computed the same bits at the same speed alone and cost a training step at F = 2048 1.2 %
+    const int rag_kt = (B & 15) ? ntile - 1 : -1;
+    f32x4 pen;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pen[r] = rag_kt * 16 + 4 * kq + r < B ? 0.f : -INFINITY;
     unsigned kb_next[NKT];
 #pragma unroll
     for (int i = 0; i < NKT; ++i) kb_next[i] = (keep && wave + NW * i < ntile) ? keep[(long)(wave + NW * i) * 64] : 0xfu;
@@ -337,7 +347,9 @@ __global__ __launch_bounds__(NTH) void attn_small_bwd1_kernel(AttnParams P) {
         for (int i = 0; i < NKT; ++i) {
             const int kt = wave + NW * i;
             if (kt < ntile) {                                     // wave-uniform
-                const f32x4 st = tile_xyT<NS>(sK, kt * 16, sQ, qb * 16, DP, q, kq);       // S^T: rows keys
+                f32x4 st;                                                                   // S^T: rows keys
+                if (kt == rag_kt) st = tile_xyT<NS>(sK, kt * 16, sQ, qb * 16, DP, q, kq, pen);
+                else st = tile_xyT<NS>(sK, kt * 16, sQ, qb * 16, DP, q, kq);
                 const f32x4 dpt = tile_xyT<NS>(sV, kt * 16, sdO, qb * 16, DP, q, kq);
                 const f32x4 sn = tile_xyT<NS>(sQ, qb * 16, sK, kt * 16, DP, q, kq);       // S: rows queries
                 const f32x4 dpn = tile_xyT<NS>(sdO, qb * 16, sV, kt * 16, DP, q, kq);
@@ -717,7 +729,8 @@ int set_dyn_lds(K kernel, size_t bytes) {
 
 }  // namespace
 
-// The fused path serves head_dim 8 and 16 whenever one head's K, V, Q, dO fit in LDS (B <= 1024 at head_dim 8).
+// The fused path serves head_dim 8 and 16 whenever one head's K, V, Q, dO and the two-sweep backward's scratch fit in LDS (bwd_lds <= 160 KB:
+// B <= 960 at head_dim 8, B <= 512 at head_dim 16).
 static bool small_supported(int B, int nhead, int head_dim) {
     return nhead > 1 && (head_dim == 8 || head_dim == 16) && B >= 1 && bwd_lds(B, head_dim) <= LDS_MAX;
 }
@@ -778,4 +791,34 @@ int bbbp_attn_small_bwd(hipStream_t st, const float* qkv, const float* ctx, cons
     else { int rc = set_dyn_lds(attn_small_bwd_kernel<4>, lds); if (rc) return rc; hipLaunchKernelGGL(attn_small_bwd_kernel<4>, dim3(nhead, head_parts(nhead, B)), dim3(NTH), lds, st, P); }
     BBBP_CHECK_LAUNCH();
     return BBBP_OK;
+}
+
+// ---- C entry points (include/bbbp_hip.h): the host functions above behind null and shape checks, arguments forwarded unchanged ----
+int bbbp_attention_supported(int B, int nhead, int head_dim) {
+    return (small_supported(B, nhead, head_dim) ? 1 : 0) | (wide_supported(B, nhead, head_dim) ? 2 : 0) |
+           (bbbp_attn_b3_supported(B, nhead, head_dim) ? 4 : 0);
+}
+
+size_t bbbp_attention_keep_bytes(int B, int nhead, int head_dim) { return bbbp_attn_small_keep_bytes(B, nhead, head_dim); }
+
+static int attention_shape_ok(const char* what, int B, int F, int nhead, float p) {
+    BBBP_CHECK_ARG(B >= 1 && F >= 1 && nhead >= 1 && F % nhead == 0, "%s: B=%d F=%d nhead=%d: F must be a positive multiple of nhead", what, B, F, nhead);
+    BBBP_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout_p=%g outside [0, 1)", what, (double)p);
+    const int D = F / nhead;
+    BBBP_CHECK_ARG(small_supported(B, nhead, D) || wide_supported(B, nhead, D), "%s: B=%d nhead=%d head_dim=%d not supported", what, B, nhead, D);
+    return BBBP_OK;
+}
+
+int bbbp_attention_fwd(void* stream, const float* qkv, float* ctx, float* lse, int B, int F, int nhead, float scale, float dropout_p,
+                       uint64_t seed, uint8_t* keep) {
+    if (int rc = attention_shape_ok("attention_fwd", B, F, nhead, dropout_p)) return rc;
+    BBBP_CHECK_ARG(qkv && ctx && lse, "attention_fwd: null pointer");
+    return bbbp_attn_small_fwd(static_cast<hipStream_t>(stream), qkv, ctx, lse, B, F, nhead, scale, dropout_p, seed, keep);
+}
+
+int bbbp_attention_bwd(void* stream, const float* qkv, const float* ctx, const float* lse, const float* dctx, float* dqkv, int B, int F,
+                       int nhead, float scale, float dropout_p, uint64_t seed, const uint8_t* keep) {
+    if (int rc = attention_shape_ok("attention_bwd", B, F, nhead, dropout_p)) return rc;
+    BBBP_CHECK_ARG(qkv && ctx && lse && dctx && dqkv, "attention_bwd: null pointer");
+    return bbbp_attn_small_bwd(static_cast<hipStream_t>(stream), qkv, ctx, lse, dctx, dqkv, B, F, nhead, scale, dropout_p, seed, keep);
 }

@@ -17,6 +17,7 @@
 // 144 MFMAs of 16 cycles per wave and tile (2304 matrix cycles for 32 keys x 16 queries x 192 x 2 products).
 #include "common.h"
 #include "attention_b3.h"
+#include "bbbp_hip.h"
 #include <stdlib.h>
 
 namespace {
@@ -308,4 +309,15 @@ int bbbp_attn_b3_fwd(hipStream_t st, const float* qkv, float* ctx, int B, int F,
         BBBP_CHECK_LAUNCH();
     }
     return BBBP_OK;
+}
+
+// ---- C entry points (include/bbbp_hip.h) ----
+size_t bbbp_attention_b3_workspace_bytes(int B, int nhead, int head_dim) { return bbbp_attn_b3_workspace_bytes(B, nhead, head_dim); }
+
+int bbbp_attention_b3_fwd(void* stream, const float* qkv, float* ctx, int B, int F, int nhead, float scale, float* workspace,
+                          size_t workspace_bytes) {
+    BBBP_CHECK_ARG(B >= 1 && F >= 1 && nhead >= 1 && F % nhead == 0, "attention_b3_fwd: B=%d F=%d nhead=%d: F must be a positive multiple of nhead", B, F,
+                   nhead);
+    BBBP_CHECK_ARG(qkv && ctx, "attention_b3_fwd: null pointer");
+    return bbbp_attn_b3_fwd(static_cast<hipStream_t>(stream), qkv, ctx, B, F, nhead, scale, workspace, workspace_bytes);
 }

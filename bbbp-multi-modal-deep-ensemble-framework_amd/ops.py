@@ -317,6 +317,60 @@ def softmax_bwd(dprob: torch.Tensor, prob: torch.Tensor, dropout_p: float = 0.0,
     return d
 
 
+def _attention_shape(qkv: torch.Tensor, nhead: int, what: str) -> Tuple[int, int, int]:
+    """(B, F, head_dim) of a contiguous qkv [B, 3F] = Q | K | V with F = nhead * head_dim."""
+    _chk(qkv, "qkv")
+    if qkv.dim() != 2 or not qkv.is_contiguous() or nhead < 1 or qkv.shape[0] < 1 or qkv.shape[1] % (3 * nhead) != 0 or qkv.shape[1] == 0:
+        raise RuntimeError(f"{what}: qkv must be a contiguous [B, 3 * nhead * head_dim] tensor, got shape {tuple(qkv.shape)} for nhead={nhead}")
+    B, F = qkv.shape[0], qkv.shape[1] // 3
+    return B, F, F // nhead
+
+
+def attention_fwd(qkv: torch.Tensor, nhead: int, scale: Optional[float] = None, dropout_p: float = 0.0, seed: int = 0,
+                  keep_mask: bool = False):
+    """Fused self-attention over the rows of qkv [B, 3F] (``bbbp_attention_fwd``; small-head or wide-head kernels by shape).  Returns
+    (ctx [B, F], lse [nhead, B], keep): ``keep`` holds the dropout decisions for ``attention_bwd`` when ``keep_mask`` and the shape's
+    kernels save them (``bbbp_attention_keep_bytes`` > 0), else None.  ``scale`` defaults to head_dim ** -0.5."""
+    B, F, D = _attention_shape(qkv, nhead, "attention_fwd")
+    L = _lib.lib()
+    ctx = torch.empty((B, F), device=qkv.device, dtype=torch.float32)
+    lse = torch.empty((nhead, B), device=qkv.device, dtype=torch.float32)
+    kb = L.bbbp_attention_keep_bytes(B, nhead, D) if keep_mask else 0
+    keep = torch.empty(kb, device=qkv.device, dtype=torch.uint8) if kb else None
+    _lib.check(L.bbbp_attention_fwd(_stream(), qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), B, F, nhead,
+                                    D ** -0.5 if scale is None else scale, dropout_p, seed, _p(keep)), "bbbp_attention_fwd")
+    return ctx, lse, keep
+
+
+def attention_bwd(qkv: torch.Tensor, ctx: torch.Tensor, lse: torch.Tensor, dctx: torch.Tensor, nhead: int, scale: Optional[float] = None,
+                  dropout_p: float = 0.0, seed: int = 0, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dqkv [B, 3F] from the forward call's operands and results (``bbbp_attention_bwd``); ``keep``: the forward call's decisions, or None
+    to draw the stream again."""
+    B, F, D = _attention_shape(qkv, nhead, "attention_bwd")
+    for t, n, shape in ((ctx, "ctx", (B, F)), (lse, "lse", (nhead, B)), (dctx, "dctx", (B, F))):
+        if tuple(_chk(t, n).shape) != shape or not t.is_contiguous():
+            raise RuntimeError(f"attention_bwd: {n} must be contiguous and shaped {shape}, got {tuple(t.shape)} strides {t.stride()}")
+    L = _lib.lib()
+    if keep is not None and (_chk(keep, "keep", torch.uint8).numel() != L.bbbp_attention_keep_bytes(B, nhead, D) or not keep.is_contiguous()):
+        raise RuntimeError(f"attention_bwd: keep must hold {L.bbbp_attention_keep_bytes(B, nhead, D)} contiguous bytes, got {keep.numel()}")
+    dqkv = torch.empty((B, 3 * F), device=qkv.device, dtype=torch.float32)
+    _lib.check(L.bbbp_attention_bwd(_stream(), qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), B, F, nhead,
+                                    D ** -0.5 if scale is None else scale, dropout_p, seed, _p(keep)), "bbbp_attention_bwd")
+    return dqkv
+
+
+def attention_b3_fwd(qkv: torch.Tensor, nhead: int, scale: Optional[float] = None) -> torch.Tensor:
+    """Forward-only self-attention of wide heads on the bf16 matrix pipe with split float32 operands (``bbbp_attention_b3_fwd``): ctx [B, F]."""
+    B, F, D = _attention_shape(qkv, nhead, "attention_b3_fwd")
+    L = _lib.lib()
+    ctx = torch.empty((B, F), device=qkv.device, dtype=torch.float32)
+    wsb = L.bbbp_attention_b3_workspace_bytes(B, nhead, D)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=qkv.device)
+    _lib.check(L.bbbp_attention_b3_fwd(_stream(), qkv.data_ptr(), ctx.data_ptr(), B, F, nhead, D ** -0.5 if scale is None else scale,
+                                       ws.data_ptr(), wsb), "bbbp_attention_b3_fwd")
+    return ctx
+
+
 def dropout(x: torch.Tensor, p: float, seed: int) -> torch.Tensor:
     x = _chk(x, "x").contiguous()
     y = torch.empty_like(x)

@@ -719,6 +719,25 @@ int bbbp_set_fold_outproj(int mask);
  * 0 selects the batched GEMM + softmax schedule everywhere.  Returns the previous mask.  Changes the workspace layout: set it
  * before the forward call, not between forward and backward. */
 int bbbp_set_flash_attention(int on);
+/* The attention kernels behind that mask as ops of their own (csrc/attention.hip, csrc/attention_b3.hip; F.scaled_dot_product_attention of
+ * nn.MultiheadAttention, R:75-78, sequence = the batch).  qkv [B][3F] = Q | K | V with head h at columns h * head_dim .. of each third, F = nhead *
+ * head_dim; ctx [B][F]; lse [nhead][B] = logsumexp of the scaled scores; dropout element (h B + q) B + k of stream `seed` (bbbp_set_seed_base
+ * applies).  bbbp_attention_supported: bit 0 the small-head kernels (nhead > 1, head_dim 8 or 16, B <= 960 / 512), bit 1 the wide-head
+ * kernels (nhead <= 8, head_dim 161 .. 176), bit 2 the forward-only split-bf16 kernel (nhead <= 16, head_dim 97 .. 192); bbbp_attention_fwd / _bwd
+ * run bit 0 where it is set, else bit 1, and return BBBP_ERR_ARG for any other shape.  `keep` (nullable, bbbp_attention_keep_bytes; 0 for
+ * shapes of the wide-head kernels, which do not use it): [nhead][ceil(B/16)][ceil(B/16)][64] bytes, bit r of byte (q, kq) = the decision for
+ * key 16 kt + 4 kq + r of query 16 qb + q; written by the forward pass when dropout_p > 0, read by the backward pass instead of drawing the
+ * stream again (NULL there: redrawn, same decisions).  bbbp_attention_b3_fwd: no dropout, no lse; `workspace` of
+ * bbbp_attention_b3_workspace_bytes (0: the key axis is not split, no merge pass). */
+int bbbp_attention_supported(int B, int nhead, int head_dim);
+size_t bbbp_attention_keep_bytes(int B, int nhead, int head_dim);
+int bbbp_attention_fwd(void* stream, const float* qkv, float* ctx, float* lse, int B, int F, int nhead, float scale, float dropout_p,
+                       uint64_t seed, uint8_t* keep);
+int bbbp_attention_bwd(void* stream, const float* qkv, const float* ctx, const float* lse, const float* dctx, float* dqkv, int B, int F,
+                       int nhead, float scale, float dropout_p, uint64_t seed, const uint8_t* keep);
+size_t bbbp_attention_b3_workspace_bytes(int B, int nhead, int head_dim);
+int bbbp_attention_b3_fwd(void* stream, const float* qkv, float* ctx, int B, int F, int nhead, float scale, float* workspace,
+                          size_t workspace_bytes);
 /* Products that take the 128 x 128 tile plan (the F = 2048 encoder's GEMMs, the 65536-wide image FC): 1 (default; initial value
  * BBBP_GEMM_SPLIT_BF16) runs them on the bf16 matrix pipe with every float32 operand split into three bf16 pieces (six MFMAs per
  * k-step, f32 accumulate, float32 accuracy; csrc/gemm.hip: gemm_b3_kernel), 0 on the f32 MFMA.  Returns the previous setting. */
