@@ -195,6 +195,11 @@ _SIGNATURES = {
     "bbbp_rf_fit_regression": (c_int, [c_void_p, POINTER(RfTree), c_void_p, c_int, c_void_p]),
     "bbbp_rf_predict_mean": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int, c_int, c_int, c_void_p]),
+    "bbbp_iforest_tree_capacity": (c_int, [c_int]),
+    "bbbp_iforest_work_bytes": (c_size_t, [c_int]),
+    "bbbp_iforest_fit": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
+    "bbbp_iforest_path_sum": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "bbbp_graph_stats": (c_int, [POINTER(c_long), POINTER(c_long)]),
     "bbbp_conv_last_clock": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "bbbp_set_conv_winograd": (c_int, [c_int]),

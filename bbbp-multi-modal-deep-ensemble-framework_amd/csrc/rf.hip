@@ -55,15 +55,7 @@ constexpr float RF_FEATURE_THRESHOLD = 1e-7f;
 constexpr double RF_MAX_TARGET = 0x1p49;         // |q| of a regression target
 constexpr unsigned long long RF_BOOT = 0xB007ull;          // the stream of a tree's bootstrap draws; features use 2 + f <= 1025, sides 0 and 1
 
-__host__ __device__ inline unsigned long long rf_mix(unsigned long long z) {          // the splitmix64 finaliser
-    z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
-    z ^= z >> 27; z *= 0x94d049bb133111ebull;
-    z ^= z >> 31;
-    return z;
-}
-__host__ __device__ inline unsigned long long rf_hash(unsigned long long a, unsigned long long b) {
-    return rf_mix(rf_mix(a) + 0x9e3779b97f4a7c15ull * (b + 1ull));
-}
+// rf_hash: tree_fit.h (iforest.hip draws from the same hash)
 
 struct TreeState { int level, nk, nk_prev, n_nodes, n_eff, done, active, error; };
 struct Table { int *start, *cnt, *node; unsigned long long* key; };       // the nodes of one level, by slot

@@ -7,10 +7,12 @@
 //   wave_segmented_scan   the inclusive scan inside a wave, restarting where a flag is set; block_segment_prefix: what the waves in front add
 //   encode_score          a non-negative score's bits as an integer that orders like the score, 0 kept for "none"
 //   split_threshold       scikit-learn's threshold between two feature values
+//   rf_hash               the counter-based hash of the forests' random choices (rf.hip, iforest.hip)
 //   make_leaf             the four stores that make a node a leaf
 // The scans take their values, their flags and their addition from the kernel: when a segment starts and what is summed differ per kernel,
 // and the order of every addition is the kernel's (a float64 scan's result depends on it).  The tree walkers, the `choose` kernels and the
-// node tables are per file on purpose: they share a shape, not code.
+// node tables are per file on purpose: they share a shape, not code.  iforest.hip (isolation trees, one work-group per tree, everything in
+// LDS) takes the scans for its segmented minimum / maximum, block_rank_before for its compaction and partition, make_leaf and the hash.
 // Members of a struct that are selected by a run-time index or address go to scratch: layouts here are filled member by member.
 #pragma once
 #include "common.h"
@@ -77,6 +79,17 @@ __device__ inline double split_threshold(float a, float b) {
     double thr = (double)a / 2.0 + (double)b / 2.0;
     if (thr == (double)b) thr = (double)a;
     return thr;
+}
+
+// The counter-based hash behind every random choice of the forests (rf.hip, iforest.hip; exported as bbbp_rf_hash): one value per (key, counter)
+__host__ __device__ inline unsigned long long rf_mix(unsigned long long z) {          // the splitmix64 finaliser
+    z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
+    z ^= z >> 27; z *= 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z;
+}
+__host__ __device__ inline unsigned long long rf_hash(unsigned long long a, unsigned long long b) {
+    return rf_mix(rf_mix(a) + 0x9e3779b97f4a7c15ull * (b + 1ull));
 }
 
 template <class Desc, class Node> __device__ inline void make_leaf(const Desc& c, Node node) {

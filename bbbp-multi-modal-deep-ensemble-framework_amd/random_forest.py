@@ -40,7 +40,8 @@ proxy ``S_L^2 / W_L + S_R^2 / W_R`` on those sums in seven float64 roundings, an
 ``bbbp_rf_predict_mean`` predicts.  The regressors' docstring lists what they refuse.
 
 The training matrix (``Matrix``), the input checks, the flattening of scikit-learn's trees and the small uploads are shared with
-``gradient_boosting`` and live in ``_tree_host.py``; the kernels' shared device code is ``csrc/tree_fit.h``.
+``gradient_boosting`` and live in ``_tree_host.py``; the kernels' shared device code is ``csrc/tree_fit.h``.  ``isolation_forest`` draws
+from the same hash under a key tag of its own.
 """
 from __future__ import annotations
 

@@ -676,6 +676,46 @@ int bbbp_rf_predict_mean(void* stream, const float* X, long ld, int m, int d, co
                          const double* threshold, const double* value, const int* n_node_samples, const int* root, int n_trees,
                          int max_depth, int min_samples_split, double* out);
 
+/* ---- isolation forest: random trees on sub-samples, fitted and walked on the GPU (csrc/iforest.hip) ------------------------------
+ * IsolationForest(contamination=0.05, random_state=42) of the regression stack's preprocessing
+ * (Descriptors/multi_input_data_preprocess_maccs_opt_IsolationForest*.py, create_descriptors_PCA_regression_{1,2,3}.py): the step behind
+ * PCA.  bbbp_amd/isolation_forest.py composes the estimator from these.  The rule is scikit-learn's ExtraTreeRegressor(max_features=1,
+ * splitter="random") as IsolationForest uses it, every random choice one bbbp_rf_hash:
+ *   key(root of tree t) = hash(hash(seed, 0x1F0BE57), t); key(child) = hash(key, side), side 0 left and 1 right;
+ *   the tree's rows: the max_samples rows i of [0, n) with the lowest hash(hash(key(root), 0x5A3B1E), i), kept in ascending order
+ *     (the hash is a bijection of i: no two rows tie);
+ *   a node is a leaf with fewer than 2 rows, at depth max_depth = ceil(log2(max(max_samples, 2))), or when every feature is constant on
+ *     its rows (float32 max <= min + 1e-7f, scikit-learn's FEATURE_THRESHOLD); there is no rule on a target's impurity;
+ *   otherwise its feature is the first in ascending order of hash(key, 2 + f) that is not constant on its rows, and its threshold is
+ *     thr = lo + (hi - lo) * u in float64, lo / hi the feature's float32 minimum / maximum over the rows, u = (hash(key, 0x7412E5) >> 11)
+ *     * 2^-53, the subtraction, the product and the sum each rounded once and none fused; thr >= hi gives thr = lo;
+ *   a row goes left when (double)x <= thr; nodes are numbered level by level from the root 0, the children of a level's split nodes in
+ *     their parents' order, left before right; children are tree-relative, -1 marks a leaf (feature 0, threshold -2 there);
+ *     n_node_samples counts rows.
+ * A tree owns capacity = 2 max_samples - 1 slots of the five node arrays and max_samples entries of `samples`. */
+#define BBBP_IFOREST_MAX_SAMPLES 1024    /* rows of one tree: four row slots per thread of the 256-thread work-group */
+#define BBBP_IFOREST_MAX_D 1024
+#define BBBP_IFOREST_MAX_N 2147483392    /* rows of X: int row indices, whole passes of 256 */
+/* Node slots per tree, 2 max_samples - 1 (0 with a message outside 1..BBBP_IFOREST_MAX_SAMPLES). */
+int bbbp_iforest_tree_capacity(int max_samples);
+/* The fit's work area is its work-group's LDS (row permutation, node segments and node tables of two levels): the caller allocates
+ * nothing but the outputs.  Returns the LDS bytes one work-group takes, 92 max_samples rounded up per array to 16 (0 with a message
+ * outside 1..BBBP_IFOREST_MAX_SAMPLES). */
+size_t bbbp_iforest_work_bytes(int max_samples);
+/* Grow trees 0 .. n_trees - 1 of the forest of `seed` over X [n][d] float32 (row stride ld), all in one launch,
+ * one work-group per tree, without a host read.  left, right, feature, n_node_samples [n_trees][capacity], threshold
+ * [n_trees][capacity], samples [n_trees][max_samples] (the tree's rows, ascending), n_nodes [n_trees]: the tree's node count, -1 when
+ * an index left its array (a defect).  1 <= max_samples <= min(n, BBBP_IFOREST_MAX_SAMPLES), n <= BBBP_IFOREST_MAX_N, d <= BBBP_IFOREST_MAX_D, n_trees <= 65535;
+ * every argument is checked before any GPU call.  A tree's numbers do not depend on what else is in the launch. */
+int bbbp_iforest_fit(void* stream, const float* X, long ld, int n, int d, int max_samples, int n_trees, unsigned long long seed,
+                     int* left, int* right, int* feature, int* n_node_samples, double* threshold, int* samples,
+                     int* n_nodes);
+/* out[q] = sum over the trees, in tree order and in float64, of term[leaf] for query rows X [m][d] float32: bbbp_rf_predict_mean's walk
+ * ((double)x[feature] <= threshold goes left, absolute child indices, root[t] tree t's first node, at most BBBP_RF_MAX_WALK steps, a
+ * longer walk yields NaN) without limits and without the division. */
+int bbbp_iforest_path_sum(void* stream, const float* X, long ld, int m, int d, const int* left, const int* right, const int* feature,
+                          const double* threshold, const double* term, const int* root, int n_trees, double* out);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
