@@ -13,15 +13,17 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbbbp_hip.so")
-SOURCES = ["util.hip", "gemm.hip", "conv.hip", "conv_wino.hip", "conv_b3.hip", "conv_b3c1.hip", "rowops.hip", "engine.hip", "encoder.hip", "fold.hip", "attention.hip", "attention_b3.hip", "preprocess.hip", "mlp.hip", "head.hip", "forest.hip", "pca.hip", "knn.hip", "svm.hip", "svr.hip", "logreg.hip", "gbt.hip", "rf.hip", "iforest.hip"]
+SOURCES = ["util.hip", "gemm.hip", "conv.hip", "conv_wino.hip", "conv_b3.hip", "conv_b3c1.hip", "rowops.hip", "engine.hip", "encoder.hip", "fold.hip", "attention.hip", "attention_b3.hip", "preprocess.hip", "mlp.hip", "head.hip", "forest.hip", "pca.hip", "knn.hip", "svm.hip", "svr.hip", "logreg.hip", "gbt.hip", "rf.hip", "iforest.hip", "bnb.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-source flags.  conv_b3c1.hip: the pooling epilogue takes maxima of accumulator registers; in IEEE mode every such operand first gets a
 # quieting `v_max_f32 x, x, x` (two extra vector instructions per maximum in a kernel whose vector issue slots are the budget).  Without the
 # IEEE bit and with finite-math NaN rules the maxima are single instructions; NaN inputs are outside this path's contract.
 # svr.hip: the solver's results are pinned bit for bit to a numpy restatement, whose products and sums round one by one: no fused multiply-add
-# may be formed from them.  iforest.hip: the same for a split's threshold, lo + (hi - lo) * u (tests/iforest_numpy.py).
-EXTRA_FLAGS = {"conv_b3c1.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"], "svr.hip": ["-ffp-contract=off"], "iforest.hip": ["-ffp-contract=off"]}
+# may be formed from them.  iforest.hip: the same for a split's threshold, lo + (hi - lo) * u (tests/iforest_numpy.py).  bnb.hip: a joint log-likelihood is a chain of float64 additions
+# pinned to tests/bnb_numpy.py; nothing in it is a product today, and the flag keeps a later edit from changing the bits.
+EXTRA_FLAGS = {"conv_b3c1.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"], "svr.hip": ["-ffp-contract=off"], "iforest.hip": ["-ffp-contract=off"],
+               "bnb.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target: str, deps) -> bool:

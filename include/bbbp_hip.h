@@ -716,6 +716,41 @@ int bbbp_iforest_fit(void* stream, const float* X, long ld, int n, int d, int ma
 int bbbp_iforest_path_sum(void* stream, const float* X, long ld, int m, int d, const int* left, const int* right, const int* feature,
                           const double* threshold, const double* term, const int* root, int n_trees, double* out);
 
+/* ---- Bernoulli naive Bayes on bits: batched counting and joint log-likelihoods (csrc/bnb.hip) -----------------------------------------
+ * BernoulliNB() of the classification stack (Models/model_maccs.py:257-267: alpha x binarize under five folds, then a learning curve).
+ * bbbp_amd/naive_bayes.py composes the estimator, fit_masks, grid_search_cv and learning_curve from these; the log tables are formed
+ * on the host from the integer counts, so alpha is no argument here.  Words are 64 bits, bit b of word w stands for index 64 w + b, and
+ * the bits past the last index of a word vector are 0. */
+#define BBBP_BNB_MAX_D 1048576           /* features: the pack grid's second dimension is ceil(d / 64) */
+#define BBBP_BNB_MAX_THRESHOLDS 1024
+#define BBBP_BNB_MAX_PROBLEMS 65535      /* masks, pairs or jll problems of one launch */
+#define BBBP_BNB_MAX_ITEMS 2147483647L   /* counts of one launch: 2 d n_pairs + 2 n_masks */
+/* bit = X[i][j] > thresholds[t] (strict, sklearn.preprocessing.binarize) for X [n][d] float32 or float64 (x_dtype: BBBP_DTYPE_*, unit
+ * inner stride, row stride ld).  For float32 X the threshold is rounded to float32 first, numpy's rule for an array compared with a
+ * Python float.  Two layouts, either may be NULL: planes [T][d][ceil(n/64)] (feature-major: a word holds 64 rows of one feature) and
+ * rowwords [T][n][ceil(d/64)] (row-major: a word holds 64 features of one row).  Every word of both is written whole, padding bits as 0:
+ * nothing has to be cleared beforehand.  *flag (device, 0 on entry) is set to 1 when X holds NaN or infinity; such an entry packs as 0.
+ * thresholds is a device array.  n <= 2^31 - 1, d <= BBBP_BNB_MAX_D, T <= BBBP_BNB_MAX_THRESHOLDS. */
+int bbbp_bnb_pack(void* stream, const void* X, int x_dtype, long ld, int n, int d, const double* thresholds, int n_thresholds,
+                  unsigned long long* planes, unsigned long long* rowwords, int* flag);
+/* Every count of a batch in one launch.  masks [M][2][ceil(n/64)]: a row subset intersected with class 0 and with class 1.  Pair q is
+ * (pair_mask[q], pair_threshold[q]), device arrays of n_pairs ints.
+ *   feature_count[q][c][j] = sum_w popcount(planes[t][j][w] & masks[m][c][w])   int32 [n_pairs][2][d]
+ *   class_count[m][c]      = sum_w popcount(masks[m][c][w])                      int32 [M][2]
+ * Exact integers, one wave per count; a pair that names a mask or a threshold outside the batch yields -1 and reads nothing.
+ * M, n_pairs <= BBBP_BNB_MAX_PROBLEMS and 2 d n_pairs + 2 M <= BBBP_BNB_MAX_ITEMS. */
+int bbbp_bnb_count(void* stream, const unsigned long long* planes, int n, int d, int n_thresholds, const unsigned long long* masks,
+                   int n_masks, const int* pair_mask, const int* pair_threshold, int n_pairs, int* feature_count, int* class_count);
+/* Joint log-likelihoods of a batch in one launch, one lane per (problem, query row).  Problem p has the table w[p][2][d], the constant
+ * c[p][2] and four longs problems[p] = {threshold index, row_begin, n_rows, out_begin}: its query rows are rows[row_begin .. + n_rows)
+ * (indices into [0, n)), or with row_begin < 0 the rows 0 .. n_rows - 1, and its results are out[out_begin .. + n_rows)[2].
+ *   out[.][k] = ((0.0 + w[p][k][j1]) + w[p][k][j2] + ...) + c[p][k],  j1 < j2 < ... the set bits of the row in rowwords[t]
+ * float64 additions, each rounded once, in exactly this order.  rows has n_row_entries ints (may be NULL with 0), out has n_out pairs of
+ * doubles, max_rows is the largest n_rows.  A problem whose threshold index or rows leave their arrays yields NaN.
+ * n_problems <= BBBP_BNB_MAX_PROBLEMS. */
+int bbbp_bnb_jll(void* stream, const unsigned long long* rowwords, int n, int d, int n_thresholds, const double* w, const double* c,
+                 const long* problems, int n_problems, const int* rows, long n_row_entries, int max_rows, long n_out, double* out);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
