@@ -13,7 +13,7 @@ The kept neighbours get their distances recomputed by direct differences: a dupl
 
 Neighbours are ordered by (distance, training index): among equidistant rows the lower index comes first.
 
-Out of scope: SMOTE itself (its random draws cannot be pinned here; ``kneighbors(X=None)`` is its GPU part), tree / ball-tree indices,
+SMOTE, TomekLinks and SMOTETomek are built on this search in ``imbalance``.  Out of scope: tree / ball-tree indices,
 approximate search, metrics other than Euclidean, ``radius_neighbors``, regression, ``n_neighbors > 32``, more than 32 classes, more than
 one GPU.  There is no CPU path.
 """

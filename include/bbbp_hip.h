@@ -751,6 +751,23 @@ int bbbp_bnb_count(void* stream, const unsigned long long* planes, int n, int d,
 int bbbp_bnb_jll(void* stream, const unsigned long long* rowwords, int n, int d, int n_thresholds, const double* w, const double* c,
                  const long* problems, int n_problems, const int* rows, long n_row_entries, int max_rows, long n_out, double* out);
 
+/* ---- resampling of imbalanced classes: SMOTE's synthesis and Tomek links (csrc/smote.hip) ------------------------------------------------
+ * SMOTE(random_state=42) / SMOTETomek(random_state=42) of the classification stack (Models/model_opt_maccs.py, model_opt_20250130.py): the
+ * step between PCA and the learners.  bbbp_amd/imbalance.py composes the estimators from these, bbbp_knn_f64 and the host's
+ * numpy.random.RandomState draws. */
+/* out[j][:] = Xc[r][:] + steps[j] * (Xc[b][:] - Xc[r][:]) for j < n_new, r = idx[j] / k, b = nn[r][idx[j] % k].  Xc [n_c][d] float32 or
+ * float64 (x_dtype: BBBP_DTYPE_*, unit inner stride, row stride ldx, any base alignment), nn [n_c][k] dense, idx [n_new] in [0, n_c k),
+ * steps [n_new] float64, out [n_new][d] of Xc's type with row stride ldo.  Rounding is numpy's for `X[rows] + steps[:, None] * diffs`:
+ * float64 rows: difference, product and sum each rounded once in float64; float32 rows: the difference rounded to float32, product and
+ * sum in float64 on the widened values, the sum rounded once to float32.  Nothing is fused.  An idx or nn entry outside its array yields a
+ * row of NaN and reads nothing.  n_new = 0 or d = 0 is a no-op; otherwise n_c > k. */
+int bbbp_smote_synth(void* stream, const void* Xc, int x_dtype, long ldx, int n_c, const long* nn, const long* idx, const double* steps,
+                     int k, int n_new, int d, void* out, long ldo);
+/* keep[i] = 0 when row i is a member of a Tomek link (y[nn1[i]] != y[i] and nn1[nn1[i]] == i) and remove[y[i]] != 0, else 1, for i < n.
+ * nn1 [n]: the nearest other row of every row; y [n]: labels in [0, n_classes); remove [n_classes] bytes.  Every byte of keep is
+ * written.  An index or a label outside its array is no link. */
+int bbbp_tomek_links(void* stream, const long* nn1, const int* y, const unsigned char* remove, int n_classes, int n, unsigned char* keep);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
