@@ -92,6 +92,17 @@ class SvrProblem(Structure):
                 ("rho", c_void_p), ("n_iter", c_void_p), ("done", c_void_p), ("n", c_int), ("C", c_double), ("epsilon", c_double), ("tol", c_double)]
 
 
+class SvmOofDesc(Structure):
+    """bbbp_svm_oof_desc (include/bbbp_hip.h)."""
+    _fields_ = [("K", c_void_p), ("ldk", c_long), ("n_rows", c_int), ("rows", c_void_p), ("y", c_void_p), ("alpha", c_void_p), ("rho", c_void_p),
+                ("n", c_int), ("held", c_void_p), ("n_held", c_int), ("out", c_void_p)]
+
+
+class SvmPlattProblem(Structure):
+    """bbbp_svm_platt_problem (include/bbbp_hip.h)."""
+    _fields_ = [("dec", c_void_p), ("y", c_void_p), ("n", c_int), ("ab", c_void_p), ("info", c_void_p)]
+
+
 class LogregProblem(Structure):
     """bbbp_logreg_problem (include/bbbp_hip.h)."""
     _fields_ = [("X", c_void_p), ("x_dtype", c_int), ("ld", c_long), ("n", c_int), ("d", c_int), ("t", c_void_p), ("C", c_double), ("tol", c_double),
@@ -174,6 +185,9 @@ _SIGNATURES = {
     "bbbp_svm_decision_workspace_bytes": (c_size_t, [POINTER(SvmDecisionDesc)]),
     "bbbp_svm_decision": (c_int, [c_void_p, POINTER(SvmDecisionDesc), c_void_p, c_size_t]),
     "bbbp_svr_smo": (c_int, [c_void_p, POINTER(SvrProblem), c_int, c_int]),
+    "bbbp_svm_oof_decision": (c_int, [c_void_p, POINTER(SvmOofDesc), c_int]),
+    "bbbp_svm_platt_fit": (c_int, [c_void_p, POINTER(SvmPlattProblem), c_int]),
+    "bbbp_svm_platt_proba": (c_int, [c_void_p, c_void_p, c_long, c_double, c_double, c_void_p]),
     "bbbp_logreg_state_bytes":(c_size_t, [c_int, c_int]),
     "bbbp_logreg_state_layout": (c_int, [c_int, c_int, POINTER(c_long)]),
     "bbbp_logreg_rounds": (c_int, [c_void_p, POINTER(LogregProblem), c_int, c_int]),

@@ -24,7 +24,15 @@ reference's five folds in one batch; ``grid_search_cv_svr``: ``GridSearchCV(SVR(
 Two correct SMO runs of one problem agree to about ``tol``, not to rounding: scikit-learn itself moves by that much between a data set and
 its reversal.  Results here are bit-identical from run to run and do not depend on what else is solved in the same batch.
 
-Out of scope: ``probability=True`` (Platt scaling's internal cross-validation draws from libsvm's own generator), more than two classes,
+``PlattSVC``: ``SVC(probability=True)`` of the reference's classification scripts (``Models/model_opt_maccs.py:128``), whose ROC AUC, stacking
+and soft voting read ``predict_proba``.  libsvm's scheme -- ``cv`` fold problems, their out-of-fold decision values, a sigmoid fitted to
+them, one more fit on all rows -- runs over ONE kernel matrix: the fold problems are row lists into it and stand in one solver batch beside
+the all-rows problem, ``bbbp_svm_oof_decision`` reads the held-out decision values from the resident matrix, ``bbbp_svm_platt_fit`` is
+libsvm's ``sigmoid_train`` in one work-group and ``bbbp_svm_platt_proba`` its ``sigmoid_predict`` (``csrc/svm_proba.hip``).  ``platt_scale``
+is the sigmoid fit on its own.  The folds are libsvm's unstratified slices of a permutation, drawn from numpy's generator where libsvm draws
+from its own: see ``PlattSVC``.
+
+Out of scope: ``probability=True`` as a mode of ``SVC`` (``PlattSVC`` is the class for it), more than two classes,
 ``class_weight``, kernels other than linear and RBF, shrinking (accepted and ignored: the optimum is the same), a kernel matrix larger than
 free device memory, more than one GPU.  There is no CPU path.
 """
@@ -207,7 +215,8 @@ class SVC:
         if unsupported:
             raise ValueError(f"SVC: unsupported parameters {sorted(unsupported)}")
         if probability:
-            raise ValueError("SVC: probability=True is not supported (Platt scaling's internal cross-validation draws from libsvm's own generator)")
+            raise ValueError("SVC: probability=True is not a mode of this class: svm.PlattSVC fits the Platt-scaled probabilities "
+                             "(its folds come from numpy's generator, not from libsvm's own)")
         if class_weight is not None:
             raise ValueError("SVC: class_weight is not supported")
         _check_params(C, kernel, gamma, tol, max_iter)
@@ -345,6 +354,243 @@ def grid_search_cv(X, y, param_grid, cv: int = 5, device="cuda", *, tol=1e-3, ma
     C, kernel, gamma = full[best]
     fitted = SVC(C, kernel, gamma, tol, max_iter, device=dev).fit(X, y)
     return points[best], scores, fitted
+
+
+# ---- Platt-scaled probabilities ----------------------------------------------------------------------------------------------------------
+PLATT_STATUS = {0: "converged", 1: "the line search failed", 2: "stopped at 100 iterations"}      # BBBP_PLATT_*
+
+
+def platt_folds(n, cv, random_state):
+    """libsvm's unstratified folds with numpy's generator: fold i holds out ``perm[i * n // cv : (i + 1) * n // cv]`` of
+    ``perm = RandomState(random_state).permutation(n)``.  A list of ``cv`` index arrays that partition ``range(n)``."""
+    perm = np.random.RandomState(random_state).permutation(n)
+    return [perm[i * n // cv:(i + 1) * n // cv] for i in range(cv)]
+
+
+def _check_folds(folds, n):
+    """``folds`` as a list of int64 held-out index arrays that partition ``range(n)``."""
+    try:
+        held = [np.asarray(f) for f in folds]
+    except TypeError:
+        raise ValueError("PlattSVC: folds must be a list of held-out index arrays") from None
+    if not held or any(f.ndim != 1 or (f.size and f.dtype.kind not in "iu") for f in held):
+        raise ValueError("PlattSVC: folds must be a non-empty list of 1-D integer index arrays")
+    held = [f.astype(np.int64) for f in held]
+    if not np.array_equal(np.sort(np.concatenate(held)), np.arange(n)):
+        raise ValueError(f"PlattSVC: folds must partition range({n}): every row held out exactly once")
+    return held
+
+
+def _platt_fit(decs, ys):
+    """``bbbp_svm_platt_fit`` of the problems (decs[q], ys[q]), float64 device vectors of equal length >= 1: one launch (per 64 problems),
+    one host read.  Returns (ab [P, 2] float64, info [P, 2] int32) as numpy arrays."""
+    dev = decs[0].device
+    ab = torch.empty((len(decs), 2), dtype=torch.float64, device=dev)
+    info = torch.empty((len(decs), 2), dtype=torch.int32, device=dev)
+    _platt_launch(decs, ys, ab, info)
+    return ab.cpu().numpy(), info.cpu().numpy()
+
+
+def _platt_launch(decs, ys, ab, info):
+    """The launch of ``_platt_fit`` alone: problem q writes ab[q] and info[q] (device, [P, 2] float64 / int32)."""
+    arr = (_lib.SvmPlattProblem * len(decs))(*[_lib.SvmPlattProblem(d.data_ptr(), y.data_ptr(), d.numel(), ab.data_ptr() + 16 * q, info.data_ptr() + 8 * q)
+                                              for q, (d, y) in enumerate(zip(decs, ys))])
+    _lib.check(_lib.lib().bbbp_svm_platt_fit(_dense.stream(), arr, len(decs)), "bbbp_svm_platt_fit")
+
+
+def _oof_launch(K, parts, oof):
+    """``bbbp_svm_oof_decision``: for every (solved fold ``_Problem`` over K, its held-out rows as an int32 device vector) of ``parts`` the
+    held-out decision values in libsvm's sign, written to ``oof`` [n] by data row.  One launch (per 32 folds), no host read."""
+    n = K.shape[0]
+    arr = (_lib.SvmOofDesc * len(parts))(*[_lib.SvmOofDesc(K.data_ptr(), K.stride(0), n, pr.rows.data_ptr(), pr.y.data_ptr(), pr.alpha.data_ptr(),
+                                                          pr.rho.data_ptr(), pr.n, te_d.data_ptr(), te_d.numel(), oof.data_ptr())
+                                          for pr, te_d in parts])
+    _lib.check(_lib.lib().bbbp_svm_oof_decision(_dense.stream(), arr, len(parts)), "bbbp_svm_oof_decision")
+
+
+def _platt_problems(K, y_d, ys, held, C, tol, oof):
+    """libsvm's fold problems over the shared matrix: for each non-empty held-out index array of ``held`` either a ``_Problem`` on the other
+    rows (a row list into K) or, where those rows have one class or are none, libsvm's constant written to ``oof`` at once.  Returns the
+    (problem, held-out rows as an int32 device vector) pairs."""
+    n, dev, parts = len(ys), K.device, []
+    for te in held:
+        if len(te) == 0:
+            continue
+        keep = np.ones(n, dtype=bool)
+        keep[te] = False
+        tr = np.flatnonzero(keep)
+        te_d = torch.from_numpy(te).to(dev)
+        ytr = ys[tr]
+        if len(tr) == 0 or (ytr > 0).all() or (ytr < 0).all():
+            oof.index_fill_(0, te_d, 0.0 if len(tr) == 0 else float(ytr[0]))
+            continue
+        tr_d = torch.from_numpy(tr).to(dev)
+        parts.append((_Problem(K, y_d.index_select(0, tr_d), C, tol, tr_d.to(torch.int32)), te_d.to(torch.int32)))
+    return parts
+
+
+def _platt_vector(v, dev, what):
+    if isinstance(v, torch.Tensor):
+        if not v.is_cuda:
+            raise RuntimeError(f"svm.platt_scale: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {v.device} (no CPU fallback)")
+        v = v.detach()
+    else:
+        v = np.asarray(v)
+        if v.dtype.kind not in "fiub":
+            raise ValueError(f"svm.platt_scale: {what} must hold real numbers, got dtype {v.dtype}")
+        v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64))
+    if v.dim() != 1 or v.numel() < 1:
+        raise ValueError(f"svm.platt_scale: {what} must be 1-D with at least one entry, got shape {tuple(v.shape)}")
+    return v.to(device=dev, dtype=torch.float64).contiguous()
+
+
+def platt_scale(dec, y_pm1, device="cuda"):
+    """libsvm's ``sigmoid_train`` on the GPU (``bbbp_svm_platt_fit``): the (A, B) that minimise the cross-entropy of
+    ``1 / (1 + exp(A dec + B))`` against the smoothed targets of the labels ``y_pm1`` (> 0 counts as the positive class), by Newton's
+    method with backtracking as Lin, Lin and Weng state it.  ``dec`` and ``y_pm1`` are numpy arrays or CUDA tensors [n], or two lists of such
+    for a batch that one launch solves, a work-group each; a problem's result does not depend on the batch.  Returns
+    ``(A, B, n_iter, status)``: floats and ints for one problem, numpy arrays [P] for a list; status 0 = both gradient components below
+    1e-5, 1 = the line search failed, 2 = 100 iterations."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"svm.platt_scale: device {device!r}: the fit runs on the GPU (no CPU fallback)")
+    batch = isinstance(dec, (list, tuple)) and len(dec) > 0 and (isinstance(dec[0], torch.Tensor) or np.ndim(dec[0]) >= 1)
+    decs, ys = (list(dec), list(y_pm1)) if batch else ([dec], [y_pm1])
+    if len(decs) != len(ys):
+        raise ValueError(f"svm.platt_scale: {len(decs)} decision vectors, {len(ys)} label vectors")
+    with torch.cuda.device(dev):
+        decs = [_platt_vector(d, dev, "dec") for d in decs]
+        ys = [_platt_vector(y, dev, "y_pm1") for y in ys]
+        for d, y in zip(decs, ys):
+            if d.numel() != y.numel():
+                raise ValueError(f"svm.platt_scale: dec has {d.numel()} entries, y_pm1 has {y.numel()}")
+        if not bool(torch.stack([torch.isfinite(d).all() for d in decs]).all().item()):
+            raise ValueError("svm.platt_scale: dec contains NaN or infinity")
+        ab, info = _platt_fit(decs, ys)
+    if batch:
+        return ab[:, 0].copy(), ab[:, 1].copy(), info[:, 0].copy(), info[:, 1].copy()
+    return float(ab[0, 0]), float(ab[0, 1]), int(info[0, 0]), int(info[0, 1])
+
+
+class PlattSVC(SVC):
+    """``PlattSVC(C=1.0, kernel="rbf", gamma="scale", tol=1e-3, max_iter=-1, *, cv=5, random_state=0, device="cuda")``: scikit-learn's
+    ``SVC(probability=True)`` for two classes.  Everything ``SVC`` has, fitted exactly as ``SVC`` fits it, plus ``predict_proba`` /
+    ``predict_log_proba``, ``probA_`` and ``probB_`` ([1] each, libsvm's sign as scikit-learn stores them), ``platt_n_iter_``,
+    ``platt_status_`` and ``oof_decision_`` ([n] float64 in libsvm's sign: positive towards ``classes_[0]``).
+
+    ``fit(X, y, *, folds=None)`` follows libsvm: ``cv`` folds, each held-out row's decision value from the model trained on the other
+    folds, a sigmoid fitted to those n values (``platt_scale``), and the model itself from all rows.  Here gamma is resolved once from all
+    rows (as scikit-learn does before it calls libsvm), one kernel matrix is formed, and the fold problems -- row lists into it -- are
+    solved in one batch with the all-rows problem.  A fold whose training part has one class gets libsvm's rule: its held-out values are
+    +1 (only ``classes_[0]`` trained on), -1 (only ``classes_[1]``) or 0 (nothing).  ``folds``: a list of held-out index arrays that
+    partition ``range(n)``, in place of the draw.  ``predict`` is the sign of the decision value, as scikit-learn's, and may disagree with
+    the arg-max of ``predict_proba``.  A ``platt_status_`` other than 0 raises a ``ConvergenceWarning``.
+
+    Two differences from scikit-learn:
+
+    * the folds are libsvm's unstratified slices ``perm[i n // cv : (i + 1) n // cv]``, but the permutation is
+      ``numpy.random.RandomState(random_state).permutation(n)``, not a draw from libsvm's own generator.  For one ``random_state``,
+      ``probA_`` / ``probB_`` differ from scikit-learn's about as scikit-learn's own differ between two seeds (n = 200, d = 5, linear,
+      scikit-learn 1.7.2: ``probA_`` from -0.954 to -0.842 over seeds 0 to 7); with the same folds they agree;
+    * ``predict_proba`` is the exact sigmoid, as libsvm >= 3.3 returns for two classes.  scikit-learn's vendored libsvm sends two classes
+      through ``multiclass_probability``, whose iteration stops at 0.005 / k: its values differ from the sigmoid of its own ``probA_`` /
+      ``probB_`` by 2e-3 to 5e-3."""
+
+    _params = ("C", "kernel", "gamma", "tol", "max_iter", "cv", "random_state", "device")
+
+    def __init__(self, C=1.0, kernel="rbf", gamma="scale", tol=1e-3, max_iter=-1, *, cv=5, random_state=0, device="cuda", **unsupported):
+        if unsupported.get("class_weight") is not None:
+            raise ValueError("PlattSVC: class_weight is not supported")
+        unsupported.pop("class_weight", None)
+        if unsupported:
+            raise ValueError(f"PlattSVC: unsupported parameters {sorted(unsupported)}")
+        _check_params(C, kernel, gamma, tol, max_iter, "PlattSVC")
+        if isinstance(cv, bool) or not isinstance(cv, numbers.Integral) or cv < 2:
+            raise ValueError(f"PlattSVC: cv must be an int of at least 2, got {cv!r}")
+        if isinstance(random_state, bool) or not isinstance(random_state, numbers.Integral) or not (0 <= random_state < 2 ** 32):
+            raise ValueError(f"PlattSVC: random_state must be an int in [0, 2^32), got {random_state!r}")
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"PlattSVC: device {device!r}: the solver runs on the GPU (no CPU fallback)")
+        # the values as given (get_params returns them, so that sklearn.base.clone round-trips)
+        self.C, self.kernel, self.gamma, self.tol, self.max_iter = C, kernel, gamma, tol, max_iter
+        self.cv, self.random_state, self.device = cv, random_state, device
+
+    def get_params(self, deep=True):
+        return {name: getattr(self, name) for name in self._params}
+
+    def set_params(self, **params):
+        unknown = set(params) - set(self._params)
+        if unknown:
+            raise ValueError(f"PlattSVC: unknown parameters {sorted(unknown)}")
+        type(self)(**{**self.get_params(), **params})          # the constructor's checks
+        for name, value in params.items():
+            setattr(self, name, value)
+        return self
+
+    # ---- fit --------------------------------------------------------------------------------------------------------
+    def fit(self, X, y, *, folds=None):
+        classes, ys = _binary_labels(y, None, "PlattSVC")
+        n = len(ys)
+        if folds is None:
+            if self.cv > n:
+                raise ValueError(f"PlattSVC: cv={self.cv} folds need at least as many rows, got {n}")
+            held = platt_folds(n, int(self.cv), int(self.random_state))
+        else:
+            held = _check_folds(folds, n)
+        dev = torch.device(self.device)
+        X, _ = _dense.to_device_matrix(X, dev, "svm", allow_row_stride=True)
+        if X.shape[0] != n:
+            raise ValueError(f"PlattSVC: X has {X.shape[0]} rows, y has {n}")
+        C, tol, max_iter = float(self.C), float(self.tol), int(self.max_iter)
+        with torch.cuda.device(dev):
+            g = _resolve_gamma(self.gamma, X)
+            K, mean, norms = kernel_matrix(X, self.kernel, g)
+            y_d = torch.from_numpy(ys).to(dev)
+            oof = torch.empty(n, dtype=torch.float64, device=dev)
+            parts = _platt_problems(K, y_d, ys, held, C, tol, oof)
+            problems = [_Problem(K, y_d, C, tol)] + [pr for pr, _ in parts]      # the all-rows problem and the folds: one batch over one matrix
+            solved = _solve(problems, max_iter)
+            if parts:
+                _oof_launch(K, parts, oof)
+            ab, info = _platt_fit([oof], [y_d])
+            # what the fold problems ended at, on the host (the device state, and with it the matrix, is released): per fold the
+            # training rows, the held-out rows, alpha and rho
+            self._folds = [(pr.rows.cpu().numpy(), te_d.cpu().numpy(), pr.alpha.cpu().numpy(), float(pr.rho.item())) for pr, te_d in parts]
+            self._adopt(X, classes, ys, g, mean, norms, problems[0], *solved[0])
+        from sklearn.exceptions import ConvergenceWarning
+        if not all(done for _, done in solved[1:]):
+            warnings.warn(f"PlattSVC: a fold's solver stopped after max_iter={self.max_iter} iterations before reaching tol={self.tol}", ConvergenceWarning)
+        self.probA_, self.probB_ = np.array([ab[0, 0]]), np.array([ab[0, 1]])
+        self.platt_n_iter_, self.platt_status_ = int(info[0, 0]), int(info[0, 1])
+        self.oof_decision_ = oof.cpu().numpy()
+        if self.platt_status_ != 0:
+            warnings.warn(f"PlattSVC: the sigmoid fit ended without meeting its gradient criterion ({PLATT_STATUS[self.platt_status_]} after "
+                          f"{self.platt_n_iter_} iterations)", ConvergenceWarning)
+        return self
+
+    # ---- probabilities ----------------------------------------------------------------------------------------------
+    def _proba(self, X):
+        if not hasattr(self, "_sv"):
+            raise RuntimeError("svm: not fitted")
+        dev = torch.device(self.device)
+        Xq, was_numpy = _dense.to_device_matrix(X, dev, "svm", allow_row_stride=True)
+        f = self._decision(Xq).neg()                                  # libsvm's sign: positive towards classes_[0]
+        m = f.numel()
+        with torch.cuda.device(dev):
+            proba = torch.empty((m, 2), dtype=torch.float64, device=dev)
+            _lib.check(_lib.lib().bbbp_svm_platt_proba(_dense.stream(), f.data_ptr() if m else None, m, float(self.probA_[0]), float(self.probB_[0]),
+                                                       proba.data_ptr() if m else None), "bbbp_svm_platt_proba")
+        return proba, was_numpy
+
+    def predict_proba(self, X):
+        """[m, 2] float64 in ``classes_`` order (numpy in, numpy out; CUDA in, CUDA out): column 0 is libsvm's ``sigmoid_predict`` of minus
+        the decision value, clipped to [1e-7, 1 - 1e-7]; column 1 is one minus it."""
+        proba, was_numpy = self._proba(X)
+        return proba.cpu().numpy() if was_numpy else proba
+
+    def predict_log_proba(self, X):
+        proba, was_numpy = self._proba(X)
+        return np.log(proba.cpu().numpy()) if was_numpy else proba.log()
 
 
 # ---- epsilon-support-vector regression ---------------------------------------------------------------------------------------------------

@@ -523,6 +523,48 @@ typedef struct bbbp_svr_problem {
  * grad.  A problem's result does not depend on `iters`, on the others in the batch or on their order, and is bit-identical from call to
  * call. */
 int bbbp_svr_smo(void* stream, const bbbp_svr_problem* problems, int n_problems, int iters);
+/* Class probabilities for the C-SVC above by Platt scaling (csrc/svm_proba.hip; SVC(probability=True) of the classification stack,
+ * Models/model_opt_maccs.py:128): out-of-fold decision values read from the resident kernel matrix, libsvm's sigmoid_train (Lin, Lin and
+ * Weng, "A note on Platt's probabilistic outputs for support vector machines") and its sigmoid_predict.  Float64 throughout; every result
+ * is bit-identical from call to call and does not depend on what else is in the batch.
+ *
+ * One fold whose dual problem the solver above has finished over the matrix K of n_rows data rows: rows / y / alpha / rho / n are that
+ * problem's (rows NULL: the identity; rho stays on the device), held lists the n_held rows of K the fold left out.  For each of them
+ * out[held[h]] = sum_s alpha[s] y[s] K[held[h]][rows[s]] - *rho, libsvm's decision value (positive towards y = +1), the terms added by
+ * one wavefront: lane l takes s = l, l + 64, ... in ascending order and a butterfly adds the 64 lanes.  Every entry of rows and held must
+ * lie in [0, n_rows); an entry outside is skipped (a held row is not written, a training row adds nothing).  n_held may be 0. */
+typedef struct bbbp_svm_oof_desc {
+    const double* K; long ldk; int n_rows;     /* [n_rows][ldk] */
+    const int* rows;                           /* [n], nullable */
+    const double* y; const double* alpha;      /* [n] each */
+    const double* rho;                         /* [1], device */
+    int n;
+    const int* held; int n_held;               /* [n_held] */
+    double* out;                               /* [n_rows], indexed by data row */
+} bbbp_svm_oof_desc;
+/* `folds` is a host array; up to 32 folds are one launch. */
+int bbbp_svm_oof_decision(void* stream, const bbbp_svm_oof_desc* folds, int n_folds);
+/* One calibration problem: min over (A, B) of sum_i t_i f_i + log(1 + exp(-f_i)), f_i = A dec[i] + B, with the targets
+ * t_i = (N+ + 1) / (N+ + 2) where y[i] > 0 and 1 / (N- + 2) elsewhere (N+ / N- count the two kinds).  Outputs: ab = (A, B);
+ * info = (Newton iterations, status). */
+#define BBBP_PLATT_CONVERGED 0          /* both gradient components below 1e-5 */
+#define BBBP_PLATT_LINE_SEARCH 1        /* the step fell below 1e-10 without sufficient decrease */
+#define BBBP_PLATT_MAX_ITER 2           /* 100 iterations */
+typedef struct bbbp_svm_platt_problem {
+    const double* dec; const double* y;        /* [n] each */
+    int n;
+    double* ab;                                /* [2] */
+    int* info;                                 /* [2] */
+} bbbp_svm_platt_problem;
+/* libsvm's sigmoid_train, one work-group per problem and no host round trip inside one: Newton's method from A = 0,
+ * B = log((N- + 1) / (N+ + 1)), the Hessian's diagonal raised by 1e-12, backtracking by halves with the Armijo constant 1e-4, the
+ * overflow-safe two-branch forms of the objective and of p and q.  The five sums of an iteration and each line-search objective are one pass
+ * over dec: per thread its elements in ascending order, the 64 lanes of a wave by a butterfly, the waves in ascending order.  `problems`
+ * is a host array. */
+int bbbp_svm_platt_fit(void* stream, const bbbp_svm_platt_problem* problems, int n_problems);
+/* proba[q][0] = 1 / (1 + exp(A dec[q] + B)) by libsvm's two-branch sigmoid_predict, clipped to [1e-7, 1 - 1e-7];
+ * proba[q][1] = 1 - proba[q][0].  m may be 0. */
+int bbbp_svm_platt_proba(void* stream, const double* dec, long m, double A, double B, double* proba);
 
 /* ---- logreg: batched float64 Newton solver for binary L2 logistic regression (csrc/logreg.hip) ------------------------------
  * LogisticRegression(max_iter=1000) of the classification stack (Models/model_opt_maccs.py:124-180), searched over C in {0.1, 1, 10}.
