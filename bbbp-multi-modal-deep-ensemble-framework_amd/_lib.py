@@ -245,6 +245,8 @@ _SIGNATURES = {
     "bbbp_bias_act_bwd": (c_int, [c_void_p, _FP, c_int, _FP, c_int, _FP, c_int, c_int, c_int, c_float]),
     "bbbp_fusion_combine_fwd": (c_int, [c_void_p, _FP, _FP, _PP, _PP, _FP, _FP, c_int, c_int, c_int, c_int]),
     "bbbp_fusion_combine_bwd": (c_int, [c_void_p, _FP, _FP, _FP, _FP, _PP, _FP, _FP, _FP, c_int, c_int, c_int, c_int]),
+    "bbbp_head_fwd": (c_int, [c_void_p, _FP, _PP, _PP, _PP, _PP] + [_FP] * 23 + [c_int] * 5),
+    "bbbp_head_bwd": (c_int, [c_void_p] + [_FP] * 10 + [_PP, _PP] + [_FP] * 14 + [c_int] * 4),
     "bbbp_mse": (c_int, [c_void_p, _FP, _FP, _FP, _FP, c_int, c_float]),
     "bbbp_adamw_step": (c_int, [c_void_p, _FP, _FP, _FP, _FP, c_long, c_double, c_double, c_double, c_double, c_double, c_int,
                                 c_double]),

@@ -574,3 +574,42 @@ int bbbp_head_backward_fused_sync(hipStream_t st, const float* dout, const float
     BBBP_CHECK_LAUNCH();
     return BBBP_OK;
 }
+
+// ---- the two directions as ops of their own (include/bbbp_hip.h): the launchers above, behind argument checks ----
+namespace {
+bool four_pointers(const float* const* a) { return a && a[0] && a[1] && a[2] && a[3]; }
+}  // namespace
+
+int bbbp_head_fwd(void* stream, const float* comb, const float* const* fw1, const float* const* fb1, const float* const* fw2,
+                  const float* const* fb2, const float* w0, const float* b0, const float* gamma, const float* beta,
+                  float* running_mean, float* running_var, const float* w3, const float* b3, const float* w5, const float* b5,
+                  const float* w7, const float* b7, float* hid, float* attn, float* fused, float* h, float* hb, float* bn_mean,
+                  float* bn_rstd, float* h2, float* h3, float* out, float* partial, int B, int training, int concat, int world, int rank) {
+    BBBP_CHECK_ARG(comb && w0 && b0 && gamma && beta && running_mean && running_var && w3 && b3 && w5 && b5 && w7 && b7 && h && hb &&
+                   bn_mean && bn_rstd && h2 && h3 && out && partial, "head_fwd: null pointer");
+    BBBP_CHECK_ARG(concat || (four_pointers(fw1) && four_pointers(fb1) && four_pointers(fw2) && four_pointers(fb2) && hid && attn && fused),
+                   "head_fwd: null pointer (the fusion block's parameters and outputs are required unless concat)");
+    const float* const none[NHEADS] = {nullptr, nullptr, nullptr, nullptr};          // concat: the launcher copies four pointers it never reads
+    bbbp_head_sync sync;
+    sync.world = world; sync.rank = rank;
+    return bbbp_head_forward_fused_sync(static_cast<hipStream_t>(stream), comb, concat ? none : fw1, concat ? none : fb1, concat ? none : fw2,
+                                        concat ? none : fb2, w0, b0, gamma, beta, running_mean, running_var, w3, b3, w5, b5, w7, b7, hid, attn,
+                                        fused, h, hb, bn_mean, bn_rstd, h2, h3, out, partial, B, training, concat, &sync);
+}
+
+int bbbp_head_bwd(void* stream, const float* dout, const float* comb, const float* hid, const float* attn, const float* h,
+                  const float* h2, const float* h3, const float* bn_mean, const float* bn_rstd, const float* gamma,
+                  const float* const* fw1, const float* const* fw2, const float* w0, const float* w3, const float* w5,
+                  const float* w7, float* dh3, float* dh2, float* dhb, float* dh, float* dlogit, float* dpre, float* dcomb,
+                  float* dgamma, float* dbeta, float* partial, int B, int training, int world, int rank) {
+    BBBP_CHECK_ARG(dout && comb && hid && attn && h && h2 && h3 && bn_mean && bn_rstd && gamma && four_pointers(fw1) && four_pointers(fw2) &&
+                   w0 && w3 && w5 && w7 && dh3 && dh2 && dhb && dh && dlogit && dpre && dcomb && dgamma && dbeta && partial,
+                   "head_bwd: null pointer");
+    BBBP_CHECK_ARG(B >= 1, "head_bwd: empty batch");
+    BBBP_CHECK_ARG(world >= 1 && rank >= 0 && rank < world, "head_bwd: rank %d of %d", rank, world);
+    BBBP_CHECK_ARG(!(training && (long)B * world <= 1), "Expected more than 1 value per channel when training, got input size [%d, %d]", B, H1);
+    bbbp_head_sync sync;
+    sync.world = world; sync.rank = rank;
+    return bbbp_head_backward_fused_sync(static_cast<hipStream_t>(stream), dout, comb, hid, attn, h, h2, h3, bn_mean, bn_rstd, gamma, fw1, fw2,
+                                         w0, w3, w5, w7, dh3, dh2, dhb, dh, dlogit, dpre, dcomb, dgamma, dbeta, partial, B, training, &sync);
+}

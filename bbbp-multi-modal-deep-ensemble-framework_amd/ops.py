@@ -428,6 +428,96 @@ def bias_act_bwd(dy: torch.Tensor, y: Optional[torch.Tensor], act=None, scale: f
     return db
 
 
+# parameters of the fusion block and the head as ops.head_fwd / head_bwd take them: name -> shape; fw1 .. fb2 are lists of four tensors
+HEAD_PARAM_SHAPES = {"fw1": (128, 256), "fb1": (128,), "fw2": (128,), "fb2": (1,), "w0": (256, 256), "b0": (256,), "gamma": (256,),
+                     "beta": (256,), "w3": (128, 256), "b3": (128,), "w5": (64, 128), "b5": (64,), "w7": (64,), "b7": (1,)}
+_HEAD_PER_HEAD = ("fw1", "fb1", "fw2", "fb2")
+
+
+def _head_operand(t: torch.Tensor, name: str, shape) -> int:
+    """Device address of a contiguous float32 tensor of ``shape`` (any shape with as many elements: the kernels index it flat)."""
+    numel = 1
+    for s in shape:
+        numel *= s
+    if _chk(t, name).numel() != numel or not t.is_contiguous():
+        raise RuntimeError(f"head: {name} must hold {numel} contiguous elements ({shape}), got shape {tuple(t.shape)} strides {t.stride()}")
+    return t.data_ptr()
+
+
+def _head_params(params, names, what: str):
+    """ctypes arguments of the named parameters, in order: a pointer array per fusion-block entry, an address per head entry."""
+    args = []
+    for n in names:
+        if n in _HEAD_PER_HEAD:
+            if len(params[n]) != 4:
+                raise RuntimeError(f"{what}: {n} must list the four fusion heads' tensors, got {len(params[n])}")
+            args.append(_lib.ptr_array([_head_operand(t, f"{n}[{i}]", HEAD_PARAM_SHAPES[n]) for i, t in enumerate(params[n])]))
+        else:
+            args.append(_head_operand(params[n], n, HEAD_PARAM_SHAPES[n]))
+    return args
+
+
+def _head_partial(partial, B: int, world: int, device, what: str) -> torch.Tensor:
+    need = max(world, 1) * ((B + 15) // 16) * 2 * 256
+    if partial is None:
+        return torch.empty(need, device=device, dtype=torch.float32)
+    if _chk(partial, "partial").numel() < need or not partial.is_contiguous():
+        raise RuntimeError(f"{what}: partial must hold at least {need} contiguous floats, got {partial.numel()}")
+    return partial
+
+
+def head_fwd(comb: torch.Tensor, params: dict, running_mean: torch.Tensor, running_var: torch.Tensor, training: bool, concat: bool = False,
+             world: int = 1, rank: int = 0, partial: Optional[torch.Tensor] = None, fusion_out=None) -> dict:
+    """Fusion block + regression head, forward (``bbbp_head_fwd``).  ``params``: HEAD_PARAM_SHAPES (the fusion entries may be missing when
+    ``concat``).  Returns every tensor the kernels write, by name: hid, attn, fused (None when ``concat``, unless ``fusion_out`` hands in
+    three buffers, which must then stay untouched), h, hb, bn_mean, bn_rstd, h2, h3, out; the running statistics are updated in place when
+    training.  ``partial``: the block-partial workspace, shared between the ranks' calls when ``world`` > 1."""
+    if _chk(comb, "comb").dim() != 2 or comb.shape[1] != 256 or not comb.is_contiguous():
+        raise RuntimeError(f"head_fwd: comb must be a contiguous [B, 256] tensor, got shape {tuple(comb.shape)} strides {comb.stride()}")
+    B, dev = comb.shape[0], comb.device
+    new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+    fusion = [None] * 4 if concat else _head_params(params, _HEAD_PER_HEAD, "head_fwd")
+    head = _head_params(params, ("w0", "b0", "gamma", "beta"), "head_fwd") + [_head_operand(running_mean, "running_mean", (256,)),
+                                                                               _head_operand(running_var, "running_var", (256,))]
+    head += _head_params(params, ("w3", "b3", "w5", "b5", "w7", "b7"), "head_fwd")
+    o = {}
+    if fusion_out is not None:
+        o["hid"], o["attn"], o["fused"] = fusion_out
+        for n, shape in (("hid", (4, B, 128)), ("attn", (B, 4)), ("fused", (B, 256))):
+            _head_operand(o[n], n, shape)
+    elif concat:
+        o["hid"] = o["attn"] = o["fused"] = None
+    else:
+        o["hid"], o["attn"], o["fused"] = new(4, B, 128), new(B, 4), new(B, 256)
+    o.update(h=new(B, 256), hb=new(B, 256), bn_mean=new(256), bn_rstd=new(256), h2=new(B, 128), h3=new(B, 64), out=new(B))
+    partial = _head_partial(partial, B, world, dev, "head_fwd")
+    _lib.check(_lib.lib().bbbp_head_fwd(_stream(), comb.data_ptr(), *fusion, *head, *[_p(o[n]) for n in (
+        "hid", "attn", "fused", "h", "hb", "bn_mean", "bn_rstd", "h2", "h3", "out")], partial.data_ptr(), B, int(training), int(concat),
+        world, rank), "bbbp_head_fwd")
+    return o
+
+
+def head_bwd(dout: torch.Tensor, comb: torch.Tensor, saved: dict, params: dict, training: bool, world: int = 1, rank: int = 0,
+             partial: Optional[torch.Tensor] = None) -> dict:
+    """Input-gradient chain of the fusion block + head (``bbbp_head_bwd``).  ``saved``: hid, attn, h, h2, h3, bn_mean, bn_rstd as
+    ``head_fwd`` returns them -- or any tensors of those shapes: they are taken as given.  Returns dh3, dh2, dhb, dh, dlogit [4, B],
+    dpre [4, B, 128], dcomb, dgamma, dbeta by name."""
+    if _chk(comb, "comb").dim() != 2 or comb.shape[1] != 256 or not comb.is_contiguous():
+        raise RuntimeError(f"head_bwd: comb must be a contiguous [B, 256] tensor, got shape {tuple(comb.shape)} strides {comb.stride()}")
+    B, dev = comb.shape[0], comb.device
+    new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+    ins = [_head_operand(dout, "dout", (B,)), comb.data_ptr()]
+    ins += [_head_operand(saved[n], n, shape) for n, shape in (("hid", (4, B, 128)), ("attn", (B, 4)), ("h", (B, 256)), ("h2", (B, 128)),
+                                                                ("h3", (B, 64)), ("bn_mean", (256,)), ("bn_rstd", (256,)))]
+    ins += _head_params(params, ("gamma", "fw1", "fw2", "w0", "w3", "w5", "w7"), "head_bwd")
+    o = dict(dh3=new(B, 64), dh2=new(B, 128), dhb=new(B, 256), dh=new(B, 256), dlogit=new(4, B), dpre=new(4, B, 128), dcomb=new(B, 256),
+             dgamma=new(256), dbeta=new(256))
+    partial = _head_partial(partial, B, world, dev, "head_bwd")
+    _lib.check(_lib.lib().bbbp_head_bwd(_stream(), *ins, *[t.data_ptr() for t in o.values()], partial.data_ptr(), B, int(training), world,
+                                        rank), "bbbp_head_bwd")
+    return o
+
+
 def mse(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0):
     """Returns (loss[1], dpred) for loss = mean((pred - target)^2)."""
     pred = _chk(pred, "pred").contiguous().view(-1)

@@ -194,6 +194,34 @@ int bbbp_fusion_combine_bwd(void* stream, const float* dout, const float* combin
                             const float* attn, const float* const* w2, float* dcombined, float* dlogit,
                             float* dpre, int rows, int dim, int hidden, int num_heads);
 
+/* ---- the fusion block and the regression head as two ops (csrc/head.hip; R:60-65, 98-107): the kernels bbbp_mixed_forward / _backward
+ * run between the join of the branches and the loss, with every tensor they read or write an argument.
+ * Forward: combined [B][256] -> 4 x (Linear(256,128) -> Tanh -> Linear(128,1)) -> softmax over the heads -> fused = sum_h a_h combined ->
+ * h = ReLU(fc.0) -> hb = BatchNorm1d (eps 1e-5, momentum 0.1; training: batch statistics, running statistics updated in place with the
+ * unbiased variance; else the running statistics) -> h2 = ReLU(fc.3) -> h3 = ReLU(fc.5) -> out [B] = fc.7.  fw1 / fb1 / fw2 / fb2: host
+ * arrays of four device pointers ([128][256], [128], [128], [1] per head); Linear weights are [out][in] and need only 4-byte alignment.
+ * Written: hid [4][B][128], attn [B][4], fused [B][256], h, hb [B][256], bn_mean, bn_rstd [256] (the statistics hb was normalised with),
+ * h2 [B][128], h3 [B][64], out.  concat != 0: fused IS combined (torch.cat fusion); the fusion block's parameters, hid, attn and fused are
+ * neither read nor written and may be NULL.
+ * Backward: the input-gradient chain from dout [B] over SAVED tensors taken as given (nothing is recomputed from combined): dh3, dh2, dhb,
+ * dh, dlogit [4][B], dpre [4][B][128], dcomb [B][256] (zero where combined <= 0) and the BatchNorm's dgamma, dbeta [256]; training = 0:
+ * dh = dhb gamma rstd.  No concat form: the engine runs the per-op chain there.
+ * world / rank: the batch is sharded over `world` ranks of B rows EACH (the merge derives every rank's block sizes from this rank's B), and
+ * statistics and backward sums are merged over all ranks' 16-row blocks in rank order; dgamma / dbeta stay this rank's sums.  The first
+ * launch of a direction writes this rank's slot of `partial`, the second reads every slot: the caller makes the other ranks' slots arrive
+ * in between (world = 1, rank = 0: the single-rank head, nothing to do).  `partial`: world * ceil(B / 16) * 2 * 256 floats.
+ * BBBP_ERR_ARG before any launch: a NULL required pointer, B < 1, rank outside [0, world), training with B * world <= 1. */
+int bbbp_head_fwd(void* stream, const float* comb, const float* const* fw1, const float* const* fb1, const float* const* fw2,
+                  const float* const* fb2, const float* w0, const float* b0, const float* gamma, const float* beta,
+                  float* running_mean, float* running_var, const float* w3, const float* b3, const float* w5, const float* b5,
+                  const float* w7, const float* b7, float* hid, float* attn, float* fused, float* h, float* hb, float* bn_mean,
+                  float* bn_rstd, float* h2, float* h3, float* out, float* partial, int B, int training, int concat, int world, int rank);
+int bbbp_head_bwd(void* stream, const float* dout, const float* comb, const float* hid, const float* attn, const float* h,
+                  const float* h2, const float* h3, const float* bn_mean, const float* bn_rstd, const float* gamma,
+                  const float* const* fw1, const float* const* fw2, const float* w0, const float* w3, const float* w5,
+                  const float* w7, float* dh3, float* dh2, float* dhb, float* dh, float* dlogit, float* dpre, float* dcomb,
+                  float* dgamma, float* dbeta, float* partial, int B, int training, int world, int rank);
+
 /* ---- nn.MSELoss (R:143,189) and its gradient; optim.AdamW.step (R:172,191) -------------------- */
 int bbbp_mse(void* stream, const float* pred, const float* target, float* loss, float* dpred, int n, float grad_scale);
 /* AdamW: the hyper-parameters are DOUBLES, as torch.optim.AdamW holds them (Python floats): the step's float32 constants are derived in
