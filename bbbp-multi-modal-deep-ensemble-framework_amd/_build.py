@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbbbp_hip.so")
-SOURCES = ["util.hip", "gemm.hip", "conv.hip", "conv_wino.hip", "conv_b3.hip", "conv_b3c1.hip", "rowops.hip", "engine.hip", "encoder.hip", "fold.hip", "attention.hip", "attention_b3.hip", "preprocess.hip", "mlp.hip", "head.hip", "forest.hip", "pca.hip", "knn.hip", "svm.hip", "svm_proba.hip", "svr.hip", "logreg.hip", "gbt.hip", "rf.hip", "iforest.hip", "bnb.hip", "smote.hip"]
+SOURCES = ["util.hip", "gemm.hip", "conv.hip", "conv_wino.hip", "conv_b3.hip", "conv_b3c1.hip", "rowops.hip", "engine.hip", "encoder.hip", "fold.hip", "attention.hip", "attention_b3.hip", "preprocess.hip", "mlp.hip", "head.hip", "forest.hip", "pca.hip", "knn.hip", "svm.hip", "svm_proba.hip", "svr.hip", "logreg.hip", "gbt.hip", "rf.hip", "iforest.hip", "bnb.hip", "smote.hip", "metrics.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-source flags.  conv_b3c1.hip: the pooling epilogue takes maxima of accumulator registers; in IEEE mode every such operand first gets a
@@ -25,8 +25,9 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # smote.hip: a synthetic row is base + step * (neighbour - base) with the product and the sum rounded one by one, as numpy rounds them
 # (tests/smote_numpy.py); fused into one multiply-add the row differs in its last bit.
 # svm_proba.hip: the sigmoid's argument A dec + B rounds as a product and a sum, as libsvm and tests/platt_numpy.py round it.
+# metrics.hip: a squared-error sum adds d * d to its accumulator as a product and a sum (tests/metrics_numpy.py); fused, the MSE differs in its last bits.
 EXTRA_FLAGS = {"conv_b3c1.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"], "svr.hip": ["-ffp-contract=off"], "iforest.hip": ["-ffp-contract=off"],
-               "bnb.hip": ["-ffp-contract=off"], "smote.hip": ["-ffp-contract=off"], "svm_proba.hip": ["-ffp-contract=off"]}
+               "bnb.hip": ["-ffp-contract=off"], "smote.hip": ["-ffp-contract=off"], "svm_proba.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target: str, deps) -> bool:

@@ -219,6 +219,10 @@ _SIGNATURES = {
     "bbbp_bnb_jll": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_int, c_long, c_void_p]),
     "bbbp_smote_synth": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_long]),
     "bbbp_tomek_links": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "bbbp_metrics_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "bbbp_metrics_confusion": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "bbbp_metrics_auc_pairs": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "bbbp_metrics_sq_sums": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "bbbp_graph_stats": (c_int, [POINTER(c_long), POINTER(c_long)]),
     "bbbp_conv_last_clock": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "bbbp_set_conv_winograd": (c_int, [c_int]),

@@ -838,6 +838,41 @@ int bbbp_smote_synth(void* stream, const void* Xc, int x_dtype, long ldx, int n_
  * written.  An index or a label outside its array is no link. */
 int bbbp_tomek_links(void* stream, const long* nn1, const int* y, const unsigned char* remove, int n_classes, int n, unsigned char* keep);
 
+/* ---- batched classification and regression scores (csrc/metrics.hip) ----------------------------------------------------------------------
+ * evaluate_model of the classification scripts (Models/model_maccs.py, model_opt*.py: eight scores per fitted model) and the
+ * mean_squared_error / r2_score pair of the regression scripts.  The device computes integers (confusion counts, Mann-Whitney pair counts)
+ * and float64 sums in a fixed order; bbbp_amd/metrics.py forms the scores from them on the host.  Common to the three entry points:
+ * M columns [M][n] with row stride ld (unit inner stride, any base alignment), one y vector [n], and seg [n] (may be NULL: every row in
+ * segment 0): a segment id in [0, G) per row, any other value leaves the row out.  Results are per (column, segment).  Every output word is
+ * written, so nothing has to be cleared; *flag (device, 0 on entry) is set to 1 when a float that takes part (a row of some segment) is NaN
+ * or infinite.  Row tiles of BBBP_METRICS_TILE_ROWS rows go to work-groups of their own: with more than one tile, `work` receives one slab
+ * of partial results per tile (bbbp_metrics_work_bytes; integer sums, so the result does not depend on any order) and a second launch adds
+ * them; with one tile `work` may be NULL and there is one launch. */
+#define BBBP_METRICS_DTYPE_U8 2          /* beside BBBP_DTYPE_F32 / _F64: hard predictions as 0 / 1 bytes (any non-zero byte is 1) */
+#define BBBP_METRICS_MAX_COLUMNS 65535
+#define BBBP_METRICS_MAX_GROUPS 64
+#define BBBP_METRICS_TILE_ROWS 16384     /* confusion counts: rows per work-group */
+#define BBBP_METRICS_PAIR_ROWS 256       /* pair counts: rows per work-group (one per lane) */
+/* Bytes of `work` for n rows: what = 0 confusion counts, 1 pair counts.  0 when one tile suffices (confusion counts only). */
+size_t bbbp_metrics_work_bytes(int what, int n_columns, int n, int n_groups);
+/* counts[m][g] = (tn, fp, fn, tp) as int64 over the rows of segment g, with the prediction of row i of column m being
+ * pred[m * ld + i] != 0 for bytes, and pred[m * ld + i] > thr[m] (strict; thr is a device array of M doubles, compared in float64) for
+ * float32 / float64 scores.  y01 [n] bytes: the truth, non-zero is positive.  thr is not read for bytes and may be NULL. */
+int bbbp_metrics_confusion(void* stream, const void* pred, int dtype, long ld, int n_columns, int n, const double* thr,
+                           const unsigned char* y01, const int* seg, int n_groups, long long* counts, void* work, int* flag);
+/* out[m][g] = (U2, P, N, nonfinite) as int64: P, N the positive and negative rows of segment g, nonfinite its rows whose score is NaN or
+ * infinite, and U2 = sum over positive rows i of #{negative rows j of the segment: s_j < s_i} + #{...: s_j <= s_i}, so that
+ * AUC = U2 / (2 P N).  Scores (dtype: float32, float64 or bytes) are compared as float64 values (-0.0 == 0.0; a NaN compares false).
+ * Every pair is visited: no sort, no row limit, n^2 / 256 LDS tile passes per column.  work (bbbp_metrics_work_bytes(1, ...)) is needed. */
+int bbbp_metrics_auc_pairs(void* stream, const void* score, int dtype, long ld, int n_columns, int n, const unsigned char* y01,
+                           const int* seg, int n_groups, long long* out, void* work);
+/* sse[m][g] = sum (y_i - p_i)^2 over the rows of segment g for column m (p float32 or float64, widened exactly), and once per segment
+ * ystat[g] = (sum y_i, sum (y_i - ybar)^2 with ybar = (sum y_i) / count, count) as doubles.  One work-group of 256 lanes per (column,
+ * segment): lane t adds its rows t, t + 256, ... in ascending order, then `v += shfl_down(v, off)` for off = 32 .. 1, then the four waves
+ * in ascending order; every product, difference and sum is rounded once (no fused multiply-add). */
+int bbbp_metrics_sq_sums(void* stream, const void* pred, int dtype, long ld, int n_columns, int n, const double* y, const int* seg,
+                         int n_groups, double* sse, double* ystat, int* flag);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
