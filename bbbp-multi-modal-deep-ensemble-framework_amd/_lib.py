@@ -227,6 +227,7 @@ _SIGNATURES = {
     "bbbp_conv_last_clock": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "bbbp_set_conv_winograd": (c_int, [c_int]),
     "bbbp_get_conv_winograd": (c_int, []),
+    "bbbp_conv_kernel_form": (c_int, [c_int, c_int, c_int, c_int]),
     "bbbp_conv_winograd_phases": (c_int, [POINTER(c_uint64)]),
     "bbbp_conv_b3_phases": (c_int, [POINTER(c_uint64)]),
     "bbbp_conv3x3_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

@@ -914,6 +914,17 @@ extern "C" int bbbp_set_conv2_fwd_pipe(int on) {
     return prev;
 }
 
+// The form the matching C entry point would run right now (include/bbbp_hip.h): the same conv_choice under the same mask, the calling
+// thread's two preferences and the knobs.  Host side only.
+extern "C" int bbbp_conv_kernel_form(int op, int cin, int cout, int hw) {
+    if (op < 0 || op > 2 || !supported(cin, cout, hw, hw) || (op == 1 && cin == 3)) return -1;
+    ConvPrefs prefs;
+    prefs.conv2_fwd_pipe = g_bbbp_conv2_fwd_pipe;
+    prefs.wgrad_beside_encoder = g_bbbp_conv_wgrad_beside_encoder;
+    const ConvOp ops[3] = {ConvOp::Fwd, ConvOp::Dgrad, ConvOp::Wgrad};
+    return (int)conv_choice(ops[op], cin, cout, hw, prefs).form;
+}
+
 extern "C" int bbbp_conv3x3_relu_pool_fwd(void* stream, const float* x, const float* w, const float* bias,
                                           float* y, uint8_t* mask, int B, int cin, int cout, int H, int W,
                                           void* workspace, size_t workspace_bytes) {

@@ -193,8 +193,33 @@ def conv3x3_relu_pool_fwd(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, kee
     return y, mask
 
 
+def _conv_bwd_check(what: str, gy: torch.Tensor, mask: torch.Tensor, x: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None) -> None:
+    """The shapes a conv backward op reads must fit each other: the kernels index ``mask`` like ``gy`` and ``x`` / ``w`` by the stage's
+    channel counts, so a short or strided operand is read out of bounds or silently mixes channels."""
+    if gy.dim() != 4:
+        raise RuntimeError(f"{what}: gy must be [B, cout, H/2, W/2], got shape {tuple(gy.shape)}")
+    if tuple(mask.shape) != tuple(gy.shape):
+        raise RuntimeError(f"{what}: mask shape {tuple(mask.shape)} != gy shape {tuple(gy.shape)}")
+    if not mask.is_contiguous():
+        raise RuntimeError(f"{what}: mask must be contiguous, got shape {tuple(mask.shape)} strides {mask.stride()}")
+    B, cout, Hp, Wp = gy.shape
+    if x is not None:
+        if x.dim() != 4 or not x.is_contiguous():
+            raise RuntimeError(f"{what}: x must be contiguous NCHW, got shape {tuple(x.shape)} strides {x.stride()}")
+        if x.shape[2] % 2 or x.shape[3] % 2:
+            raise RuntimeError(f"{what}: x has an odd height or width, shape {tuple(x.shape)}")
+        if (x.shape[0], x.shape[2] // 2, x.shape[3] // 2) != (B, Hp, Wp):
+            raise RuntimeError(f"{what}: gy shape {tuple(gy.shape)} does not match x shape {tuple(x.shape)} (batch, H/2, W/2)")
+    if w is not None:
+        if not w.is_contiguous():
+            raise RuntimeError(f"{what}: weight must be contiguous, got shape {tuple(w.shape)} strides {w.stride()}")
+        if w.dim() != 4 or tuple(w.shape) != (cout, w.shape[1], 3, 3):
+            raise RuntimeError(f"{what}: weight shape {tuple(w.shape)} is not ({cout}, cin, 3, 3) for gy shape {tuple(gy.shape)}")
+
+
 def conv3x3_relu_pool_bwd_data(gy: torch.Tensor, mask: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     _chk(gy, "gy"); _chk(mask, "mask", torch.uint8); _chk(w, "weight")
+    _conv_bwd_check("conv3x3_relu_pool_bwd_data", gy, mask, w=w)
     gy = gy.contiguous()
     B, cout, Hp, Wp = gy.shape
     cin = w.shape[1]
@@ -210,6 +235,7 @@ def conv3x3_relu_pool_bwd_data(gy: torch.Tensor, mask: torch.Tensor, w: torch.Te
 
 def conv3x3_relu_pool_bwd_weight(x: torch.Tensor, gy: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     _chk(x, "x"); _chk(gy, "gy"); _chk(mask, "mask", torch.uint8)
+    _conv_bwd_check("conv3x3_relu_pool_bwd_weight", gy, mask, x=x)
     gy = gy.contiguous()
     B, cin, H, W = x.shape
     cout = gy.shape[1]

@@ -110,6 +110,15 @@ int bbbp_conv_last_clock(unsigned long long* shader_cycles, unsigned long long* 
  * -- half the matrix-pipe time, same six piece products, same float32 accuracy; bit 8 (256): its 4-wave form wherever it runs (tests). */
 int bbbp_set_conv_winograd(int mask);
 int bbbp_get_conv_winograd(void);
+/* Which kernel form a conv call of this stage runs on right now: under the current mask, the calling thread's two preferences
+ * (bbbp_set_conv2_fwd_pipe, bbbp_set_conv_wgrad_beside_encoder) and the process's BBBP_C* settings (host side, no GPU work).
+ * op: 0 forward, 1 data gradient, 2 weight gradient; hw: the input map's height = width.
+ * 0 direct implicit GEMM on the f32 MFMA, 1 Winograd F(2x2,3x3), 2 split-bf16, 3 its software-pipelined kernel (64 x 64 maps),
+ * 4 split-bf16 of the 3->32 stage (weight gradient, or the phase-by-phase forward), 5 that stage's software-pipelined forward,
+ * 6 dense split-bf16 weight gradient, 7 / 8 the structured-sparse weight gradient with 8 / 4 waves;
+ * -1 for a stage the entry points reject, the data gradient of a 3-channel stage included.
+ * For A/B scripts and tests; a caller never needs it to run a conv. */
+int bbbp_conv_kernel_form(int op, int cin, int cout, int hw);
 /* Measurement aid: with BBBP_WINO_PROBE=1 in the environment the Winograd kernels stamp the shader clock at phase boundaries;
  * phases4 = cycles work-group 0 spent in {accumulator init, k-steps, stage hand-over, output transform} of the last launch. */
 int bbbp_conv_winograd_phases(unsigned long long* phases4);
