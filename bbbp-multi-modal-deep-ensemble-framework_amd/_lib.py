@@ -125,6 +125,14 @@ class GbtChain(Structure):
                 ("tree_nodes", c_void_p), ("train_score", c_void_p), ("raw", c_void_p)]
 
 
+class XgbProblem(Structure):
+    """bbbp_xgb_problem (include/bbbp_hip.h)."""
+    _fields_ = [("bins", c_void_p), ("cuts", c_void_p), ("y", c_void_p), ("n", c_int), ("d", c_int), ("cut_stride", c_int), ("n_estimators", c_int),
+                ("max_depth", c_int), ("min_child_rows", c_int), ("reg_lambda", c_double), ("gamma", c_double), ("learning_rate", c_float),
+                ("base_score", c_float), ("work", c_void_p), ("left", c_void_p), ("right", c_void_p), ("feature", c_void_p), ("cond", c_void_p),
+                ("base_weight", c_void_p), ("loss_change", c_void_p), ("sum_hessian", c_void_p), ("tree_nodes", c_void_p), ("margin", c_void_p)]
+
+
 _FP = c_void_p          # device float*
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -199,6 +207,12 @@ _SIGNATURES = {
     "bbbp_gbr_fit": (c_int, [c_void_p, POINTER(GbtChain), c_void_p, c_int]),
     "bbbp_gbt_staged_decision": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                          c_double, c_double, c_void_p, c_int, c_void_p]),
+    "bbbp_xgb_fit_tree_capacity": (c_int, [c_int, c_int]),
+    "bbbp_xgb_fit_work_bytes": (c_size_t, [c_int, c_int]),
+    "bbbp_xgb_bin": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "bbbp_xgb_fit": (c_int, [c_void_p, POINTER(XgbProblem), c_void_p, c_int, c_void_p]),
+    "bbbp_xgb_fit_profile": (c_int, [c_int]),
+    "bbbp_xgb_fit_last": (c_int, [POINTER(c_double), POINTER(c_long)]),
     "bbbp_rf_fit_tree_capacity": (c_int, [c_int]),
     "bbbp_rf_fit_work_bytes": (c_size_t, [c_int, c_int, c_int]),
     "bbbp_rf_hash": (c_uint64, [c_uint64, c_uint64]),

@@ -2,8 +2,8 @@
 
 Reference: ``Models/multi_input_data_regression_opt_transformer_cnn_20250108.py:186-189`` (``XGBRegressor(n_estimators=300,
 learning_rate=0.01, max_depth=30, tree_method="hist")`` fitted on ``hstack([fingerprints, images])``) and the fitted model the
-repository ships, ``Models/xgb_model_maccs.pkl``.  Fitting stays with XGBoost (third-party CPU/GPU code, as in the reference);
-prediction over screening-scale libraries runs here.
+repository ships, ``Models/xgb_model_maccs.pkl``.  Prediction over screening-scale libraries runs here, from a model XGBoost fitted or
+from one ``bbbp_amd.xgb.XGBRegressor`` fitted on the GPU (its ``booster_`` is an ``XGBTrees``).
 
 The pickle holds the booster's raw model buffer (``Booster.save_raw``: UBJSON).  ``lift_raw_from_pickle`` takes that byte string
 out of the pickle stream with ``pickletools`` -- nothing is unpickled, no xgboost import -- and ``parse_ubjson`` /
@@ -15,7 +15,8 @@ CatBoost's JSON export (``model.save_model(path, format="json")``): oblivious tr
 
 PARITY UNPINNED: neither xgboost nor catboost is installed in the build image (and the reference ships no fitted CatBoost model), so outputs cannot be compared with the library's own
 ``predict``; the predict rule is XGBoost's published one (csrc/forest.hip) and the tests check the GPU path against the numpy
-restatement in ``oracle/reference_cpu.py`` only.
+restatement in ``oracle/reference_cpu.py`` only.  The same holds for fitting: ``bbbp_amd.xgb`` has never been compared with the package,
+and that XGBoost loads the JSON document ``XGBRegressor.get_model_json`` writes is unpinned too (``from_raw`` reads it back).
 """
 from __future__ import annotations
 

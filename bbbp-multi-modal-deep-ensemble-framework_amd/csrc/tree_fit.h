@@ -13,6 +13,9 @@
 // and the order of every addition is the kernel's (a float64 scan's result depends on it).  The tree walkers, the `choose` kernels and the
 // node tables are per file on purpose: they share a shape, not code.  iforest.hip (isolation trees, one work-group per tree, everything in
 // LDS) takes the scans for its segmented minimum / maximum, block_rank_before for its compaction and partition, make_leaf and the hash.
+// xgb.hip (histogram-boosted trees over byte features: one row list per problem instead of an order per feature, integer histograms instead
+// of float64 scans) takes Area, row_of and block_rank_before (the ranks of the splits and of the next level's slots in its `choose`); its
+// leaf stores are its own, XGBoost's node arrays being others than scikit-learn's.
 // Members of a struct that are selected by a run-time index or address go to scratch: layouts here are filled member by member.
 #pragma once
 #include "common.h"

@@ -697,6 +697,49 @@ int bbbp_gbt_staged_decision(void* stream, const float* X, long ld, int m, int d
                              const double* threshold, const double* value, const int* root, int n_trees, double init, double learning_rate,
                              const int* stages, int n_stages, double* out);
 
+/* ---- xgb fit: histogram-boosted regression trees, XGBoost's hist updater for reg:squarederror (csrc/xgb.hip) ---------------------
+ * XGBRegressor of the logBB stack (Models/multi_input_data_regression_opt_transformer_cnn_20250108.py:186-189).  bbbp_amd/xgb.py states
+ * the algorithm and composes XGBRegressor / fit_regressors from these.  A problem is one model being fitted.  Its features are bytes:
+ * bins[f][i] = the number of feature f's cuts <= x, cuts[f] padded with +infinity to cut_stride entries.  A tree t owns the node slots
+ * [t * capacity, t * capacity + tree_nodes[t]) of the seven node arrays; node ids are XGBoost's (the root 0, nodes expanded level by
+ * level in ascending id, each split appends its left and right child as the next two ids), children are tree-relative, -1 marks a leaf;
+ * cond is the split's threshold cuts[feature][bin] (a row goes left when x < cond, which is bin <= split bin) or the leaf's value
+ * float32((double)learning_rate * w); base_weight is w = -G / (H + lambda) in a split node and the leaf's value in a leaf; loss_change is
+ * the gain (0 in a leaf); sum_hessian the row count.  feature counts the columns of `bins`. */
+#define BBBP_XGB_FIT_MAX_N 8192
+#define BBBP_XGB_FIT_MAX_D 65536
+#define BBBP_XGB_FIT_MAX_DEPTH 1024
+#define BBBP_XGB_FIT_MAX_TREES 10000
+typedef struct bbbp_xgb_problem {
+    const uint8_t* bins;                       /* [d][n] */
+    const float* cuts;                         /* [d][cut_stride] */
+    const float* y;                            /* [n]: the targets rounded to float32 */
+    int n, d, cut_stride;
+    int n_estimators, max_depth;
+    int min_child_rows;                        /* max(1, ceil(min_child_weight)): the hessian of a row is 1 */
+    double reg_lambda, gamma;
+    float learning_rate, base_score;
+    void* work;                                /* bbbp_xgb_fit_work_bytes(n, d) bytes, 16-byte aligned; need not be initialised */
+    int* left; int* right; int* feature; float* cond; float* base_weight; float* loss_change; float* sum_hessian;      /* [n_estimators][capacity] */
+    int* tree_nodes;                           /* [n_estimators]; -1 from the first tree on in which an index left its array (a defect) */
+    float* margin;                             /* [n]: the training rows' margins after the last tree */
+} bbbp_xgb_problem;
+/* Node slots per tree, min(2 n - 1, 2^(max_depth + 1) - 1) (0 with a message outside the limits above). */
+int bbbp_xgb_fit_tree_capacity(int n, int max_depth);
+/* Bytes of a problem's `work` (0 with a message outside the limits above). */
+size_t bbbp_xgb_fit_work_bytes(int n, int d);
+/* bins[f][i] = the number of entries of cuts[f] that are <= XT[f][i], by binary search; XT is [d][n] float32 and finite. */
+int bbbp_xgb_bin(void* stream, const float* XT, int n, int d, const float* cuts, int cut_stride, uint8_t* bins);
+/* Fit every problem, all side by side: rounds of four launches, one tree level per round and problem, enqueued in blocks; between blocks
+ * the word `alive_device` is read (the only host read), and the call returns when no problem grows any more: the stream is then idle.
+ * `problems` is a host array, `problems_device` the same bytes in device memory.  A problem's numbers do not depend on what else is in
+ * the batch: every sum is an integer sum or has a fixed order. */
+int bbbp_xgb_fit(void* stream, const bbbp_xgb_problem* problems, const bbbp_xgb_problem* problems_device, int n_problems, int* alive_device);
+/* For tools/bench_xgb.py, per host thread: with the profile on, bbbp_xgb_fit puts every split launch between two events; bbbp_xgb_fit_last
+ * gives the last fit's sum of those times (0 with the profile off) and the number of launches it enqueued.  Returns the previous setting. */
+int bbbp_xgb_fit_profile(int enable);
+int bbbp_xgb_fit_last(double* split_ms, long* launches);
+
 /* ---- rf fit: random-forest classification trees fitted by exact split search (csrc/rf.hip) --------------------------------------
  * RandomForestClassifier and DecisionTreeClassifier of the classification stack (Models/model_opt_maccs.py:124-200): two classes, Gini,
  * bootstrap rows as integer weights, max_features candidate features per node.  bbbp_amd/random_forest.py composes the classifiers and

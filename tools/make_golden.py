@@ -243,6 +243,21 @@ def case_xgb_head(n_keep=6):
     print("xgb_maccs_head:", hi, "nodes of", int(root[-1]), "| tree 0 bytes", nxt - start)
 
 
+def case_xgb_stats(n_keep=6):
+    """What XGBoost recorded while it fitted the shipped model, for the same leading trees as ``xgb_maccs_head.npz``: per node the parent
+    (tree-relative, 2147483647 at a root), ``base_weights``, ``loss_changes`` and ``sum_hessian``, float32 as the model file holds them.
+    The yardstick of tests/test_xgb_cpu.py: the package's own numbers, read without the package."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from bbbp_amd import boosters
+    doc = boosters.parse_ubjson(boosters.lift_raw_from_pickle(os.path.join(REF, "Models", "xgb_model_maccs.pkl")))
+    trees = doc["Model"]["learner"]["gradient_booster"]["model"]["trees"][:n_keep]
+    cat = lambda key, dtype: np.concatenate([np.asarray(t[key], dtype) for t in trees])  # noqa: E731
+    out = dict(parents=cat("parents", np.int32), base_weights=cat("base_weights", np.float32), loss_changes=cat("loss_changes", np.float32),
+               sum_hessian=cat("sum_hessian", np.float32))
+    np.savez_compressed(os.path.join(OUT, "xgb_maccs_stats.npz"), **out)
+    print("xgb_maccs_stats:", len(out["parents"]), "nodes of", n_keep, "trees")
+
+
 def case_oof_f64():
     """The network column of the published fold loop (...20250113.py:147-266), all ten folds, by the FLOAT64 oracle: the yardstick for
     tests/test_gpu_training.py::test_out_of_fold_driver_and_stack_against_oracle_folds.  Per fold the REFERENCE class is constructed
@@ -432,6 +447,8 @@ def main():
     case_ops()
     if not only or "xgb_head" in only:
         case_xgb_head()
+    if not only or "xgb_stats" in only:
+        case_xgb_stats()
     if not only or "oof_f64" in only:
         case_oof_f64()
     if "b3db_oof" in only:                        # ~1 h of CPU: only on request
