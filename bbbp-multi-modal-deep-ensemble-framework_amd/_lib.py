@@ -133,6 +133,16 @@ class XgbProblem(Structure):
                 ("base_weight", c_void_p), ("loss_change", c_void_p), ("sum_hessian", c_void_p), ("tree_nodes", c_void_p), ("margin", c_void_p)]
 
 
+class EnsSource(Structure):
+    """bbbp_ens_source (include/bbbp_hip.h)."""
+    _fields_ = [("src", c_void_p), ("stride", c_long), ("col", c_long), ("rows", c_void_p), ("count", c_long), ("dst", c_long)]
+
+
+class EnsColumn(Structure):
+    """bbbp_ens_column (include/bbbp_hip.h)."""
+    _fields_ = [("src", c_void_p), ("stride", c_long), ("col", c_long)]
+
+
 _FP = c_void_p          # device float*
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -237,6 +247,9 @@ _SIGNATURES = {
     "bbbp_metrics_confusion": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "bbbp_metrics_auc_pairs": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "bbbp_metrics_sq_sums": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "bbbp_ens_meta_scatter": (c_int, [c_void_p, POINTER(EnsSource), c_void_p, c_int, POINTER(c_long), c_int, c_int, c_void_p, c_long]),
+    "bbbp_ens_soft_vote": (c_int, [c_void_p, POINTER(EnsColumn), c_void_p, c_int, c_void_p, c_double, c_int, c_void_p, c_void_p]),
+    "bbbp_ens_hard_vote": (c_int, [c_void_p, POINTER(EnsColumn), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "bbbp_graph_stats": (c_int, [POINTER(c_long), POINTER(c_long)]),
     "bbbp_conv_last_clock": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "bbbp_set_conv_winograd": (c_int, [c_int]),

@@ -41,7 +41,7 @@ import numbers
 import numpy as np
 import torch
 
-from . import _dense, _lib, _tree_host
+from . import _estimator, _dense, _lib, _tree_host
 from ._tree_host import Matrix as _Matrix, is_int as _is_int          # shared with random_forest: they live in _tree_host.py
 from .linear_model import _binary_targets
 
@@ -168,7 +168,7 @@ class _BoostedTrees:
         return out
 
 
-class GradientBoostingClassifier(_BoostedTrees):
+class GradientBoostingClassifier(_estimator.Params, _BoostedTrees):
     """``GradientBoostingClassifier(n_estimators=100, learning_rate=0.1, max_depth=3, min_samples_split=2, min_samples_leaf=1, *,
     device="cuda")``: scikit-learn's names for two classes and the log-loss.
 
@@ -191,22 +191,14 @@ class GradientBoostingClassifier(_BoostedTrees):
         self.min_samples_split, self.min_samples_leaf = int(min_samples_split), int(min_samples_leaf)
         self.random_state = random_state                 # accepted and unused: ties are broken by the fixed rule, not by a random order
 
+    _params = ("n_estimators", "learning_rate", "max_depth", "min_samples_split", "min_samples_leaf", "random_state", "device")
+
     # ---- fit --------------------------------------------------------------------------------------------------------
     def fit(self, X, y, sample_weight=None):
         who = "GradientBoostingClassifier"
         if sample_weight is not None:
             raise ValueError(f"{who}: sample_weight is not supported")
-        classes, t = _binary_targets(y, None, who)
-        X32 = _training_matrix32(X, who)
-        if X32.shape[0] != len(t):
-            raise ValueError(f"{who}: X has {X32.shape[0]} rows, y has {len(t)}")
-        with torch.cuda.device(self.device):
-            mat = _Matrix(X32, self.device)
-            chain = _Chain(mat, torch.from_numpy(t).to(self.device), _prior_logit(t), self.n_estimators, self.learning_rate, self.max_depth,
-                           self.min_samples_split, self.min_samples_leaf)
-            keep = _fit_chains([chain])
-            self._adopt(classes, chain)
-            del keep
+        _fit_classifiers([self], [(X, y)])
         return self
 
     def _adopt(self, classes, chain, n_estimators=None):
@@ -281,6 +273,27 @@ class GradientBoostingClassifier(_BoostedTrees):
         """Class labels as a numpy array of ``classes_``' dtype: ``classes_[1]`` where the decision value is >= 0 (scikit-learn's rule)."""
         Xq, _ = self._queries(X)
         return self.classes_[(self._staged(Xq, [self.n_estimators_])[0] >= 0).cpu().numpy().astype(np.intp)]
+
+
+def _fit_classifiers(classifiers, problems):
+    """Fit the chains of ``classifiers[i]`` over ``problems[i] = (X, y)`` in one ``bbbp_gbt_fit`` batch and every classifier from its own: what
+    ``fit`` does, for one or many (``ensemble`` fits a learner on all rows and on every fold's training rows this way).  Each classifier
+    equals its single ``fit`` bit for bit."""
+    who = "GradientBoostingClassifier"
+    checked = []
+    for X, y in problems:
+        classes, t = _binary_targets(y, None, who)
+        X32 = _training_matrix32(X, who)
+        if X32.shape[0] != len(t):
+            raise ValueError(f"{who}: X has {X32.shape[0]} rows, y has {len(t)}")
+        checked.append((classes, t, X32))
+    with torch.cuda.device(classifiers[0].device):
+        chains = [_Chain(_Matrix(X32, clf.device), torch.from_numpy(t).to(clf.device), _prior_logit(t), clf.n_estimators, clf.learning_rate, clf.max_depth,
+                         clf.min_samples_split, clf.min_samples_leaf) for clf, (_, t, X32) in zip(classifiers, checked)]
+        keep = _fit_chains(chains)
+        for clf, chain, (classes, _, _) in zip(classifiers, chains, checked):
+            clf._adopt(classes, chain)
+        del keep
 
 
 def grid_points(param_grid, who="gradient_boosting.grid_search_cv"):

@@ -28,7 +28,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _dense, _lib
+from . import _estimator, _dense, _lib
 
 SOLVERS = ("lbfgs", "newton-cholesky")
 MAX_FEATURES = 255                         # BBBP_LOGREG_MAX_D
@@ -143,7 +143,7 @@ def _evaluate(X, t, theta, C=1.0, fit_intercept=True, device="cuda"):
                 w=st[off[4]:off[4] + n].copy())
 
 
-class LogisticRegression:
+class LogisticRegression(_estimator.Params):
     """``LogisticRegression(C=1.0, tol=1e-4, max_iter=100, fit_intercept=True, penalty="l2", solver="lbfgs", *, device="cuda")``:
     scikit-learn's names for two classes.
 
@@ -171,20 +171,13 @@ class LogisticRegression:
         self.C, self.tol, self.max_iter, self.fit_intercept = float(C), float(tol), int(max_iter), bool(fit_intercept)
         self.penalty, self.solver = penalty, solver
 
+    _params = ("C", "tol", "max_iter", "fit_intercept", "penalty", "solver", "device")
+
     # ---- fit --------------------------------------------------------------------------------------------------------
     def fit(self, X, y, sample_weight=None):
         if sample_weight is not None:
             raise ValueError("LogisticRegression: sample weights are not supported")
-        classes, t = _binary_targets(y, None)
-        X, _ = _dense.to_device_matrix(X, self.device, "linear_model", allow_row_stride=True)
-        if X.shape[0] != len(t):
-            raise ValueError(f"LogisticRegression: X has {X.shape[0]} rows, y has {len(t)}")
-        _check_shape(X, "LogisticRegression")
-        with torch.cuda.device(self.device):
-            _check_finite(X, "the training set")
-            pr = _Problem(X, torch.from_numpy(t).to(self.device), self.C, self.tol, self.max_iter, self.fit_intercept)
-            (n_iter, status), = _solve([pr])
-            self._adopt(classes, pr, n_iter, status)
+        _fit_classifiers([self], [(X, y)])
         return self
 
     def _adopt(self, classes, pr, n_iter, status):
@@ -244,6 +237,27 @@ class LogisticRegression:
         """Class labels as a numpy array of ``classes_``' dtype (labels need not be numbers, so they stay on the host)."""
         Xq, _ = self._queries(X)
         return self.classes_[(self._decision(Xq) > 0).cpu().numpy().astype(np.intp)]
+
+
+def _fit_classifiers(classifiers, problems):
+    """Solve ``classifiers[i]`` over ``problems[i] = (X, y)`` in one ``_solve`` batch and fit every classifier from its own problem: what
+    ``fit`` does, for one or many (``ensemble`` fits a learner on all rows and on every fold's training rows this way).  Each classifier
+    equals its single ``fit`` bit for bit."""
+    checked = []
+    for clf, (X, y) in zip(classifiers, problems):
+        classes, t = _binary_targets(y, None)
+        X, _ = _dense.to_device_matrix(X, clf.device, "linear_model", allow_row_stride=True)
+        if X.shape[0] != len(t):
+            raise ValueError(f"LogisticRegression: X has {X.shape[0]} rows, y has {len(t)}")
+        _check_shape(X, "LogisticRegression")
+        checked.append((classes, t, X))
+    with torch.cuda.device(classifiers[0].device):
+        solving = []
+        for clf, (_, t, X) in zip(classifiers, checked):
+            _check_finite(X, "the training set")
+            solving.append(_Problem(X, torch.from_numpy(t).to(clf.device), clf.C, clf.tol, clf.max_iter, clf.fit_intercept))
+        for clf, pr, (classes, _, _), (n_iter, status) in zip(classifiers, solving, checked, _solve(solving)):
+            clf._adopt(classes, pr, n_iter, status)
 
 
 def grid_search_cv(X, y, param_grid, cv: int = 5, device="cuda", *, tol=1e-4, max_iter=100):

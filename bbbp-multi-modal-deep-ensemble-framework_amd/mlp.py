@@ -20,7 +20,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _estimator, _lib, ops
 
 _ACT = {"relu": 0, "tanh": 1}
 
@@ -71,14 +71,16 @@ class GridMLPTrainer:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("GridMLPTrainer needs a GPU (no CPU fallback)")
-        X = np.ascontiguousarray(X, dtype=np.float64)
+        on_device = isinstance(X, torch.Tensor) and X.is_cuda      # a CUDA tensor stays where it is (ensemble: one upload for all learners);
+        if not on_device:                                           # whatever else numpy can read, a CPU tensor included, goes the way it always went
+            X = np.ascontiguousarray(X, dtype=np.float64)
         y = np.ascontiguousarray(y, dtype=np.float64)
-        if X.ndim != 2 or y.shape != (X.shape[0],):
-            raise ValueError(f"X must be [n, features] and y [n]; got {X.shape} and {y.shape}")
+        if len(X.shape) != 2 or y.shape != (X.shape[0],):
+            raise ValueError(f"X must be [n, features] and y [n]; got {tuple(X.shape)} and {y.shape}")
         if not np.isin(y, (0.0, 1.0)).all():
             raise ValueError("y must be binary {0, 1} (binarise labels first, as MLPClassifier does)")
-        self.n, self.n_features = X.shape
-        self.X = torch.from_numpy(X).to(self.device)
+        self.n, self.n_features = (int(v) for v in X.shape)
+        self.X = X.to(self.device, torch.float64).contiguous() if on_device else torch.from_numpy(X).to(self.device)
         self.y = torch.from_numpy(y).to(self.device)
         self._models_dev = None
         self._keep = []
@@ -257,14 +259,20 @@ class GridMLPTrainer:
     def _predict(self, index: int, X) -> np.ndarray:
         if self._models_dev is None:
             raise RuntimeError("predict before fit")
-        Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(self.device)
+        return self._predict_device(index, torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(self.device)).cpu().numpy()
+
+    def _predict_device(self, index: int, Xd):
+        """P(class 1) of fit ``index`` for the float64 device rows ``Xd``: float64 [m] on the device."""
+        if self._models_dev is None:
+            raise RuntimeError("predict before fit")
         if Xd.dim() != 2 or Xd.shape[1] != self.n_features:
             raise ValueError(f"X must be [n, {self.n_features}]")
+        Xd = Xd.to(self.device, torch.float64).contiguous()
         out = torch.empty(Xd.shape[0], dtype=torch.float64, device=self.device)
         max_units = max(self._keep[index]["units"][1:])
         _lib.check(_lib.lib().bbbp_mlp_predict_proba(ops._stream(), self._models_dev.data_ptr(), self._keep[index]["slot"], Xd.data_ptr(), Xd.shape[0],
                                                      self.n_features, max_units, out.data_ptr()), "bbbp_mlp_predict_proba")
-        return out.cpu().numpy()
+        return out
 
 
 def grid_search_cv(X, y, param_grid: dict, cv: int = 5, base: Optional[MLPConfig] = None, device="cuda", random_state: int = 0):
@@ -292,3 +300,135 @@ def grid_search_cv(X, y, param_grid: dict, cv: int = 5, base: Optional[MLPConfig
         scores.append(float(np.mean(f1)))
     best = int(np.argmax(scores))
     return points[best], scores, fitted
+
+
+# ---- the estimator: one fit of the trainer with scikit-learn's MLPClassifier surface -------------------------------------------------------
+_MLP_DEFAULTS = dict(learning_rate="constant", power_t=0.5, shuffle=True, verbose=False, warm_start=False, momentum=0.9, nesterovs_momentum=True,
+                     early_stopping=False, validation_fraction=0.1, beta_1=0.9, beta_2=0.999, epsilon=1e-8, max_fun=15000)
+
+
+class MLPClassifier(_estimator.Params):
+    """``MLPClassifier(hidden_layer_sizes=(100,), activation="relu", *, solver="adam", alpha=1e-4, batch_size="auto",
+    learning_rate_init=0.001, max_iter=200, tol=1e-4, n_iter_no_change=10, random_state=0, device="cuda")``: scikit-learn's names for two
+    classes, a thin estimator over ``GridMLPTrainer`` with one ``MLPConfig``.
+
+    ``fit`` takes a numpy array or a CUDA tensor [n, d] (trained in float64) and labels with two distinct values; ``classes_[1]`` is the
+    positive class.  ``batch_size="auto"`` is ``min(200, n)``.  It sets ``classes_``, ``coefs_``, ``intercepts_``, ``n_iter_``, ``loss_``,
+    ``best_loss_``, ``loss_curve_`` and ``n_features_in_``.  ``predict_proba`` returns float64 [m, 2] as ``[1 - p, p]`` (numpy for numpy
+    input, a CUDA tensor for a CUDA tensor); ``predict`` returns numpy labels, ``classes_[1]`` where ``p > 0.5``.  ``get_params`` /
+    ``set_params`` make the estimator clonable, so ``ensemble.StackingClassifier`` takes it as a base learner.
+    A fitted estimator predicts through the trainer that fitted it and keeps it: the trainer's float64 copy of the training matrix, and
+    the models fitted beside it in the same batch (``ensemble`` fits six at once), stay on the device for the estimator's lifetime.
+
+    Refused by name, being what the trainer does not implement: solvers other than ``"adam"``, activations other than ``"relu"`` and
+    ``"tanh"``, more than three hidden layers or 256 units in one, ``early_stopping``, ``warm_start``, ``shuffle=False``, other values of
+    ``beta_1``, ``beta_2``, ``epsilon``, a ``random_state`` that is not an int (the seed is part of the model), ``sample_weight``,
+    ``partial_fit``, more than two classes, a device other than CUDA."""
+
+    _who = "MLPClassifier"
+    _params = ("hidden_layer_sizes", "activation", "solver", "alpha", "batch_size", "learning_rate_init", "max_iter", "tol", "n_iter_no_change",
+               "random_state", "device")
+
+    def __init__(self, hidden_layer_sizes=(100,), activation="relu", *, solver="adam", alpha=1e-4, batch_size="auto", learning_rate_init=0.001,
+                 max_iter=200, tol=1e-4, n_iter_no_change=10, random_state=0, device="cuda", **other):
+        from . import _tree_host
+        who = self._who
+        _tree_host.refuse_non_defaults(who, other, _MLP_DEFAULTS)
+        if solver != "adam":
+            raise NotImplementedError(f"{who}: solver={solver!r} is not supported (only 'adam')")
+        if activation not in _ACT:
+            raise NotImplementedError(f"{who}: activation={activation!r} is not supported (only {sorted(_ACT)})")
+        hidden = [hidden_layer_sizes] if _tree_host.is_int(hidden_layer_sizes) else list(hidden_layer_sizes)
+        if not all(_tree_host.is_int(h) for h in hidden) or not 1 <= len(hidden) <= 3 or min(hidden) < 1 or max(hidden) > 256:
+            raise NotImplementedError(f"{who}: hidden_layer_sizes={hidden_layer_sizes!r} is not supported (1 to 3 hidden layers of 1 to 256 units)")
+        if not (batch_size == "auto" if isinstance(batch_size, str) else (_tree_host.is_int(batch_size) and batch_size >= 1)):
+            raise ValueError(f"{who}: batch_size must be 'auto' or an int >= 1, got {batch_size!r}")
+        for name, value, low in (("alpha", alpha, 0.0), ("learning_rate_init", learning_rate_init, None), ("tol", tol, 0.0)):
+            ok = isinstance(value, (int, float, np.integer, np.floating)) and not isinstance(value, bool) and np.isfinite(value)
+            if not ok or (value <= 0.0 if low is None else value < low):
+                raise ValueError(f"{who}: {name} must be a finite number {'> 0' if low is None else '>= 0'}, got {value!r}")
+        for name, value in (("max_iter", max_iter), ("n_iter_no_change", n_iter_no_change)):
+            if not _tree_host.is_int(value) or value < 1:
+                raise ValueError(f"{who}: {name} must be an int >= 1, got {value!r}")
+        if not _tree_host.is_int(random_state) or not 0 <= random_state < 2 ** 32:
+            raise NotImplementedError(f"{who}: random_state must be an int in [0, 2^32) (the seed is part of the model), got {random_state!r}")
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"{who}: device {device!r}: the fits run on the GPU (no CPU fallback)")
+        # the parameters are kept as they were given, so that a clone is made of the same values
+        self.hidden_layer_sizes, self.activation, self.solver, self.alpha, self.batch_size = hidden_layer_sizes, activation, solver, alpha, batch_size
+        self.learning_rate_init, self.max_iter, self.tol, self.n_iter_no_change = learning_rate_init, max_iter, tol, n_iter_no_change
+        self.random_state, self.device = random_state, device
+
+    # ---- fit --------------------------------------------------------------------------------------------------------
+    def _config(self, n_train, train_rows=None):
+        from . import _tree_host
+        hidden = [self.hidden_layer_sizes] if _tree_host.is_int(self.hidden_layer_sizes) else list(self.hidden_layer_sizes)
+        bs = min(200, n_train) if isinstance(self.batch_size, str) else int(self.batch_size)
+        return MLPConfig(hidden_layer_sizes=tuple(int(h) for h in hidden), activation=self.activation, learning_rate_init=float(self.learning_rate_init),
+                         batch_size=bs, alpha=float(self.alpha), max_iter=int(self.max_iter), tol=float(self.tol),
+                         n_iter_no_change=int(self.n_iter_no_change), random_state=int(self.random_state), train_rows=train_rows)
+
+    @staticmethod
+    def _fit_rows(clones, X, y, row_sets):
+        """Fit ``clones[i]`` on the rows ``row_sets[i]`` (None: all) of ``X`` (numpy or a CUDA tensor) and ``y``: one trainer, one batch of
+        fits, the rows gathered by the kernel (``MLPConfig.train_rows``).  Each fit equals the single ``fit`` on those rows."""
+        from .linear_model import _binary_targets
+        who = clones[0]._who
+        if isinstance(y, torch.Tensor):
+            y = y.detach().cpu().numpy()
+        y = np.asarray(y)
+        if len(X.shape) != 2 or X.shape[0] != len(y):
+            raise ValueError(f"{who}: X must be [n, d] with one label per row, got {tuple(X.shape)} and {len(y)} labels")
+        classes, t_all = _binary_targets(y, None, who)
+        configs = []
+        for c, rows in zip(clones, row_sets):
+            rows = None if rows is None else np.asarray(rows, dtype=np.int64)
+            # one label vector serves every fit: a row set must hold both classes of all rows
+            if rows is not None and not np.array_equal(np.unique(y[rows]), classes):
+                raise ValueError(f"{who}: a row set's classes {np.unique(y[rows])!r} differ from those of all rows {classes!r}")
+            configs.append(c._config(len(y) if rows is None else len(rows), rows))
+        trainer = GridMLPTrainer(X, t_all, device=clones[0].device)
+        for c, fitted in zip(clones, trainer.fit(configs)):
+            c._adopt(classes, fitted, int(X.shape[1]))
+        return clones
+
+    def fit(self, X, y, sample_weight=None):
+        if sample_weight is not None:
+            raise NotImplementedError(f"{self._who}: sample_weight is not supported")
+        self._fit_rows([self], X, y, [None])
+        return self
+
+    def partial_fit(self, X, y, classes=None):
+        raise NotImplementedError(f"{self._who}: partial_fit is not supported")
+
+    def _adopt(self, classes, fitted, n_features):
+        self.classes_, self._fitted, self.n_features_in_ = classes, fitted, n_features
+        self.coefs_, self.intercepts_, self.n_iter_ = fitted.coefs_, fitted.intercepts_, fitted.n_iter_
+        self.loss_, self.best_loss_, self.loss_curve_ = fitted.loss_, fitted.best_loss_, fitted.loss_curve_
+        self.n_layers_, self.out_activation_ = len(fitted.coefs_) + 1, "logistic"
+
+    # ---- prediction -------------------------------------------------------------------------------------------------
+    def _p1(self, X):
+        """(P(classes_[1]) float64 [m] on the device, was_numpy)."""
+        if not hasattr(self, "_fitted"):
+            raise RuntimeError(f"{self._who}: not fitted")
+        was_numpy = not isinstance(X, torch.Tensor)
+        trainer = self._fitted._trainer
+        if was_numpy:
+            X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64))
+        elif not X.is_cuda:
+            raise RuntimeError(f"{self._who}: expected a CUDA (HIP) tensor or a numpy array, got a tensor on {X.device} (no CPU fallback)")
+        if X.dim() != 2 or X.shape[1] != self.n_features_in_:
+            raise ValueError(f"{self._who}: the queries must be [m, {self.n_features_in_}], got shape {tuple(X.shape)}")
+        with torch.cuda.device(trainer.device):
+            return trainer._predict_device(self._fitted._index, X.to(trainer.device)), was_numpy
+
+    def predict_proba(self, X):
+        p, was_numpy = self._p1(X)
+        out = torch.stack([1.0 - p, p], dim=1)
+        return out.cpu().numpy() if was_numpy else out
+
+    def predict(self, X):
+        """Class labels as a numpy array of ``classes_``' dtype: ``classes_[1]`` where P(``classes_[1]``) > 0.5 (scikit-learn's rule)."""
+        p, _ = self._p1(X)
+        return self.classes_[(p > 0.5).cpu().numpy().astype(np.intp)]

@@ -24,7 +24,7 @@ import numbers
 import numpy as np
 import torch
 
-from . import _dense, _lib
+from . import _estimator, _dense, _lib
 
 MAX_NEIGHBORS = 32
 MAX_CLASSES = 32
@@ -147,7 +147,7 @@ class NearestNeighbors:
         return (dist, ind) if return_distance else ind
 
 
-class KNeighborsClassifier(NearestNeighbors):
+class KNeighborsClassifier(_estimator.Params, NearestNeighbors):
     """``KNeighborsClassifier(n_neighbors=5, *, weights="uniform", device="cuda")``.
 
     ``fit(X, y)`` maps the labels (any sortable values, at most 32 distinct) to ids as ``numpy.unique`` does (``classes_``).
@@ -161,6 +161,8 @@ class KNeighborsClassifier(NearestNeighbors):
             raise ValueError(f"KNeighborsClassifier: weights must be 'uniform' or 'distance', got {weights!r}")
         super().__init__(n_neighbors, device=device)
         self.weights = weights
+
+    _params = ("n_neighbors", "weights", "device")
 
     def fit(self, X, y):
         y = np.asarray(y)

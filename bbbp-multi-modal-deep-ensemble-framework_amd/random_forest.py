@@ -48,7 +48,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _dense, _lib, _tree_host
+from . import _estimator, _dense, _lib, _tree_host
 from ._tree_host import Matrix as _Matrix, is_int as _is_int          # shared with gradient_boosting: they live in _tree_host.py
 from .linear_model import _binary_targets
 
@@ -234,7 +234,7 @@ def _flat_sklearn(fitted, value_columns, who):
     return _tree_host.sklearn_trees(ests, value_columns, who + ": ") + (len(ests),)
 
 
-class RandomForestClassifier:
+class RandomForestClassifier(_estimator.Params):
     """``RandomForestClassifier(n_estimators=100, *, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features="sqrt",
     bootstrap=True, random_state=0, device="cuda")``: scikit-learn's names for two classes and the Gini criterion.
 
@@ -261,22 +261,13 @@ class RandomForestClassifier:
         self.min_samples_split, self.min_samples_leaf, self.max_features = int(min_samples_split), int(min_samples_leaf), max_features
         self.bootstrap, self.random_state = bool(bootstrap), int(random_state)
 
+    _params = ("n_estimators", "max_depth", "min_samples_split", "min_samples_leaf", "max_features", "bootstrap", "random_state", "device")
+
     # ---- fit --------------------------------------------------------------------------------------------------------
     def fit(self, X, y, sample_weight=None):
-        who = self._who
         if sample_weight is not None:
-            raise NotImplementedError(f"{who}: sample_weight is not supported")
-        classes, t = _binary_targets(y, None, who)
-        X32 = _training_matrix32(X, who)
-        if X32.shape[0] != len(t):
-            raise ValueError(f"{who}: X has {X32.shape[0]} rows, y has {len(t)}")
-        mf = _resolve_max_features(self.max_features, X32.shape[1], who)
-        with torch.cuda.device(self.device):
-            mat = _Matrix(X32, self.device)
-            spec = _Spec(mat, torch.from_numpy(t).to(self.device), self.n_estimators, self.max_depth, self.min_samples_split, self.min_samples_leaf, mf,
-                         self.bootstrap, self.random_state)
-            _grow([spec])
-            self._adopt(classes, spec)
+            raise NotImplementedError(f"{self._who}: sample_weight is not supported")
+        _fit_classifiers([self], [(X, y)])
         return self
 
     def _adopt(self, classes, spec, limits=None):
@@ -361,11 +352,32 @@ class DecisionTreeClassifier(RandomForestClassifier):
     random_state=0, device="cuda")``: the same fit with one tree, every row once and all features at every node."""
 
     _who = "DecisionTreeClassifier"
+    _params = RandomForestClassifier._params[1:]
 
     def __init__(self, *, max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features=None, bootstrap=False, random_state=0, device="cuda",
                  **other):
         super().__init__(1, max_depth=max_depth, min_samples_split=min_samples_split, min_samples_leaf=min_samples_leaf, max_features=max_features,
                          bootstrap=bootstrap, random_state=random_state, device=device, **other)
+
+
+def _fit_classifiers(classifiers, problems):
+    """Grow the forests of ``classifiers[i]`` over ``problems[i] = (X, y)`` in one ``_grow`` call and fit every classifier from its own: what
+    ``fit`` does, for one or many (``ensemble`` fits a learner on all rows and on every fold's training rows this way).  Each classifier
+    equals its single ``fit`` bit for bit."""
+    checked = []
+    for clf, (X, y) in zip(classifiers, problems):
+        who = clf._who
+        classes, t = _binary_targets(y, None, who)
+        X32 = _training_matrix32(X, who)
+        if X32.shape[0] != len(t):
+            raise ValueError(f"{who}: X has {X32.shape[0]} rows, y has {len(t)}")
+        checked.append((classes, t, X32, _resolve_max_features(clf.max_features, X32.shape[1], who)))
+    with torch.cuda.device(classifiers[0].device):
+        specs = [_Spec(_Matrix(X32, clf.device), torch.from_numpy(t).to(clf.device), clf.n_estimators, clf.max_depth, clf.min_samples_split,
+                       clf.min_samples_leaf, mf, clf.bootstrap, clf.random_state) for clf, (_, t, X32, mf) in zip(classifiers, checked)]
+        _grow(specs)
+        for clf, spec, (classes, _, _, _) in zip(classifiers, specs, checked):
+            clf._adopt(classes, spec)
 
 
 def grid_points(param_grid, who="random_forest.grid_search_cv"):

@@ -45,7 +45,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _dense, _lib
+from . import _dense, _estimator, _lib
 
 KERNELS = {"linear": 0, "rbf": 1}          # BBBP_SVM_LINEAR / BBBP_SVM_RBF
 ITERS_PER_LAUNCH = 2000                    # iterations per problem and launch up to ITERS_REFERENCE_N rows: DESIGN.md gives the measured time of one
@@ -201,7 +201,7 @@ def _decision(model, dev, Xq, slices=0):
     return out
 
 
-class SVC:
+class SVC(_estimator.Params):
     """``SVC(C=1.0, kernel="rbf", gamma="scale", tol=1e-3, max_iter=-1, *, device="cuda")``: scikit-learn's names for two classes.
 
     ``fit`` takes a CUDA tensor or a numpy array, float32 or float64, [n, d], and labels of any sortable kind with two distinct values.
@@ -224,6 +224,8 @@ class SVC:
         if self.device.type != "cuda":
             raise RuntimeError(f"SVC: device {device!r}: the solver runs on the GPU (no CPU fallback)")
         self.C, self.kernel, self.gamma, self.tol, self.max_iter = float(C), kernel, gamma, float(tol), int(max_iter)
+
+    _params = ("C", "kernel", "gamma", "tol", "max_iter", "device")
 
     # ---- fit --------------------------------------------------------------------------------------------------------
     def fit(self, X, y):

@@ -925,6 +925,45 @@ int bbbp_metrics_auc_pairs(void* stream, const void* score, int dtype, long ld, 
 int bbbp_metrics_sq_sums(void* stream, const void* pred, int dtype, long ld, int n_columns, int n, const double* y, const int* seg,
                          int n_groups, double* sse, double* ystat, int* flag);
 
+/* ---- the classifier stack's device glue (csrc/ensemble.hip) ---------------------------------------------------------------------------------
+ * StackingClassifier(estimators, final_estimator=GradientBoostingClassifier(...), cv=5) and VotingClassifier(estimators, voting='soft') of the
+ * classification scripts (Models/model_opt.py:208-222).  bbbp_amd/ensemble.py composes the two estimators from the base learners' fits and
+ * these three entries, each one launch however many estimators and folds there are, each pinned bit for bit to tests/ensemble_numpy.py.
+ * Every table exists twice: the host's copy, which the entry validates before the launch, and the same bytes on the device, which the kernel
+ * reads; the caller keeps both, and what they point to, alive until the kernel is done.  Sources have unit inner stride inside a row, any
+ * row stride (in elements) and any base alignment of their element type. */
+#define BBBP_ENS_MAX_ENTRIES 65535       /* (estimator, fold) entries of one scatter */
+#define BBBP_ENS_MAX_ESTIMATORS 65535    /* columns of one vote */
+typedef struct bbbp_ens_source {
+    const double* src;   /* device: element (i, col) at src[i * stride + col] */
+    long stride, col;    /* stride >= col + 1 */
+    const long* rows;    /* device: the destination row of every source row, count ids; NULL: row i goes to row i */
+    long count;          /* source rows */
+    long dst;            /* destination column in [0, n_columns) */
+} bbbp_ens_source;
+typedef struct bbbp_ens_column {
+    const void* src;     /* device: doubles (soft vote: the pair at columns col, col + 1) or bytes (hard vote: the 0 / 1 prediction at col) */
+    long stride, col;    /* stride >= col + 2 (soft vote), col + 1 (hard vote) */
+} bbbp_ens_column;
+/* meta[rows[i]][dst] = src[i * stride + col] for every entry and i < count; meta [n][n_columns] float64 with row stride ld.  Nothing is
+ * cleared and nothing is added: the entries of one destination column must write every one of its n rows exactly once (a fold's test rows
+ * partition the rows), which is checked here on rows_host, the host's copy of the row ids of all entries that have some, concatenated in
+ * entry order (NULL when no entry has row ids); a row id outside [0, n), a cell written twice or never is BBBP_ERR_ARG.  The kernel has no
+ * bounds check of its own.  n = 0 is a no-op. */
+int bbbp_ens_meta_scatter(void* stream, const bbbp_ens_source* table, const void* table_dev, int n_entries, const long* rows_host, int n,
+                          int n_columns, double* meta, long ld);
+/* np.average of n_estimators probability pairs per row over the estimator axis: s = P_0 (* w_0), s = s + P_j (* w_j) in estimator order,
+ * out[i] = s / scl; without weights (NULL; device array of n_estimators doubles otherwise) out[i] = s / n_estimators and scl is not read.
+ * scl is the sum of the weights as the caller's numpy forms it (pairwise from eight on).  Every product, sum and quotient is rounded once,
+ * nothing is fused.  out [m][2] float64 dense; label [m] bytes: 1 when the second average is the first maximum (numpy's argmax, a NaN
+ * counting as a maximum), else 0.  m = 0 is a no-op. */
+int bbbp_ens_soft_vote(void* stream, const bbbp_ens_column* cols, const void* cols_dev, int n_estimators, const double* weights, double scl,
+                       int m, double* out, unsigned char* label);
+/* np.bincount(predictions, weights=) per row: counts[i][k] = sum over j in estimator order of w_j (1.0 without weights) where the byte of
+ * estimator j is k (any non-zero byte is 1), added in float64 from 0.0; label as for the soft vote: ties go to class 0.  m = 0 is a no-op. */
+int bbbp_ens_hard_vote(void* stream, const bbbp_ens_column* cols, const void* cols_dev, int n_estimators, const double* weights, int m,
+                       double* counts, unsigned char* label);
+
 /* ---- optional per-section timing (HIP events on the launch stream; used by bench.py's roofline leg) ----
  * enable(1), run steps, synchronise the stream, collect(ms_sum[n], count[n]) with n = num_sections(). */
 int bbbp_set_partition(int reserved_cus, size_t small_lds_pad);   /* CU partition knob, see csrc/common.h */
