@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_uint8, c_uint64, c_void_p)
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BBBP_LIB", os.path.join(_HERE, "libbbbp_hip.so"))    # BBBP_LIB: A/B another build
@@ -133,6 +133,15 @@ class XgbProblem(Structure):
                 ("base_weight", c_void_p), ("loss_change", c_void_p), ("sum_hessian", c_void_p), ("tree_nodes", c_void_p), ("margin", c_void_p)]
 
 
+class XgbcProblem(Structure):
+    """bbbp_xgbc_problem (include/bbbp_hip.h)."""
+    _fields_ = [("bins", c_void_p), ("cuts", c_void_p), ("y", c_void_p), ("n", c_int), ("d", c_int), ("cut_stride", c_int), ("n_estimators", c_int),
+                ("max_depth", c_int), ("subsample_threshold", c_uint32), ("reg_lambda", c_double), ("gamma", c_double), ("min_child_weight", c_double),
+                ("learning_rate", c_float), ("base_margin", c_float), ("seed", c_uint64), ("col_mask", c_void_p), ("col_mask_stride", c_int),
+                ("work", c_void_p), ("left", c_void_p), ("right", c_void_p), ("feature", c_void_p), ("cond", c_void_p), ("base_weight", c_void_p),
+                ("loss_change", c_void_p), ("sum_hessian", c_void_p), ("tree_nodes", c_void_p), ("margin", c_void_p)]
+
+
 class EnsSource(Structure):
     """bbbp_ens_source (include/bbbp_hip.h)."""
     _fields_ = [("src", c_void_p), ("stride", c_long), ("col", c_long), ("rows", c_void_p), ("count", c_long), ("dst", c_long)]
@@ -223,6 +232,10 @@ _SIGNATURES = {
     "bbbp_xgb_fit": (c_int, [c_void_p, POINTER(XgbProblem), c_void_p, c_int, c_void_p]),
     "bbbp_xgb_fit_profile": (c_int, [c_int]),
     "bbbp_xgb_fit_last": (c_int, [POINTER(c_double), POINTER(c_long)]),
+    "bbbp_xgbc_fit_tree_capacity": (c_int, [c_int, c_int]),
+    "bbbp_xgbc_fit_work_bytes": (c_size_t, [c_int, c_int]),
+    "bbbp_xgbc_fit": (c_int, [c_void_p, POINTER(XgbcProblem), c_void_p, c_int, c_void_p]),
+    "bbbp_xgbc_proba": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
     "bbbp_rf_fit_tree_capacity": (c_int, [c_int]),
     "bbbp_rf_fit_work_bytes": (c_size_t, [c_int, c_int, c_int]),
     "bbbp_rf_hash": (c_uint64, [c_uint64, c_uint64]),

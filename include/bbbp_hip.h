@@ -740,6 +740,42 @@ int bbbp_xgb_fit(void* stream, const bbbp_xgb_problem* problems, const bbbp_xgb_
 int bbbp_xgb_fit_profile(int enable);
 int bbbp_xgb_fit_last(double* split_ms, long* launches);
 
+/* ---- xgbc fit: histogram-boosted classification trees, XGBoost's hist updater for binary:logistic (csrc/xgbc.hip) -------------------
+ * XGBClassifier of the classification stack (Models/model_opt_20250130.py:445-456).  bbbp_amd/xgb.py states the algorithm and composes
+ * XGBClassifier / fit_classifiers / randomized_search_cv from these.  Everything is bbbp_xgb_fit's -- the byte features (bbbp_xgb_bin makes
+ * them), the node arrays, the ids, the limits BBBP_XGB_FIT_MAX_* -- but: y holds the targets 0.0 / 1.0; a row's gradient and hessian are
+ * p - y and p (1 - p) in float32 with p = sigmoid32(margin), a float32 sigmoid made of IEEE float64 operations only; a node's hessian
+ * sum is H = 2^-48 R with R the exact integer sum of max(1, llrint(h 2^48)), and sum_hessian records (float)H; a boundary is a candidate
+ * iff either side holds a row, R >= 1 and H >= min_child_weight; a child is searched iff it has two rows.  With subsample_threshold != 0
+ * tree t uses row i (its position in the problem) iff the high 32 bits of mix(mix(mix(seed + 0x9E3779B97F4A7C15) + t) + i) are below the
+ * threshold (mix: the splitmix64 finaliser); the other rows have gradient and hessian 0 in that tree and still take their leaf's value; a
+ * node without a used row is a leaf of weight -0.0.  With col_mask, tree t may split on feature f iff bit f % 32 of
+ * col_mask[t * col_mask_stride + f / 32] is set. */
+typedef struct bbbp_xgbc_problem {
+    const uint8_t* bins;                       /* [d][n] */
+    const float* cuts;                         /* [d][cut_stride] */
+    const float* y;                            /* [n]: 0.0 / 1.0 */
+    int n, d, cut_stride;
+    int n_estimators, max_depth;
+    uint32_t subsample_threshold;              /* floor(subsample 2^32); 0: every row is used */
+    double reg_lambda, gamma, min_child_weight;
+    float learning_rate, base_margin;          /* base_margin: the margin every row starts from */
+    uint64_t seed;
+    const uint32_t* col_mask;                  /* [n_estimators][col_mask_stride], or null: every feature is eligible */
+    int col_mask_stride;                       /* >= ceil(d / 32) */
+    void* work;                                /* bbbp_xgbc_fit_work_bytes(n, d) bytes, 16-byte aligned; need not be initialised */
+    int* left; int* right; int* feature; float* cond; float* base_weight; float* loss_change; float* sum_hessian;      /* [n_estimators][capacity] */
+    int* tree_nodes;                           /* [n_estimators]; -1 from the first tree on in which an index left its array (a defect) */
+    float* margin;                             /* [n]: the training rows' margins after the last tree */
+} bbbp_xgbc_problem;
+/* Node slots per tree and bytes of a problem's `work`, as for bbbp_xgb_fit (0 with a message outside the limits). */
+int bbbp_xgbc_fit_tree_capacity(int n, int max_depth);
+size_t bbbp_xgbc_fit_work_bytes(int n, int d);
+/* Fit every problem, all side by side, in bbbp_xgb_fit's rounds; a problem's numbers do not depend on what else is in the batch. */
+int bbbp_xgbc_fit(void* stream, const bbbp_xgbc_problem* problems, const bbbp_xgbc_problem* problems_device, int n_problems, int* alive_device);
+/* proba [m][2] float32: proba[i][1] = sigmoid32(margin[i]), proba[i][0] = 1 - proba[i][1] in float32. */
+int bbbp_xgbc_proba(void* stream, const float* margin, long m, float* proba);
+
 /* ---- rf fit: random-forest classification trees fitted by exact split search (csrc/rf.hip) --------------------------------------
  * RandomForestClassifier and DecisionTreeClassifier of the classification stack (Models/model_opt_maccs.py:124-200): two classes, Gini,
  * bootstrap rows as integer weights, max_features candidate features per node.  bbbp_amd/random_forest.py composes the classifiers and
