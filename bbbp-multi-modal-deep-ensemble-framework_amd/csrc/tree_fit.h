@@ -15,7 +15,9 @@
 // LDS) takes the scans for its segmented minimum / maximum, block_rank_before for its compaction and partition, make_leaf and the hash.
 // xgb.hip (histogram-boosted trees over byte features: one row list per problem instead of an order per feature, integer histograms instead
 // of float64 scans) takes Area, row_of and block_rank_before (the ranks of the splits and of the next level's slots in its `choose`); its
-// leaf stores are its own, XGBoost's node arrays being others than scikit-learn's.
+// leaf stores are its own, XGBoost's node arrays being others than scikit-learn's.  cat.hip (boosted symmetric trees over the same byte
+// features: one split per level for all parts, a part table instead of nodes) takes Area, row_of and block_rank_before (the compaction of
+// the children that hold a row in its `partition`).
 // Members of a struct that are selected by a run-time index or address go to scratch: layouts here are filled member by member.
 #pragma once
 #include "common.h"

@@ -776,6 +776,42 @@ int bbbp_xgbc_fit(void* stream, const bbbp_xgbc_problem* problems, const bbbp_xg
 /* proba [m][2] float32: proba[i][1] = sigmoid32(margin[i]), proba[i][0] = 1 - proba[i][1] in float32. */
 int bbbp_xgbc_proba(void* stream, const float* margin, long m, float* proba);
 
+/* ---- cat fit: boosted oblivious (symmetric) regression trees, CatBoost's Plain boosting for RMSE (csrc/cat.hip) ----------------------
+ * CatBoostRegressor of the logBB stack (Models/multi_input_data_regression_opt_transformer_cnn_20250108.py:192-195).  bbbp_amd/cat.py
+ * states the algorithm and composes CatBoostRegressor / fit_regressors from these.  A problem is one model being fitted.  Its features are
+ * bbbp_xgb_bin's bytes; candidate (f, c), c < n_cuts[f], sends a row right iff bins[f][i] > c.  Tree t owns split_feature / split_bin
+ * [t * depth, t * depth + tree_depth[t]) (the feature counts the columns of `bins`) and leaf_values / leaf_weights
+ * [t << depth, (t << depth) + (1 << tree_depth[t])); bit i of a leaf's index is the outcome of the tree's split i (CatBoost's order); an
+ * empty leaf has value 0.0 and weight 0.  A tree is shallower than `depth` only when no unused (feature, cut) pair is left. */
+#define BBBP_CAT_FIT_MAX_N 8192
+#define BBBP_CAT_FIT_MAX_D 65536
+#define BBBP_CAT_FIT_MAX_DEPTH 16
+#define BBBP_CAT_FIT_MAX_TREES 10000
+typedef struct bbbp_cat_problem {
+    const uint8_t* bins;                       /* [d][n] */
+    const int* n_cuts;                         /* [d]: the cuts of every feature, 1..255 */
+    const double* y;                           /* [n] */
+    int n, d;
+    int iterations, depth;
+    double l2_leaf_reg, learning_rate, bias;   /* bias: the mean of y, formed by the caller */
+    void* work;                                /* bbbp_cat_fit_work_bytes(n, d, depth) bytes, 16-byte aligned; need not be initialised */
+    int* split_feature; int* split_bin;        /* [iterations][depth] */
+    double* leaf_values; int* leaf_weights;    /* [iterations][1 << depth] */
+    int* tree_depth;                           /* [iterations]; -1 from the first tree on in which an index left its array (a defect) */
+    double* approx;                            /* [n]: the training rows' approximations (leaf sums + bias) after the last tree */
+} bbbp_cat_problem;
+/* Bytes of a problem's `work` (0 with a message outside the limits above). */
+size_t bbbp_cat_fit_work_bytes(int n, int d, int depth);
+/* Fit every problem, all side by side: per tree and level three launches (split, choose, partition) and one more per tree (update), all
+ * enqueued without a host read; the call returns when the stream is idle.  `problems` is a host array, `problems_device` the same bytes in
+ * device memory.  A problem's numbers do not depend on what else is in the batch: every sum is an integer sum or has a fixed order. */
+int bbbp_cat_fit(void* stream, const bbbp_cat_problem* problems, const bbbp_cat_problem* problems_device, int n_problems);
+/* For tools/bench_cat.py, per host thread: with the profile on, bbbp_cat_fit puts every split launch between two events and waits for the
+ * stream after every tree; bbbp_cat_fit_last gives the last fit's sum of those times (0 with the profile off) and the number of launches
+ * it enqueued.  Returns the previous setting. */
+int bbbp_cat_fit_profile(int enable);
+int bbbp_cat_fit_last(double* split_ms, long* launches);
+
 /* ---- rf fit: random-forest classification trees fitted by exact split search (csrc/rf.hip) --------------------------------------
  * RandomForestClassifier and DecisionTreeClassifier of the classification stack (Models/model_opt_maccs.py:124-200): two classes, Gini,
  * bootstrap rows as integer weights, max_features candidate features per node.  bbbp_amd/random_forest.py composes the classifiers and
