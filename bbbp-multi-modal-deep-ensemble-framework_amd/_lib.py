@@ -149,6 +149,14 @@ class CatProblem(Structure):
                 ("split_bin", c_void_p), ("leaf_values", c_void_p), ("leaf_weights", c_void_p), ("tree_depth", c_void_p), ("approx", c_void_p)]
 
 
+class CatcProblem(Structure):
+    """bbbp_catc_problem (include/bbbp_hip.h)."""
+    _fields_ = [("bins", c_void_p), ("n_cuts", c_void_p), ("t", c_void_p), ("weights", c_void_p), ("weight_stride", c_long), ("n", c_int), ("d", c_int),
+                ("iterations", c_int), ("depth", c_int), ("l2_leaf_reg", c_double), ("learning_rate", c_double), ("bias", c_double), ("work", c_void_p),
+                ("split_feature", c_void_p), ("split_bin", c_void_p), ("leaf_values", c_void_p), ("leaf_weights", c_void_p), ("tree_depth", c_void_p),
+                ("approx", c_void_p)]
+
+
 class EnsSource(Structure):
     """bbbp_ens_source (include/bbbp_hip.h)."""
     _fields_ = [("src", c_void_p), ("stride", c_long), ("col", c_long), ("rows", c_void_p), ("count", c_long), ("dst", c_long)]
@@ -247,6 +255,11 @@ _SIGNATURES = {
     "bbbp_cat_fit": (c_int, [c_void_p, POINTER(CatProblem), c_void_p, c_int]),
     "bbbp_cat_fit_profile": (c_int, [c_int]),
     "bbbp_cat_fit_last": (c_int, [POINTER(c_double), POINTER(c_long)]),
+    "bbbp_catc_fit_work_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "bbbp_catc_fit": (c_int, [c_void_p, POINTER(CatcProblem), c_void_p, c_int]),
+    "bbbp_catc_fit_profile": (c_int, [c_int]),
+    "bbbp_catc_fit_last": (c_int, [POINTER(c_double), POINTER(c_long)]),
+    "bbbp_catc_proba": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
     "bbbp_rf_fit_tree_capacity": (c_int, [c_int]),
     "bbbp_rf_fit_work_bytes": (c_size_t, [c_int, c_int, c_int]),
     "bbbp_rf_hash": (c_uint64, [c_uint64, c_uint64]),

@@ -59,6 +59,78 @@ its ``depth`` levels, and is shallower only when no unused candidate is left.
 roundings; an empty leaf has 0.0.  Then ``s_i += v[leaf(i)]``; ``leaf_weights`` records ``m_j``.
 
 *Model.*  A ``boosters.CatBoostTrees`` with ``scale = 1``, ``bias``, no NaN treatment, float32 borders and float64 leaf values.
+
+
+``catboost.CatBoostClassifier`` for two classes under Logloss, fitted by ``csrc/catc.hip``
+==========================================================================================
+
+Every classification script of the reference ends in a table of ten learners, one of them ``CatBoostClassifier(iterations=500,
+learning_rate=0.03, depth=10, l2_leaf_reg=5, bagging_temperature=0.5, loss_function="Logloss", verbose=0, random_seed=42)``
+(``Models/model_opt_20250130.py:413-457``), searched with ``RandomizedSearchCV`` over ``iterations``, ``learning_rate``, ``depth``,
+``l2_leaf_reg`` and ``border_count`` (``:547-561``) and a member of the stack's soft ``VotingClassifier`` (``:596-642``).
+
+PARITY UNPINNED, as for the regressor: the catboost package is absent where this is built and where it runs.  Fits and the loading of
+``get_model_json`` by CatBoost itself have never been compared with the package, only with the numpy restatement
+(``tests/catc_numpy.py``), which the GPU fit equals bit for bit: alone, in any batch and from run to run.
+
+THE DEVIATIONS from the package: the regressor's five stand (the deterministic form, the borders, the gradient grid -- here ``2^-28`` of
+``gmax`` --, the score ``num^2 / den``, ``learning_rate=None`` meaning 0.03), and
+
+6. *bootstrap_type=None* means ``"Bayesian"`` with the given temperature when ``bagging_temperature`` is given, otherwise ``"No"``.
+   ``bootstrap_type="Bayesian"`` with ``bagging_temperature=None`` means temperature 1.0.  The package's default is ``"MVS"`` for this loss.
+7. *The weights* are drawn per tree from our hash (``xgb.sample_hash``), in fixed point, not from the package's generator; and
+   ``bagging_temperature`` must lie in [0, 1].
+8. *random_strength=None* means 0; the package's default is 1.
+9. *leaf_estimation_iterations* must be ``None`` or 1, with method ``Newton``: one Newton step per leaf.  The package's default count for
+   Logloss is believed to be larger; that could not be checked, the package being absent.
+10. *The bias rule* below (``boost_from_average``).
+
+Refused by name with ``ValueError``: everything the regressor refuses, ``class_weights``, ``auto_class_weights``, ``scale_pos_weight``
+other than 1, bootstrap types other than ``"No"`` / ``"Bayesian"`` (MVS, Bernoulli, Poisson), ``subsample``, ``bagging_temperature`` outside
+[0, 1], ``random_strength > 0``, more than one leaf-estimation iteration, more or fewer than two classes (``MultiClass``), NaN.
+
+The algorithm is the regressor's -- quantisation, border rule, levels, the choice of a split and the model are word for word the text
+above -- with these differences:
+
+*Labels and bias.*  Exactly two classes; ``classes_ = np.unique(y)`` may hold labels of any dtype and ``t_i`` in {0.0, 1.0} is the row's
+index in ``classes_``.  With P rows of class 1 and N of class 0, ``boost_from_average=None`` or ``True`` gives ``bias = np.log(np.float64(P)
+/ np.float64(N))``, formed on the host, and ``False`` gives ``bias = 0.0``.  A fit whose rows lack a class is refused with ``ValueError``.
+
+*State.*  ``s_i`` and ``a_i = s_i + bias`` as in the regressor: float64, summed in tree order, the bias last, so
+``predict(X_train, prediction_type="RawFormulaVal")`` equals ``train_approx_`` bit for bit.
+
+*The sigmoid.*  ``p_i = sigmoid64(a_i)`` is ``csrc/xgbc.hip``'s ``sigmoid32`` without its final rounding to float32: ``a = max(-|z|,
+-700.0)`` (the clamp keeps ``p`` a normal float64), ``k = rint(a / ln2)``, ``r = (a - k LN2_HI) - k LN2_LO``, the Taylor polynomial of degree
+13 in ``r`` by Horner's rule in float64, ``e = ldexp(P, k)``, and ``1 / (1 + e)`` for ``z >= 0``, otherwise ``e / (1 + e)``.  IEEE operations
+only, in a file compiled with ``-ffp-contract=off``: numpy gives the same bits.  Against x86 long double the numpy form is within 2.4 ulp
+over +-700, monotone, finite and normal (``tests/test_catc_cpu.py`` asserts 4 ulp).
+
+*Per tree.*  ``g_i = t_i - p_i`` and ``h_i = p_i (1 - p_i)`` in float64, each operation rounded on its own; ``gmax = max |g_i|``, ``k = 27 -
+ilogb(gmax)`` (``k = 0`` when ``gmax == 0``), ``q_i = llrint(ldexp(g_i, k))``, so ``|q_i| <= 2^28``, and ``r_i = max(1, llrint(ldexp(h_i,
+48)))``, so ``r_i <= 2^46``.
+
+*Bootstrap weights.*  The Bayesian bootstrap, drawn once per tree, on the host (``log`` and ``pow`` are not IEEE-exact on the device).
+With the stream tag 2 (``xgb`` holds 0 and 1): ``u = ((sample_hash(seed, 2, tree, i) >> 11) + 1) 2^-53`` in (0, 1], ``i`` the row's
+position in the problem; ``w = np.power(-np.log(u), bagging_temperature)``; ``w_i = max(1, llrint(w 2^16))`` as uint32.  With the
+temperature in [0, 1], ``w_i <= 2 407 583 < 2^22``.  One table ``[iterations, n]`` is built per (seed, temperature) and batch, uploaded
+once and shared by the problems of the batch that use it, its row stride their largest ``n``.  ``random_seed=None`` means 0.
+``bootstrap_type="No"`` passes no table and every ``w_i`` is ``2^16``; ``bagging_temperature=0`` gives a table of ``2^16`` (``0 ** 0 == 1``
+in numpy): the two give the same model bit for bit.  The draw for tree ``t`` does not depend on ``iterations``: a model of T trees is
+the prefix of a longer one.
+
+*Structure search.*  The regressor's, with weighted gradients and weight sums for gradients and counts.  A row carries ``qw_i = q_i
+w_i``, an exact int64 product, ``|qw_i| < 2^50``.  A part carries ``QW = sum qw_i``, ``MW = sum w_i`` and its row count; with ``n <= 8 192``,
+``|QW| < 2^63`` and ``MW < 2^35``: exact integers in any order.  ``S = ldexp((double)QW, -(k + 16))`` and ``M = ldexp((double)MW, -16)``.  A
+side of a part is empty iff it holds no row, which is ``MW == 0`` (``w_i >= 1``); an empty side is skipped, otherwise ``alpha = S / (M +
+lambda)``, ``num += alpha S``, ``den += (alpha alpha) M``.  The order of the parts and sides, ``score = den > 0 ? (num num) / den : 0``, the
+tie rule, no pair used twice in a tree and no minimum gain are the regressor's.
+
+*Leaves.*  One Newton step over all rows of the leaf, unweighted (the bootstrap shapes the structure only): ``Qg = sum q_i`` and ``R = sum
+r_i`` over the leaf's rows, exact integers (``R <= 2^59``); ``G = ldexp((double)Qg, -k)``, ``H = ldexp((double)R, -48)``, ``value =
+learning_rate (G / (H + lambda))``; an empty leaf has 0.0; ``leaf_weights`` records the row count.
+
+*Output.*  ``predict_proba`` is float64 ``(1 - p1, p1)`` with ``p1 = sigmoid64(raw)``, the subtraction in float64; the class is
+``classes_[raw > 0]``.
 """
 from __future__ import annotations
 
@@ -99,15 +171,15 @@ def _same(value, ok):
     return isinstance(value, str) and value == ok
 
 
-def _refuse(other, who=_WHO):
+def _refuse(other, who=_WHO, neutral=_NEUTRAL):
     for name, value in other.items():
         if name in _IGNORED:
             continue
-        if name not in _NEUTRAL:
+        if name not in neutral:
             raise ValueError(f"{who}: unknown parameter {name}")
-        if value is None or any(_same(value, ok) for ok in _NEUTRAL[name]):
+        if value is None or any(_same(value, ok) for ok in neutral[name]):
             continue
-        only = " or ".join(repr(ok) for ok in _NEUTRAL[name] + (None,))
+        only = " or ".join(repr(ok) for ok in neutral[name] + (None,))
         raise ValueError(f"{who}: {name}={value!r} is not supported (only {only}): this class is the deterministic Plain form")
 
 
@@ -150,6 +222,8 @@ def borders_of(XT, cuts):
 class _Problem:
     """One model to fit: its outputs, its work area and the descriptor ``bbbp_cat_fit`` takes.  Nothing needs initialising."""
 
+    source = "csrc/cat.hip"
+
     def __init__(self, reg, up, rows, bins, n_cuts, y, dev):
         L = _lib.lib()
         n, d, T, D = bins.n, bins.d, int(reg.iterations), int(reg.depth)
@@ -177,13 +251,13 @@ class _Problem:
         levels = self.tree_depth.cpu().numpy().astype(np.int64)
         if (levels < 0).any() or (levels > D).any():
             raise RuntimeError(f"cat: the fit kernels reported an index outside its array in tree {int(np.argmax((levels < 0) | (levels > D)))} "
-                               "(a defect of csrc/cat.hip, not of the data); no model is returned")
+                               f"(a defect of {self.source}, not of the data); no model is returned")
         keep_split = (np.arange(D)[None, :] < levels[:, None]).ravel()
         keep_leaf = (np.arange(1 << D)[None, :] < (1 << levels)[:, None]).ravel()
         f_live = self.split_feature.cpu().numpy()[keep_split].astype(np.int64)
         c = self.split_bin.cpu().numpy()[keep_split].astype(np.int64)
         if len(f_live) and (f_live.min() < 0 or f_live.max() >= self.bins.d or c.min() < 0 or c.max() >= self.bins.cuts.shape[1]):
-            raise RuntimeError("cat: the fit kernels recorded a split outside the bin matrix (a defect of csrc/cat.hip); no model is returned")
+            raise RuntimeError(f"cat: the fit kernels recorded a split outside the bin matrix (a defect of {self.source}); no model is returned")
         # the borders of the pairs the model uses, from the problem's own training columns
         pairs, inverse = np.unique(f_live * 256 + c, return_inverse=True)
         uf, uc = torch.from_numpy(pairs // 256).to(dev), torch.from_numpy(pairs % 256).to(dev)
@@ -393,3 +467,410 @@ def fit_regressors(problems, **params):
     regressors = [CatBoostRegressor(**params) for _ in problems]
     _fit(regressors, problems)
     return regressors
+
+
+# ---- the classifier: Logloss, two classes (the second part of the module docstring) -------------------------------------------------------
+_CWHO = "CatBoostClassifier"
+WEIGHT_STREAM = 2                                    # the bootstrap's stream tag of xgb.sample_hash; xgb's row and column draws hold 0 and 1
+WEIGHT_BITS = 16                                     # fraction bits of a bootstrap weight
+_BOOTSTRAPS = ("No", "Bayesian")
+# as _NEUTRAL; the bootstrap and the bias are parameters of the constructor here
+_CLASSIFIER_NEUTRAL = {**{k: v for k, v in _NEUTRAL.items() if k not in ("bootstrap_type", "bagging_temperature", "boost_from_average")},
+                       "loss_function": ("Logloss",), "objective": ("Logloss",), "eval_metric": ("Logloss",), "leaf_estimation_method": ("Newton",),
+                       "class_weights": (), "auto_class_weights": (), "scale_pos_weight": (1,), "class_names": (), "classes_count": (2,)}
+
+
+def sigmoid64(x):
+    """``sigmoid64`` of the module docstring on the host: float64 probabilities of float64 raw values, the bits ``csrc/catc.hip`` gives."""
+    z = np.asarray(x, np.float64)
+    a = np.maximum(-np.abs(z), -700.0)
+    k = np.rint(a * xgb.INV_LN2)
+    r = (a - k * xgb.LN2_HI) - k * xgb.LN2_LO
+    P = np.full_like(r, xgb._EXP_COEFFS[13])
+    for j in range(12, -1, -1):
+        P = P * r + xgb._EXP_COEFFS[j]
+    e = np.ldexp(P, k.astype(np.int32))
+    return np.where(z >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
+def weight_table(seed, temperature, iterations, n):
+    """uint32 [iterations, n]: the Bayesian bootstrap's fixed-point weights of the module docstring, tree by row position.  Formed on the
+    host: ``log`` and ``pow`` are not IEEE-exact on the device."""
+    if not 0.0 <= float(temperature) <= 1.0:
+        raise ValueError(f"{_CWHO}: bagging_temperature must lie in [0, 1], got {temperature!r}")
+    h = xgb.sample_hash(0 if seed is None else seed, WEIGHT_STREAM, np.arange(int(iterations))[:, None], np.arange(int(n))[None, :])
+    u = ((h >> np.uint64(11)) + np.uint64(1)).astype(np.float64) * 2.0 ** -53
+    w = np.power(-np.log(u), np.float64(temperature))
+    return np.maximum(1, np.rint(w * 2.0 ** WEIGHT_BITS).astype(np.int64)).astype(np.uint32)
+
+
+def _binary_labels(y, n_rows, who=_CWHO):
+    """(classes_, t): ``np.unique(y)`` of exactly two classes and the targets 0.0 / 1.0 as float64 [n_rows]."""
+    y = np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y)
+    if y.ndim == 2 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.ndim != 1 or (n_rows is not None and len(y) != n_rows):
+        raise ValueError(f"{who}: y must hold one label per row of X, got shape {tuple(y.shape)} for {n_rows} rows")
+    if y.dtype.kind == "f" and not np.isfinite(y).all():
+        raise ValueError(f"{who}: y contains NaN or infinity")
+    classes = np.unique(y)
+    if len(classes) != 2:
+        raise ValueError(f"{who}: y must hold exactly two classes (loss_function Logloss; MultiClass is not supported), got {len(classes)}: "
+                         f"{classes[:5]!r}")
+    return classes, (y == classes[1]).astype(np.float64)
+
+
+def _proba_of_raw(raw):
+    """float64 [m, 2] on the raw values' device: ``bbbp_catc_proba``."""
+    raw = raw.contiguous()
+    out = torch.empty((raw.shape[0], 2), dtype=torch.float64, device=raw.device)
+    with torch.cuda.device(raw.device):
+        _lib.check(_lib.lib().bbbp_catc_proba(_dense.stream(), raw.data_ptr(), raw.shape[0], out.data_ptr()), "bbbp_catc_proba")
+    return out
+
+
+class _ClassifierProblem(_Problem):
+    """One classifier to fit: its outputs, its work area and the descriptor ``bbbp_catc_fit`` takes.  ``weights`` is the batch's table for
+    the classifier's (seed, temperature), uint32 [>= iterations, stride] on the device, or None."""
+
+    source = "csrc/catc.hip"
+
+    def __init__(self, clf, up, rows, bins, n_cuts, classes, t, weights, dev):
+        L = _lib.lib()
+        n, d, T, D = bins.n, bins.d, int(clf.iterations), int(clf.depth)
+        nbytes = L.bbbp_catc_fit_work_bytes(n, d, D)
+        if not nbytes:
+            raise ValueError("cat: " + L.bbbp_last_error().decode("utf-8", "replace"))
+        self.up, self.rows, self.bins, self.n_cuts, self.T, self.D, self.classes, self.weights = up, rows, bins, n_cuts, T, D, classes, weights
+        positives = float(t.sum())
+        self.bias = 0.0 if clf.boost_from_average is False else float(np.log(np.float64(positives) / np.float64(len(t) - positives)))
+        self.learning_rate = DEFAULT_LEARNING_RATE if clf.learning_rate is None else float(clf.learning_rate)
+        self.y = torch.from_numpy(np.ascontiguousarray(t, np.float64)).to(dev)
+        self.work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.split_feature = torch.empty(T * D, dtype=torch.int32, device=dev)
+        self.split_bin = torch.empty(T * D, dtype=torch.int32, device=dev)
+        self.leaf_values = torch.empty(T << D, dtype=torch.float64, device=dev)
+        self.leaf_weights = torch.empty(T << D, dtype=torch.int32, device=dev)
+        self.tree_depth = torch.empty(T, dtype=torch.int32, device=dev)
+        self.approx = torch.empty(n, dtype=torch.float64, device=dev)
+        if weights is not None and (weights.shape[0] < T or weights.shape[1] < n):
+            raise RuntimeError(f"cat: a weight table of shape {tuple(weights.shape)} for {T} trees of {n} rows")
+        self.desc = _lib.CatcProblem(bins.bins.data_ptr(), n_cuts.data_ptr(), self.y.data_ptr(), weights.data_ptr() if weights is not None else None,
+                                     weights.stride(0) if weights is not None else 0, n, d, T, D, float(clf.l2_leaf_reg), self.learning_rate, self.bias,
+                                     self.work.data_ptr(), self.split_feature.data_ptr(), self.split_bin.data_ptr(), self.leaf_values.data_ptr(),
+                                     self.leaf_weights.data_ptr(), self.tree_depth.data_ptr(), self.approx.data_ptr())
+
+
+def _run_classifiers(problems, dev):
+    arr = (_lib.CatcProblem * len(problems))(*[p.desc for p in problems])
+    on_device = _tree_host.upload(arr, dev)
+    _lib.check(_lib.lib().bbbp_catc_fit(_dense.stream(), arr, on_device.data_ptr(), len(problems)), "bbbp_catc_fit")
+    return on_device                                  # the fit has synchronised the stream; kept alive by the caller all the same
+
+
+class CatBoostClassifier(_estimator.Params):
+    """``CatBoostClassifier(iterations=1000, learning_rate=None, depth=6, l2_leaf_reg=3.0, border_count=254, bagging_temperature=None,
+    bootstrap_type=None, boost_from_average=None, random_seed=None, verbose=None, device="cuda")``: CatBoost's names for two classes under
+    ``Logloss``; the regressor's aliases apply (``random_state``, ``n_estimators``, ``max_depth``, ``reg_lambda``), and ``loss_function`` /
+    ``objective`` / ``eval_metric`` pass as ``"Logloss"``.  ``bootstrap_type`` is ``None``, ``"No"`` or ``"Bayesian"``: ``None`` means
+    ``"Bayesian"`` when ``bagging_temperature`` is given and ``"No"`` otherwise, ``"Bayesian"`` without a temperature means 1.0; the
+    temperature lies in [0, 1].  The reference's ``CatBoostClassifier(iterations=500, learning_rate=0.03, depth=10, l2_leaf_reg=5,
+    bagging_temperature=0.5, loss_function="Logloss", verbose=0, random_seed=42)`` (Models/model_opt_20250130.py:413-457) builds as written.
+    Everything else is refused by name with ``ValueError`` (the module docstring lists it, with the algorithm, the deviations and the
+    unpinned parity with the catboost package).
+
+    ``fit(X, y)`` takes what the regressor's takes, with finite features, and labels of any dtype in exactly two classes.  It sets
+    ``classes_``, ``model_`` (a ``boosters.CatBoostTrees`` of raw values), ``trees_``, ``bias_``, ``tree_count_``, ``n_features_in_`` and
+    ``train_approx_`` (float64: the training rows' raw values as the fit summed them; ``predict(X_train,
+    prediction_type="RawFormulaVal")`` equals it bit for bit).  ``predict_proba`` / ``predict_log_proba`` are float64 [m, 2], ``predict`` takes
+    ``prediction_type="Class" | "Probability" | "RawFormulaVal"``; numpy in gives numpy out, a CUDA tensor in a CUDA tensor, answered from
+    the device.  ``get_model_json`` / ``save_model`` write CatBoost's JSON export schema; ``get_params`` / ``set_params`` make
+    ``sklearn.base.clone`` and ``ensemble.StackingClassifier`` / ``VotingClassifier`` work."""
+
+    _params = ("iterations", "learning_rate", "depth", "l2_leaf_reg", "border_count", "bagging_temperature", "bootstrap_type", "boost_from_average",
+               "random_seed", "verbose", "device")
+
+    def __init__(self, iterations=1000, learning_rate=None, depth=6, l2_leaf_reg=3.0, border_count=254, bagging_temperature=None, bootstrap_type=None,
+                 boost_from_average=None, random_seed=None, verbose=None, device="cuda", **other):
+        given = dict(iterations=iterations, depth=depth, l2_leaf_reg=l2_leaf_reg, random_seed=random_seed)
+        for alias, name in _ALIASES.items():
+            if alias in other:
+                value = other.pop(alias)
+                if given[name] is not _DEFAULTS[name] and given[name] != _DEFAULTS[name]:
+                    raise ValueError(f"{_CWHO}: {alias} is an alias of {name}: only one of them may be given")
+                given[name] = value
+        _refuse(other, _CWHO, _CLASSIFIER_NEUTRAL)
+        border_count = 254 if border_count is None else border_count
+        _check_params(given["iterations"], learning_rate, given["depth"], given["l2_leaf_reg"], border_count, given["random_seed"], who=_CWHO)
+        seed = given["random_seed"]
+        if seed is not None and not 0 <= seed < 2 ** 64:
+            raise ValueError(f"{_CWHO}: random_seed must be None or an int in 0..2^64-1, got {seed!r}")
+        if bootstrap_type is not None and bootstrap_type not in _BOOTSTRAPS:
+            raise ValueError(f"{_CWHO}: bootstrap_type={bootstrap_type!r} is not supported (only 'No', 'Bayesian' or None: MVS, Bernoulli and "
+                             "Poisson sampling are not built)")
+        if bagging_temperature is not None:
+            xgb._number(bagging_temperature, "bagging_temperature", 0.0, who=_CWHO)
+            if bagging_temperature > 1:
+                raise ValueError(f"{_CWHO}: bagging_temperature must lie in [0, 1] (the weights are fixed point below 2^22), got {bagging_temperature!r}")
+            if bootstrap_type == "No":
+                raise ValueError(f"{_CWHO}: bagging_temperature={bagging_temperature!r} needs bootstrap_type='Bayesian' or None, got 'No'")
+        if boost_from_average is not None and not isinstance(boost_from_average, (bool, np.bool_)):
+            raise ValueError(f"{_CWHO}: boost_from_average must be None, True or False, got {boost_from_average!r}")
+        if isinstance(device, (list, tuple)):
+            raise ValueError(f"{_CWHO}: device={device!r}: more than one GPU is not supported")
+        # the parameters are kept as they were given: sklearn.base.clone compares them by identity
+        self.iterations, self.depth, self.l2_leaf_reg, self.random_seed = given["iterations"], given["depth"], given["l2_leaf_reg"], given["random_seed"]
+        self.learning_rate, self.border_count, self.verbose, self.device = learning_rate, border_count, verbose, device
+        self.bagging_temperature, self.bootstrap_type, self.boost_from_average = bagging_temperature, bootstrap_type, boost_from_average
+
+    def set_params(self, **params):
+        return super().set_params(**{_ALIASES.get(k, k): v for k, v in params.items()})
+
+    def _temperature(self):
+        """The Bayesian bootstrap's temperature, or None without a bootstrap."""
+        if self.bagging_temperature is not None:
+            return float(self.bagging_temperature)
+        return 1.0 if self.bootstrap_type == "Bayesian" else None
+
+    # ---- fit --------------------------------------------------------------------------------------------------------
+    def fit(self, X, y, cat_features=None, text_features=None, embedding_features=None, sample_weight=None, eval_set=None, early_stopping_rounds=None,
+            use_best_model=None, **other):
+        if cat_features is not None or text_features is not None or embedding_features is not None:
+            raise ValueError(f"{_CWHO}: categorical, text and embedding features are not supported (float features only)")
+        if sample_weight is not None:
+            raise ValueError(f"{_CWHO}: sample_weight is not supported")
+        if eval_set is not None or early_stopping_rounds is not None or use_best_model:
+            raise ValueError(f"{_CWHO}: eval_set and early stopping are not supported")
+        rest = set(other) - {"verbose", "verbose_eval", "silent", "logging_level", "plot", "metric_period"}
+        if rest:
+            raise ValueError(f"{_CWHO}: fit arguments {sorted(rest)} are not supported")
+        _fit_classifiers([self], [(X, y)])
+        return self
+
+    def _adopt(self, classes, trees, bias, n_features, train_approx=None):
+        self.classes_ = np.asarray(classes)
+        return CatBoostRegressor._adopt(self, trees, bias, n_features, train_approx)
+
+    @classmethod
+    def from_trees(cls, trees, bias, n_features, classes=(0, 1), device="cuda", **params):
+        """A classifier around fitted arrays (``trees_``' keys): for prediction and the JSON export.  ``device="cpu"`` gives a model that
+        exports and validates but cannot predict."""
+        classes = np.asarray(classes)
+        if classes.shape != (2,) or not np.array_equal(np.unique(classes), classes):
+            raise ValueError(f"{_CWHO}: classes must be two distinct labels in ascending order, got {classes!r}")
+        self = cls(device=device, **params)
+        return self._adopt(classes, {k: np.asarray(v) for k, v in trees.items()}, bias, n_features)
+
+    # ---- prediction -------------------------------------------------------------------------------------------------
+    def _fitted(self):
+        if not hasattr(self, "model_"):
+            raise RuntimeError(f"{_CWHO}: not fitted")
+        return self.model_
+
+    def predict_device(self, X):
+        """float64 [m] on the device: the raw values, ``bias_`` behind the sum of the trees' leaf values (``bbbp_oblivious_predict``)."""
+        return self._fitted().predict_device(X)
+
+    def predict_proba(self, X):
+        """float64 [m, 2]: ``(1 - p1, p1)`` with ``p1 = sigmoid64(raw)`` (``bbbp_catc_proba``)."""
+        out = _proba_of_raw(self.predict_device(X))
+        return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
+
+    def predict_log_proba(self, X):
+        """float64 [m, 2]: the logarithm of ``predict_proba``; a logarithm of finished probabilities is plumbing (torch's, on the device)."""
+        out = torch.log(_proba_of_raw(self.predict_device(X)))
+        return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
+
+    def predict(self, X, prediction_type="Class"):
+        """``classes_[raw > 0]``, the probabilities or the raw values: numpy for numpy queries; for a CUDA tensor a CUDA tensor (of the labels
+        when they are numbers)."""
+        if prediction_type == "Probability":
+            return self.predict_proba(X)
+        if prediction_type not in ("Class", "RawFormulaVal"):
+            raise ValueError(f"{_CWHO}: prediction_type={prediction_type!r} is not supported (only 'Class', 'Probability' or 'RawFormulaVal')")
+        raw = self.predict_device(X)
+        if prediction_type == "RawFormulaVal":
+            return raw if isinstance(X, torch.Tensor) else raw.cpu().numpy()
+        positive = raw > 0
+        if isinstance(X, torch.Tensor) and self.classes_.dtype.kind in "biuf":
+            return torch.from_numpy(self.classes_).to(positive.device)[positive.long()]
+        return self.classes_[positive.cpu().numpy().astype(np.intp)]
+
+    # ---- export -----------------------------------------------------------------------------------------------------
+    def get_model_json(self):
+        """The regressor's document with ``loss_function.type = "Logloss"`` and ``model_info.class_params`` (``class_names``,
+        ``class_to_label``, ``class_label_type``); ``boosters.CatBoostTrees.from_json`` reads it back to the same arrays, which give raw
+        values.  That CatBoost itself loads it is UNPINNED: the package is absent (see the module docstring)."""
+        doc = json.loads(CatBoostRegressor.get_model_json(self))
+        doc["model_info"]["params"]["loss_function"] = {"type": "Logloss"}
+        kind = self.classes_.dtype.kind
+        doc["model_info"]["class_params"] = {"class_label_type": "Integer" if kind in "biu" else "Float" if kind == "f" else "String",
+                                             "class_names": [c.item() if kind in "biuf" else str(c) for c in self.classes_], "class_to_label": [0, 1]}
+        return json.dumps(doc)
+
+    def save_model(self, path, format="json"):
+        if format != "json":
+            raise ValueError(f"{_CWHO}: save_model writes format='json' only, got {format!r}")
+        with open(path, "w") as f:
+            f.write(self.get_model_json())
+
+
+def _fit_classifiers(classifiers, problems):
+    """Fit ``classifiers[i]`` on ``problems[i] = (X, y)`` or ``(X, y, rows)`` in one ``bbbp_catc_fit`` batch.  Uploads and bin matrices are
+    shared as ``_fit`` shares them; cuts, classes, the bias and the weights (by a row's position within the problem) are the problem's own:
+    a fold fitted in a batch equals the fold fitted alone bit for bit.  One weight table per (seed, temperature) serves the batch."""
+    devices = {str(_cuda_device(clf.device, _CWHO)) for clf in classifiers}
+    if len(devices) != 1:
+        raise ValueError(f"{_CWHO}: the classifiers of one batch name the devices {sorted(devices)}: more than one GPU is not supported")
+    dev = _cuda_device(classifiers[0].device, _CWHO)
+    checked, uploads = [], {}
+    for prob in problems:
+        if len(prob) not in (2, 3):
+            raise ValueError(f"{_CWHO}: a problem is (X, y) or (X, y, rows), got {len(prob)} items")
+        X, y, rows = prob[0], prob[1], (prob[2] if len(prob) == 3 else None)
+        n_all = X.shape[0] if hasattr(X, "shape") and len(X.shape) == 2 else None
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64)
+            if rows.ndim != 1 or n_all is None or (len(rows) and (rows.min() < 0 or rows.max() >= n_all)):
+                raise ValueError(f"{_CWHO}: rows must be a 1-D array of row indices of X")
+        n = len(rows) if rows is not None else n_all
+        if n is not None and n > MAX_ROWS:
+            raise ValueError(f"{_CWHO}: n = {n} rows, more than {MAX_ROWS} are not supported (BBBP_CAT_FIT_MAX_N)")
+        if n is not None and n < 2:
+            raise ValueError(f"{_CWHO}: at least two rows are needed, got {n}")
+        y_all = np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y)
+        if y_all.ndim == 2 and y_all.shape[1] == 1:
+            y_all = y_all[:, 0]
+        if y_all.ndim != 1 or (n_all is not None and len(y_all) != n_all):
+            raise ValueError(f"{_CWHO}: y must hold one label per row of X, got shape {tuple(y_all.shape)} for {n_all} rows")
+        classes, t = _binary_labels(y_all if rows is None else y_all[rows], n)
+        if id(X) not in uploads:
+            uploads[id(X)] = xgb._Upload(X, who=_CWHO)
+        up = uploads[id(X)]
+        if len(up.cols) == 0:
+            raise ValueError(f"{_CWHO}: all features are constant")
+        if rows is None and len(up.cols) > MAX_LIVE_FEATURES:
+            raise ValueError(f"{_CWHO}: {len(up.cols)} live features, more than {MAX_LIVE_FEATURES} are not supported (BBBP_CAT_FIT_MAX_D)")
+        checked.append((X, classes, t, rows))
+    with torch.cuda.device(dev):
+        binned, per_problem = {}, []
+        for clf, (X, classes, t, rows) in zip(classifiers, checked):
+            up = uploads[id(X)].upload(dev)
+            key = (id(X), None if rows is None else rows.tobytes(), int(clf.border_count))
+            if key not in binned:
+                try:
+                    bins = xgb._Bins(up, rows, int(clf.border_count) + 1, dev, who=_CWHO)
+                except NotImplementedError as e:
+                    raise ValueError(str(e)) from None
+                n_cuts = torch.isfinite(bins.cuts).sum(dim=1).to(torch.int32).contiguous()
+                if int(n_cuts.min()) < 1:                 # xgb._Bins' dead feature: no column of these rows has a cut
+                    raise ValueError(f"{_CWHO}: all features are constant")
+                binned[key] = (bins, n_cuts)
+            per_problem.append((up, binned[key]))
+        shapes = {}                                       # (seed, temperature) -> (most trees, most rows) among the problems that draw from it
+        for clf, (_, (bins, _)) in zip(classifiers, per_problem):
+            if clf._temperature() is not None:
+                key = (0 if clf.random_seed is None else int(clf.random_seed), clf._temperature())
+                T, n = shapes.get(key, (0, 0))
+                shapes[key] = (max(T, int(clf.iterations)), max(n, bins.n))
+        tables = {}
+        for key, (T, n) in shapes.items():
+            tables[key] = torch.empty((T, n), dtype=torch.int32, device=dev)
+            tables[key].copy_(torch.from_numpy(weight_table(key[0], key[1], T, n).view(np.int32)))
+        fits = []
+        for clf, (X, classes, t, rows), (up, (bins, n_cuts)) in zip(classifiers, checked, per_problem):
+            key = (0 if clf.random_seed is None else int(clf.random_seed), clf._temperature())
+            fits.append(_ClassifierProblem(clf, up, rows, bins, n_cuts, classes, t, tables.get(key), dev))
+        keep = _run_classifiers(fits, dev)
+        for clf, fit in zip(classifiers, fits):
+            clf._adopt(fit.classes, fit.trees(dev), fit.bias, fit.up.d, fit.approx.cpu().numpy())
+        del keep
+
+
+def fit_classifiers(problems, **params):
+    """``[CatBoostClassifier(**params).fit(X[rows], y[rows]) for X, y, rows in problems]`` with every problem in one batch (``(X, y)`` means
+    all rows): five folds and the refit are one call.  Each classifier equals its single ``fit`` bit for bit."""
+    problems = list(problems)
+    if not problems:
+        raise ValueError("cat.fit_classifiers: no problems")
+    classifiers = [CatBoostClassifier(**params) for _ in problems]
+    _fit_classifiers(classifiers, problems)
+    return classifiers
+
+
+# ---- the reference's randomized search ------------------------------------------------------------------------------------------------------
+_SEARCH_KEYS = ("iterations", "learning_rate", "depth", "l2_leaf_reg", "border_count", "bagging_temperature")
+
+
+def _prefix_raw(clf, Xq, lengths):
+    """{T: float64 raw values of ``clf``'s first T trees on the device rows ``Xq``}.  A prefix is a model of its own
+    (``boosters.CatBoostTrees`` over the first T trees), so each equals the raw values of the shorter fit bit for bit."""
+    t, out = clf.trees_, {}
+    first_leaf = np.concatenate([t["tree_first_leaf"], [len(t["leaf_values"])]])
+    for T in lengths:
+        ns, nl = int(t["tree_first_split"][T]), int(first_leaf[T])
+        short = boosters.CatBoostTrees(t["split_feature"][:ns], t["split_border"][:ns], np.zeros(clf.n_features_in_, np.uint8), t["tree_first_split"][:T + 1],
+                                       t["tree_first_leaf"][:T], t["leaf_values"][:nl], clf.n_features_in_, 1.0, float(clf.bias_), device=clf.device)
+        out[T] = short.predict_device(Xq)
+    return out
+
+
+def randomized_search_cv(X, y, param_distributions, n_iter=50, cv=5, scoring=("accuracy", "precision"), refit="accuracy", random_state=None, device="cuda",
+                         **fixed):
+    """The reference's ``RandomizedSearchCV(CatBoostClassifier(...), param_grid, n_iter=50, cv=StratifiedKFold(5), scoring={accuracy,
+    precision}, refit="accuracy")`` (Models/model_opt_20250130.py:533-561) over ``iterations``, ``learning_rate``, ``depth``, ``l2_leaf_reg``,
+    ``border_count`` and ``bagging_temperature``; ``fixed`` holds the estimator's other parameters.
+
+    The points are scikit-learn's ``ParameterSampler(param_distributions, n_iter, random_state=random_state)``, the folds
+    ``StratifiedKFold(cv)`` without shuffling.  The weights of tree ``t`` do not depend on ``iterations``, so a model of T trees is the prefix
+    of a longer one: every fold fits one chain per distinct setting of everything but ``iterations`` to the longest length asked of it, all
+    chains of all folds in one ``bbbp_catc_fit`` batch, and the shorter models are scored from tree prefixes of the fold's test rows.  Scores
+    come through ``bbbp_amd.metrics`` with ``classes_[1]`` as the positive class (an undefined precision counts 0, scikit-learn's default).
+    Returns (best_params, {name: mean score per point}, the classifier refitted on all rows with best_params); the first maximum of
+    ``refit`` wins."""
+    from sklearn.model_selection import ParameterSampler, StratifiedKFold
+    from . import metrics
+    who = "cat.randomized_search_cv"
+    score_keys = {"accuracy": "Accuracy", "precision": "Precision", "recall": "Recall", "f1": "F1 Score"}
+    scoring = (scoring,) if isinstance(scoring, str) else tuple(scoring)
+    unknown = [s for s in scoring if s not in score_keys]
+    if unknown or not scoring:
+        raise ValueError(f"{who}: scoring {unknown!r} is not supported (only {sorted(score_keys)})")
+    if refit not in scoring:
+        raise ValueError(f"{who}: refit={refit!r} is not one of the scores {scoring!r}")
+    dev = _cuda_device(device, who)
+    strangers = set(param_distributions) - set(_SEARCH_KEYS)
+    if strangers:
+        raise ValueError(f"{who}: the parameters {sorted(strangers)} cannot be searched (only {list(_SEARCH_KEYS)})")
+    points = list(ParameterSampler(param_distributions, n_iter=n_iter, random_state=random_state))
+    models = [CatBoostClassifier(**{**fixed, **pt, "device": dev}) for pt in points]       # every point is checked before anything is fitted
+    X = np.asarray(X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else X)
+    y = np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y)
+    classes, _ = _binary_labels(y, X.shape[0] if X.ndim == 2 else None, who)
+    folds = list(StratifiedKFold(n_splits=cv).split(np.zeros((len(y), 1)), y))
+    rest_of = lambda m: tuple((k, v) for k, v in m.get_params().items() if k not in ("iterations", "device"))  # noqa: E731
+    longest = {}
+    for m in models:
+        longest[rest_of(m)] = max(longest.get(rest_of(m), 0), int(m.iterations))
+    chains, problems = {}, []
+    for fi, (tr, _) in enumerate(folds):
+        for rest, T in longest.items():
+            chains[(fi, rest)] = CatBoostClassifier(iterations=T, device=dev, **dict(rest))
+            problems.append((X, y, tr))
+    _fit_classifiers(list(chains.values()), problems)
+    table = {s: np.zeros((len(points), len(folds))) for s in scoring}
+    with torch.cuda.device(dev):
+        for fi, (_, te) in enumerate(folds):
+            Xq = torch.from_numpy(np.ascontiguousarray(X[te], dtype=np.float32)).to(dev)
+            for rest in longest:
+                chain = chains[(fi, rest)]
+                members = [pi for pi, m in enumerate(models) if rest_of(m) == rest]
+                raw = _prefix_raw(chain, Xq, sorted({int(models[pi].iterations) for pi in members}))
+                preds = np.stack([chain.classes_[(raw[int(models[pi].iterations)] > 0).cpu().numpy().astype(np.intp)] for pi in members])
+                got = metrics.classification_scores(y[te], preds, pos_label=classes[1], zero_division=0, device=dev)
+                for s in scoring:
+                    table[s][members, fi] = got[score_keys[s]][:, 0]
+    means = {s: [float(v) for v in table[s].mean(axis=1)] for s in scoring}
+    best = int(np.argmax(means[refit]))
+    fitted = CatBoostClassifier(**{**fixed, **points[best], "device": dev}).fit(X, y)
+    return points[best], means, fitted

@@ -336,10 +336,10 @@ def _subset(X_dev, t, rows):
 def _batched_path(est):
     """The name of the list-of-problems path ``_fit_rows`` takes for ``est``, or None when its fits are looped.  A subclass that brings a
     ``fit`` of its own is looped: its fits go through that ``fit``."""
-    from . import gradient_boosting, linear_model, mlp, naive_bayes, random_forest, xgb
+    from . import cat, gradient_boosting, linear_model, mlp, naive_bayes, random_forest, xgb
     for cls, path in ((random_forest.RandomForestClassifier, "random_forest._grow"), (gradient_boosting.GradientBoostingClassifier, "gradient_boosting._fit_chains"),
                       (mlp.MLPClassifier, "GridMLPTrainer.fit"), (naive_bayes.BernoulliNB, "naive_bayes.fit_masks"), (linear_model.LogisticRegression, "linear_model._solve"),
-                      (xgb.XGBClassifier, "xgb._fit_classifiers")):
+                      (xgb.XGBClassifier, "xgb._fit_classifiers"), (cat.CatBoostClassifier, "cat._fit_classifiers")):
         if isinstance(est, cls) and type(est).fit is cls.fit:
             return path
     return None
@@ -350,7 +350,7 @@ def _fit_rows(estimator, X_dev, t, row_sets):
     ``t``: through the learner's own list-of-problems path where it has one (``_batched_path``; each module keeps that path next to its
     ``fit``, which goes through it too), so that the fits of one learner run side by side and each equals the one-at-a-time fit bit for
     bit; looped otherwise.  Learners of this package get row-gathered device tensors, foreign ones the rows on the host."""
-    from . import gradient_boosting, linear_model, mlp, naive_bayes, random_forest, xgb
+    from . import cat, gradient_boosting, linear_model, mlp, naive_bayes, random_forest, xgb
     path = _batched_path(estimator)
     clones = [_clone(estimator) for _ in row_sets]
     if path == "naive_bayes.fit_masks":                  # row masks over the one packed matrix: nothing is gathered
@@ -369,7 +369,7 @@ def _fit_rows(estimator, X_dev, t, row_sets):
             c.fit(Xr, tr)
     else:
         module = {"random_forest._grow": random_forest, "gradient_boosting._fit_chains": gradient_boosting, "linear_model._solve": linear_model,
-                  "xgb._fit_classifiers": xgb}[path]
+                  "xgb._fit_classifiers": xgb, "cat._fit_classifiers": cat}[path]
         module._fit_classifiers(clones, problems)
     return clones
 

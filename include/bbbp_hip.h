@@ -812,6 +812,41 @@ int bbbp_cat_fit(void* stream, const bbbp_cat_problem* problems, const bbbp_cat_
 int bbbp_cat_fit_profile(int enable);
 int bbbp_cat_fit_last(double* split_ms, long* launches);
 
+/* ---- catc fit: boosted oblivious (symmetric) classification trees, CatBoost's Plain boosting for Logloss (csrc/catc.hip) ---------------
+ * CatBoostClassifier of the classification stack (Models/model_opt_20250130.py:413-457).  bbbp_amd/cat.py states the algorithm and
+ * composes CatBoostClassifier / fit_classifiers / randomized_search_cv from these.  Everything is bbbp_cat_fit's -- the byte features, the
+ * split and leaf arrays, the leaf order, the limits BBBP_CAT_FIT_MAX_* -- but: t holds the targets 0.0 / 1.0; a row's gradient and hessian
+ * are t - p and p (1 - p) in float64 with p = sigmoid64(approx), a float64 sigmoid made of IEEE operations only; tree k gives row i (its
+ * position in the problem) the weight weights[k * weight_stride + i] / 2^16 in the split scores, 1 <= weights < 2^22 (the caller draws
+ * them: cat.py's Bayesian bootstrap); with weights null every weight is 2^16.  A part's gradient and weight sums are exact integer sums
+ * (|gradient 2^k weight| < 2^50, at most 8 192 rows).  A leaf's value is one unweighted Newton step, learning_rate (G / (H + l2_leaf_reg)),
+ * H = 2^-BBBP_CATC_HESS_BITS times the exact integer sum of max(1, llrint(h 2^BBBP_CATC_HESS_BITS)); leaf_weights records the row count. */
+#define BBBP_CATC_HESS_BITS 48
+typedef struct bbbp_catc_problem {
+    const uint8_t* bins;                       /* [d][n] */
+    const int* n_cuts;                         /* [d]: the cuts of every feature, 1..255 */
+    const double* t;                           /* [n]: 0.0 / 1.0 */
+    const uint32_t* weights;                   /* [iterations][weight_stride], or null: every row weighs 2^16 in every tree */
+    long weight_stride;                        /* >= n */
+    int n, d;
+    int iterations, depth;
+    double l2_leaf_reg, learning_rate, bias;   /* bias: every row's approximation before the first tree, formed by the caller */
+    void* work;                                /* bbbp_catc_fit_work_bytes(n, d, depth) bytes, 16-byte aligned; need not be initialised */
+    int* split_feature; int* split_bin;        /* [iterations][depth] */
+    double* leaf_values; int* leaf_weights;    /* [iterations][1 << depth] */
+    int* tree_depth;                           /* [iterations]; -1 from the first tree on in which an index left its array (a defect) */
+    double* approx;                            /* [n]: the training rows' raw values (leaf sums + bias) after the last tree */
+} bbbp_catc_problem;
+/* Bytes of a problem's `work` (0 with a message outside the limits BBBP_CAT_FIT_MAX_*). */
+size_t bbbp_catc_fit_work_bytes(int n, int d, int depth);
+/* Fit every problem, all side by side, in bbbp_cat_fit's launches; a problem's numbers do not depend on what else is in the batch. */
+int bbbp_catc_fit(void* stream, const bbbp_catc_problem* problems, const bbbp_catc_problem* problems_device, int n_problems);
+/* For tools/bench_catc.py: as bbbp_cat_fit_profile / bbbp_cat_fit_last, for bbbp_catc_fit. */
+int bbbp_catc_fit_profile(int enable);
+int bbbp_catc_fit_last(double* split_ms, long* launches);
+/* proba [m][2] float64: proba[i][1] = sigmoid64(raw[i]), proba[i][0] = 1 - proba[i][1] in float64; one launch. */
+int bbbp_catc_proba(void* stream, const double* raw, long m, double* proba);
+
 /* ---- rf fit: random-forest classification trees fitted by exact split search (csrc/rf.hip) --------------------------------------
  * RandomForestClassifier and DecisionTreeClassifier of the classification stack (Models/model_opt_maccs.py:124-200): two classes, Gini,
  * bootstrap rows as integer weights, max_features candidate features per node.  bbbp_amd/random_forest.py composes the classifiers and
