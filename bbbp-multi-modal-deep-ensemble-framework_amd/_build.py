@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbbbp_hip.so")
-SOURCES = ["util.hip", "gemm.hip", "conv.hip", "conv_wino.hip", "conv_b3.hip", "conv_b3c1.hip", "rowops.hip", "engine.hip", "encoder.hip", "fold.hip", "attention.hip", "attention_b3.hip", "preprocess.hip", "mlp.hip", "head.hip", "forest.hip", "pca.hip", "knn.hip", "svm.hip", "svm_proba.hip", "svr.hip", "logreg.hip", "gbt.hip", "rf.hip", "iforest.hip", "bnb.hip", "smote.hip", "metrics.hip", "xgb.hip", "xgbc.hip", "cat.hip", "catc.hip", "ensemble.hip"]
+SOURCES = ["util.hip", "gemm.hip", "conv.hip", "conv_wino.hip", "conv_b3.hip", "conv_b3c1.hip", "rowops.hip", "engine.hip", "encoder.hip", "fold.hip", "attention.hip", "attention_b3.hip", "preprocess.hip", "mlp.hip", "head.hip", "forest.hip", "pca.hip", "knn.hip", "svm.hip", "svm_proba.hip", "svr.hip", "logreg.hip", "gbt.hip", "rf.hip", "iforest.hip", "bnb.hip", "smote.hip", "scaler.hip", "poly.hip", "metrics.hip", "xgb.hip", "xgbc.hip", "cat.hip", "catc.hip", "ensemble.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-source flags.  conv_b3c1.hip: the pooling epilogue takes maxima of accumulator registers; in IEEE mode every such operand first gets a
@@ -38,8 +38,10 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # and the trees follow.
 # ensemble.hip: a weighted soft vote is P_0 * w_0, then s + P_j * w_j, with every product and sum rounded on its own, as numpy's np.average rounds
 # them (tests/ensemble_numpy.py); fused into one multiply-add the averaged probabilities differ in their last bit.
+# scaler.hip: a column's squared sum adds t * t to its accumulator as a product and a sum, and the inverse transform is x * scale + mean with two
+# roundings, as scikit-learn rounds them (tests/preprocessing_numpy.py); fused, the variance and the restored values differ in their last bits.
 EXTRA_FLAGS = {"conv_b3c1.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"], "svr.hip": ["-ffp-contract=off"], "iforest.hip": ["-ffp-contract=off"],
-               "bnb.hip": ["-ffp-contract=off"], "smote.hip": ["-ffp-contract=off"], "svm_proba.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
+               "bnb.hip": ["-ffp-contract=off"], "smote.hip": ["-ffp-contract=off"], "scaler.hip": ["-ffp-contract=off"], "svm_proba.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
                "xgb.hip": ["-ffp-contract=off"], "xgbc.hip": ["-ffp-contract=off"], "cat.hip": ["-ffp-contract=off"], "catc.hip": ["-ffp-contract=off"], "ensemble.hip": ["-ffp-contract=off"]}
 
 

@@ -280,6 +280,9 @@ _SIGNATURES = {
     "bbbp_bnb_jll": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_int, c_long, c_void_p]),
     "bbbp_smote_synth": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_long]),
     "bbbp_tomek_links": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "bbbp_scaler_moments": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bbbp_scaler_apply": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p]),
+    "bbbp_poly_expand": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_void_p, c_long, c_void_p]),
     "bbbp_metrics_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "bbbp_metrics_confusion": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "bbbp_metrics_auc_pairs": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),

@@ -997,6 +997,32 @@ int bbbp_smote_synth(void* stream, const void* Xc, int x_dtype, long ldx, int n_
  * written.  An index or a label outside its array is no link. */
 int bbbp_tomek_links(void* stream, const long* nn1, const int* y, const unsigned char* remove, int n_classes, int n, unsigned char* keep);
 
+/* ---- preprocessing: StandardScaler and PolynomialFeatures in float64 (csrc/scaler.hip, csrc/poly.hip) -------------------------------------
+ * The first step of every pipeline of the reference (Models/model_opt_maccs.py:104: StandardScaler -> PCA -> SMOTE -> learners) and the
+ * expansion of the regression feature scripts (Descriptors/multi_input_data_preprocess_maccs_opt_IsolationForest_fixed_1.py:105-134).
+ * bbbp_amd/preprocessing.py composes the estimators from these.  Common to the three entry points: X [n][d] float64 with unit inner
+ * stride and row stride ldx >= d, read in place at any 8-byte aligned base; flag: one int that the call sets to 0 and a kernel ORs to 1
+ * when it meets a NaN or an infinity in X (bbbp_scaler_apply and bbbp_poly_expand accept NULL: no check). */
+/* Column moments of one batch, merged with the moments of the rows seen before: scikit-learn 1.7's _incremental_mean_and_var and
+ * _is_constant_feature, every operation rounded once and in this order.  Per column, rows in order: S = sum x from 0.0; T = S / n;
+ * corr = sum (x - T), sq = sum (x - T) * (x - T); u_new = sq - (corr * corr) / n.  last_n == 0 (last_mean, last_var may be NULL):
+ * mean = (0.0 + S) / n, u = u_new, N = n.  Otherwise last_sum = last_mean * last_n, N = last_n + n, mean = (last_sum + S) / N, r = last_n / n,
+ * u = (last_var * last_n + u_new) + (r / N) * (y * y) with y = last_sum / r - S (last_var NULL: taken as 0, for a caller that keeps no
+ * variance).  var = u / N; scale = 1.0 where var <= (N * eps) * var + ((N * mean) * eps)^2, eps = 2^-52, else sqrt(var).  mean, var and
+ * scale [d] are written in full.  One launch, no host read.  n >= 1, d >= 1. */
+int bbbp_scaler_moments(void* stream, const double* X, long ldx, int n, int d, const double* last_mean, const double* last_var, long last_n,
+                        double* mean, double* var, double* scale, int* flag);
+/* out[i][j] = (X[i][j] - mean[j]) / scale[j] (inverse == 0) or X[i][j] * scale[j] + mean[j] (inverse == 1), two roundings; a NULL mean or
+ * scale skips its step.  out [n][d] with row stride ldo >= d, 8-byte aligned; every element is written and nothing else.  Where both
+ * bases are 16-byte aligned and both row strides even the accesses are 16 bytes wide.  n = 0 or d = 0 is a no-op. */
+int bbbp_scaler_apply(void* stream, const double* X, long ldx, int n, int d, const double* mean, const double* scale, int inverse,
+                      double* out, long ldo, int* flag);
+/* out[i][p] for p < P from table [P][3] (int, dense): the row (f0, f1, f2) with -1 for an absent factor gives 1.0 when f0 == -1, else
+ * X[i][f0], times X[i][f1] when f1 >= 0, times X[i][f2] when f2 >= 0: float64 products in that order, each rounded once.  out [n][P]
+ * with row stride ldo >= P, 8-byte aligned; every element is written and nothing else.  The flag watches the one-factor columns.  A
+ * factor outside [-1, d) reads nothing and yields NaN.  n = 0 is a no-op; d >= 1, P >= 1. */
+int bbbp_poly_expand(void* stream, const double* X, long ldx, int n, int d, const int* table, int P, double* out, long ldo, int* flag);
+
 /* ---- batched classification and regression scores (csrc/metrics.hip) ----------------------------------------------------------------------
  * evaluate_model of the classification scripts (Models/model_maccs.py, model_opt*.py: eight scores per fitted model) and the
  * mean_squared_error / r2_score pair of the regression scripts.  The device computes integers (confusion counts, Mann-Whitney pair counts)
