@@ -170,6 +170,26 @@ class EnsColumn(Structure):
 _FP = c_void_p          # device float*
 _PP = POINTER(c_void_p)  # host array of device pointers
 
+ENCODER_ROWS_FWD_INPUTS = ("ctx", "xin", "wo", "bo", "g1", "be1", "w1", "b1", "w2", "b2", "g2", "be2")
+ENCODER_ROWS_FWD_OUTPUTS = ("z1", "y1", "hff", "z2", "y2", "mean1", "rstd1", "mean2", "rstd2")
+ENCODER_ROWS_BWD_INPUTS = ("z2", "mean2", "rstd2", "g2", "w2", "hff", "w1", "z1", "mean1", "rstd1", "g1", "wo")
+ENCODER_ROWS_BWD_OUTPUTS = ("dz2", "dff", "dhff", "dy1", "dz1", "dsa", "dctx")
+
+
+class EncoderRowsFwdDesc(Structure):
+    """bbbp_encoder_rows_fwd_desc (include/bbbp_hip.h)."""
+    _fields_ = ([("B", c_int), ("F", c_int), ("DFF", c_int), ("dropout_p", c_float), ("seed1", c_uint64), ("seed2", c_uint64), ("seed3", c_uint64)]
+                + [(n, c_void_p) for n in ENCODER_ROWS_FWD_INPUTS]
+                + [("wn", c_void_p), ("bn", c_void_p), ("outn", c_void_p), ("nn", c_int), ("ldn", c_int), ("actn", c_int)]
+                + [(n, c_void_p) for n in ENCODER_ROWS_FWD_OUTPUTS])
+
+
+class EncoderRowsBwdDesc(Structure):
+    """bbbp_encoder_rows_bwd_desc (include/bbbp_hip.h)."""
+    _fields_ = ([("B", c_int), ("F", c_int), ("DFF", c_int), ("dropout_p", c_float), ("seed1", c_uint64), ("seed3", c_uint64)]
+                + [("dqkv_up", c_void_p), ("win_up", c_void_p), ("dz1_up", c_void_p), ("dyout", c_void_p)]
+                + [(n, c_void_p) for n in ENCODER_ROWS_BWD_INPUTS] + [(n, c_void_p) for n in ENCODER_ROWS_BWD_OUTPUTS])
+
 _SIGNATURES = {
     "bbbp_abi_version": (c_int, []),
     "bbbp_last_error": (c_char_p, []),
@@ -197,6 +217,13 @@ _SIGNATURES = {
     "bbbp_attention_bwd": (c_int, [c_void_p, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_float, c_float, c_uint64, c_void_p]),
     "bbbp_attention_b3_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "bbbp_attention_b3_fwd": (c_int, [c_void_p, _FP, _FP, c_int, c_int, c_int, c_float, c_void_p, c_size_t]),
+    "bbbp_outproj_fold_supported": (c_int, [c_int, c_int, c_int]),
+    "bbbp_outproj_fold_fwd": (c_int, [c_void_p, c_int, c_int] + [_PP] * 7),
+    "bbbp_outproj_fold_bwd": (c_int, [c_void_p, c_int, c_int] + [_FP] * 5 + [c_int] + [_FP] * 4),
+    "bbbp_ln_param_grad": (c_int, [c_void_p, c_int] + [_PP] * 6 + [c_int, c_int]),
+    "bbbp_encoder_rows_supported": (c_int, [c_int, c_int, c_int]),
+    "bbbp_encoder_rows_fwd": (c_int, [c_void_p, POINTER(EncoderRowsFwdDesc)]),
+    "bbbp_encoder_rows_bwd": (c_int, [c_void_p, POINTER(EncoderRowsBwdDesc)]),
     "bbbp_set_gemm_split_bf16": (c_int, [c_int]),
     "bbbp_set_gemm_fold_reduce": (c_int, [c_int]),
     "bbbp_gemm_split_bf16_phases": (c_int, [POINTER(c_uint64)]),

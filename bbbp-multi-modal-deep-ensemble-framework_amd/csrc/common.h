@@ -181,7 +181,7 @@ bool bbbp_param_pending_elsewhere(const void* ptr);
 // gemm.hip: LayerNorm absorbed by the consuming Linear (bbbp_layernorm_linear_fwd) -- is that the faster form for this product?
 bool bbbp_layernorm_linear_preferred(int M, int N, int K);
 // fold.hip: out_proj folded into the value projection of a one-head encoder layer (W' = Wo Wv, b' = Wo bv) and the gradients unfolded
-bool bbbp_outproj_fold_supported(int F, int nhead, int layers);
+bool bbbp_fold_supported(int F, int nhead, int layers);
 size_t bbbp_outproj_fold_floats(int F, int which);          // 0 wf [3F][F], 1 bf [3F], 2 wvt [F + 1][F], 3 tdw [F][F], 4 tdb [F]
 int bbbp_outproj_fold(hipStream_t st, int layers, int F, const float* const* win, const float* const* bin, const float* const* wo,
                       const float* const* bo, float* const* wf, float* const* bf, float* const* wvt);

@@ -642,7 +642,9 @@ __global__ __launch_bounds__(NTH) void enc_sliced_fwd_kernel(SlFwdParams P) {
         // ctx^T[d][query] = sum_key V^T[d][key] Pd^T[key][query]: wave w takes the d tiles w, w + NW; a step contracts 4 keys
         for (int dt = wave; dt * 16 < ldz; dt += NW) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            const float* vcol = Y.qkv + 2 * F + 16 * dt + q;                           // V[.][d = 16 dt + (lane & 15)]: inside the row (d < F + 15)
+            // V[.][d = 16 dt + (lane & 15)], clamped to the row: V is the last third, so d >= F of the last key would lie behind qkv
+            // (those lanes feed only the accumulator rows d >= F, which are dropped below)
+            const float* vcol = Y.qkv + 2 * F + min(16 * dt + q, F - 1);
 #pragma unroll 4
             for (int k4 = 0; k4 < Bp; k4 += 4) {
                 const float a = vcol[(long)min(k4 + kq, B - 1) * F3];
@@ -1047,6 +1049,56 @@ int bbbp_ln_param_grad_multi(hipStream_t st, int n, const float* const* dy, cons
         BBBP_CHECK_LAUNCH();
     }
     return BBBP_OK;
+}
+
+// ---- the same three launches as ops of their own (include/bbbp_hip.h): every argument is checked here, before any HIP call -------------
+extern "C" int bbbp_encoder_rows_supported(int F, int nhead, int dff) { return bbbp_enc_rows_supported(F, nhead, dff) ? 1 : 0; }
+
+extern "C" int bbbp_encoder_rows_fwd(void* stream, const bbbp_encoder_rows_fwd_desc* d) {
+    BBBP_CHECK_ARG(d, "encoder_rows_fwd: null descriptor");
+    BBBP_CHECK_ARG(d->B >= 1, "encoder_rows_fwd: B %d", d->B);
+    BBBP_CHECK_ARG(bbbp_enc_rows_supported(d->F, 1, d->DFF), "encoder_rows_fwd: F %d (4 .. %d), DFF %d (>= 16) not supported", d->F, MAXF, d->DFF);
+    BBBP_CHECK_ARG(d->dropout_p >= 0.f && d->dropout_p < 1.f, "encoder_rows_fwd: dropout_p %g not in [0, 1)", (double)d->dropout_p);
+    BBBP_CHECK_ARG(d->ctx && d->xin && d->wo && d->bo && d->g1 && d->be1 && d->w1 && d->b1 && d->w2 && d->b2 && d->g2 && d->be2,
+                   "encoder_rows_fwd: null pointer (input or parameter)");
+    BBBP_CHECK_ARG(d->z1 && d->y1 && d->hff && d->z2 && d->y2 && d->mean1 && d->rstd1 && d->mean2 && d->rstd2, "encoder_rows_fwd: null pointer (output)");
+    if (d->wn) {
+        BBBP_CHECK_ARG(d->bn && d->outn, "encoder_rows_fwd: null pointer (bn or outn of the next projection)");
+        BBBP_CHECK_ARG(d->nn >= 1 && d->ldn >= d->nn, "encoder_rows_fwd: next projection nn %d, ldn %d", d->nn, d->ldn);
+    }
+    bbbp_enc_row_fwd_args a;
+    a.ctx = d->ctx; a.xin = d->xin; a.wo = d->wo; a.bo = d->bo; a.g1 = d->g1; a.be1 = d->be1; a.w1 = d->w1; a.b1 = d->b1; a.w2 = d->w2;
+    a.b2 = d->b2; a.g2 = d->g2; a.be2 = d->be2; a.wn = d->wn; a.bn = d->bn; a.outn = d->outn; a.nn = d->nn; a.ldn = d->ldn; a.actn = d->actn;
+    a.z1 = d->z1; a.y1 = d->y1; a.hff = d->hff; a.z2 = d->z2; a.y2 = d->y2; a.mean1 = d->mean1; a.rstd1 = d->rstd1; a.mean2 = d->mean2;
+    a.rstd2 = d->rstd2; a.B = d->B; a.F = d->F; a.DFF = d->DFF; a.p = d->dropout_p; a.seed1 = d->seed1; a.seed2 = d->seed2; a.seed3 = d->seed3;
+    return bbbp_enc_row_fwd(static_cast<hipStream_t>(stream), &a);
+}
+
+extern "C" int bbbp_encoder_rows_bwd(void* stream, const bbbp_encoder_rows_bwd_desc* d) {
+    BBBP_CHECK_ARG(d, "encoder_rows_bwd: null descriptor");
+    BBBP_CHECK_ARG(d->B >= 1, "encoder_rows_bwd: B %d", d->B);
+    BBBP_CHECK_ARG(bbbp_enc_rows_supported(d->F, 1, d->DFF), "encoder_rows_bwd: F %d (4 .. %d), DFF %d (>= 16) not supported", d->F, MAXF, d->DFF);
+    BBBP_CHECK_ARG(d->dropout_p >= 0.f && d->dropout_p < 1.f, "encoder_rows_bwd: dropout_p %g not in [0, 1)", (double)d->dropout_p);
+    BBBP_CHECK_ARG(d->dyout && d->z2 && d->mean2 && d->rstd2 && d->g2 && d->w2 && d->hff && d->w1 && d->z1 && d->mean1 && d->rstd1 && d->g1 && d->wo,
+                   "encoder_rows_bwd: null pointer (input or parameter)");
+    BBBP_CHECK_ARG(d->dz2 && d->dff && d->dhff && d->dy1 && d->dz1 && d->dsa && d->dctx, "encoder_rows_bwd: null pointer (output)");
+    BBBP_CHECK_ARG((d->dqkv_up && d->win_up && d->dz1_up) || (!d->dqkv_up && !d->win_up && !d->dz1_up),
+                   "encoder_rows_bwd: stage 0 takes dqkv_up, win_up and dz1_up together, or none of them");
+    bbbp_enc_row_bwd_args a;
+    a.dqkv_up = d->dqkv_up; a.win_up = d->win_up; a.dz1_up = d->dz1_up; a.dyout = d->dyout; a.z2 = d->z2; a.mean2 = d->mean2; a.rstd2 = d->rstd2;
+    a.g2 = d->g2; a.w2 = d->w2; a.hff = d->hff; a.w1 = d->w1; a.z1 = d->z1; a.mean1 = d->mean1; a.rstd1 = d->rstd1; a.g1 = d->g1; a.wo = d->wo;
+    a.dz2 = d->dz2; a.dff = d->dff; a.dhff = d->dhff; a.dy1 = d->dy1; a.dz1 = d->dz1; a.dsa = d->dsa; a.dctx = d->dctx; a.B = d->B; a.F = d->F;
+    a.DFF = d->DFF; a.p = d->dropout_p; a.seed1 = d->seed1; a.seed3 = d->seed3;
+    return bbbp_enc_row_bwd(static_cast<hipStream_t>(stream), &a);
+}
+
+extern "C" int bbbp_ln_param_grad(void* stream, int n, const float* const* dy, const float* const* z, const float* const* mean,
+                                  const float* const* rstd, float* const* dgamma, float* const* dbeta, int rows, int cols) {
+    BBBP_CHECK_ARG(n >= 1 && rows >= 1 && cols >= 1, "ln_param_grad: n %d, rows %d, cols %d", n, rows, cols);
+    BBBP_CHECK_ARG(dy && z && mean && rstd && dgamma && dbeta, "ln_param_grad: null pointer list");
+    for (int i = 0; i < n; ++i)
+        BBBP_CHECK_ARG(dy[i] && z[i] && mean[i] && rstd[i] && dgamma[i] && dbeta[i], "ln_param_grad: null pointer (norm %d)", i);
+    return bbbp_ln_param_grad_multi(static_cast<hipStream_t>(stream), n, dy, z, mean, rstd, dgamma, dbeta, rows, cols);
 }
 
 // ---- sliced persistent forward ---------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@
 // Every launch on the encoder's chain costs 11-20 us at B = 512 whatever its size, so two fewer per layer and
 // direction is what this buys; the products here are 167^3 and run as plain float32 FMA loops in a fixed order (bit-reproducible).
 #include "common.h"
+#include "bbbp_hip.h"
 
 namespace {
 
@@ -187,7 +188,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 
 }  // namespace
 
-bool bbbp_outproj_fold_supported(int F, int nhead, int layers) { return nhead == 1 && F >= 1 && F <= FOLD_MAX_F - 1 && layers >= 1 && layers <= 32; }
+bool bbbp_fold_supported(int F, int nhead, int layers) { return nhead == 1 && F >= 1 && F <= FOLD_MAX_F - 1 && layers >= 1 && layers <= 32; }
 
 // per layer: wf [3F][F], bf [3F], wvt [F + 1][F], tdw [F][F], tdb [F]
 size_t bbbp_outproj_fold_floats(int F, int which) {
@@ -197,7 +198,7 @@ size_t bbbp_outproj_fold_floats(int F, int which) {
 
 int bbbp_outproj_fold(hipStream_t st, int layers, int F, const float* const* win, const float* const* bin, const float* const* wo,
                       const float* const* bo, float* const* wf, float* const* bf, float* const* wvt) {
-    BBBP_CHECK_ARG(bbbp_outproj_fold_supported(F, 1, layers), "outproj_fold: F %d, %d layers", F, layers);
+    BBBP_CHECK_ARG(bbbp_fold_supported(F, 1, layers), "outproj_fold: F %d, %d layers", F, layers);
     FoldArgs a;
     for (int l = 0; l < layers; ++l) {
         BBBP_CHECK_ARG(win[l] && bin[l] && wo[l] && wf[l] && bf[l] && wvt[l], "outproj_fold: null pointer (layer %d)", l);
@@ -213,11 +214,28 @@ int bbbp_outproj_fold(hipStream_t st, int layers, int F, const float* const* win
 
 int bbbp_outproj_unfold(hipStream_t st, int F, int B, const float* tdw, const float* tdb, const float* wo, const float* wvt, const float* dz,
                         int lddz, float* g_outw, float* g_outb, float* g_inw_v, float* g_inb_v) {
-    BBBP_CHECK_ARG(bbbp_outproj_fold_supported(F, 1, 1) && B >= 1 && lddz >= F, "outproj_unfold: F %d, B %d, lddz %d", F, B, lddz);
+    BBBP_CHECK_ARG(bbbp_fold_supported(F, 1, 1) && B >= 1 && lddz >= F, "outproj_unfold: F %d, B %d, lddz %d", F, B, lddz);
     BBBP_CHECK_ARG(tdw && tdb && wo && wvt && dz && g_outw && g_outb && g_inw_v && g_inb_v, "outproj_unfold: null pointer");
     UnfoldArgs a{tdw, tdb, wo, wvt, dz, lddz, B, g_outw, g_outb, g_inw_v, g_inb_v, F};
     const int nrt = (F + UR - 1) / UR;
     hipLaunchKernelGGL(outproj_unfold_kernel, dim3(nrt * ((F + 63) / 64) + nrt * ((F + 1 + 63) / 64) + (F + 31) / 32), dim3(NT), g_bbbp_small_lds_pad, st, a);
     BBBP_CHECK_LAUNCH();
     return BBBP_OK;
+}
+
+// ---- the two launches as ops of their own (include/bbbp_hip.h): every argument is checked here, before any HIP call ---------------------
+extern "C" int bbbp_outproj_fold_supported(int F, int nhead, int layers) { return bbbp_fold_supported(F, nhead, layers) ? 1 : 0; }
+
+extern "C" int bbbp_outproj_fold_fwd(void* stream, int layers, int F, const float* const* win, const float* const* bin, const float* const* wo,
+                                     const float* const* bo, float* const* wf, float* const* bf, float* const* wvt) {
+    BBBP_CHECK_ARG(bbbp_fold_supported(F, 1, layers), "outproj_fold_fwd: F %d (1 .. %d), %d layers (1 .. 32) not supported", F, FOLD_MAX_F - 1, layers);
+    BBBP_CHECK_ARG(win && bin && wo && wf && bf && wvt, "outproj_fold_fwd: null pointer list");
+    return bbbp_outproj_fold(static_cast<hipStream_t>(stream), layers, F, win, bin, wo, bo, wf, bf, wvt);
+}
+
+extern "C" int bbbp_outproj_fold_bwd(void* stream, int F, int B, const float* tdw, const float* tdb, const float* wo, const float* wvt,
+                                     const float* dz, int lddz, float* g_outw, float* g_outb, float* g_inw_v, float* g_inb_v) {
+    BBBP_CHECK_ARG(bbbp_fold_supported(F, 1, 1), "outproj_fold_bwd: F %d (1 .. %d) not supported", F, FOLD_MAX_F - 1);
+    BBBP_CHECK_ARG(B >= 1 && lddz >= F, "outproj_fold_bwd: B %d, lddz %d (F %d)", B, lddz, F);
+    return bbbp_outproj_unfold(static_cast<hipStream_t>(stream), F, B, tdw, tdb, wo, wvt, dz, lddz, g_outw, g_outb, g_inw_v, g_inb_v);
 }

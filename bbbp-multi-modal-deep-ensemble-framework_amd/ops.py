@@ -8,6 +8,7 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
+import ctypes
 import threading
 
 import torch
@@ -395,6 +396,181 @@ def attention_b3_fwd(qkv: torch.Tensor, nhead: int, scale: Optional[float] = Non
     _lib.check(L.bbbp_attention_b3_fwd(_stream(), qkv.data_ptr(), ctx.data_ptr(), B, F, nhead, D ** -0.5 if scale is None else scale,
                                        ws.data_ptr(), wsb), "bbbp_attention_b3_fwd")
     return ctx
+
+
+def _dense(t: torch.Tensor, name: str, shape) -> int:
+    """Device address of a contiguous float32 tensor of exactly ``shape``."""
+    if tuple(_chk(t, name).shape) != tuple(shape) or not t.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous tensor of shape {tuple(shape)}, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t.data_ptr()
+
+
+def _outputs(out: Optional[dict], shapes: dict, device) -> dict:
+    """The named outputs of an op: ``out[name]`` where the caller placed one (contiguous, of the op's shape), else a new tensor."""
+    given = out or {}
+    unknown = set(given) - set(shapes)
+    if unknown:
+        raise RuntimeError(f"out: unknown output name(s) {sorted(unknown)}; this op writes {sorted(shapes)}")
+    o = {}
+    for name, shape in shapes.items():
+        if name in given:
+            _dense(given[name], name, shape)
+            o[name] = given[name]
+        else:
+            o[name] = torch.empty(shape, device=device, dtype=torch.float32)
+    return o
+
+
+def _output_lists(out: Optional[dict], shapes: dict, count: int, device) -> dict:
+    """``_outputs`` for ops that write one tensor of every name per layer / norm: lists of ``count`` tensors."""
+    given = out or {}
+    unknown = set(given) - set(shapes)
+    if unknown:
+        raise RuntimeError(f"out: unknown output name(s) {sorted(unknown)}; this op writes {sorted(shapes)}")
+    o = {}
+    for name, shape in shapes.items():
+        if name in given:
+            if len(given[name]) != count:
+                raise RuntimeError(f"out: {name} must list {count} tensors, got {len(given[name])}")
+            for i, t in enumerate(given[name]):
+                _dense(t, f"{name}[{i}]", shape)
+            o[name] = list(given[name])
+        else:
+            o[name] = [torch.empty(shape, device=device, dtype=torch.float32) for _ in range(count)]
+    return o
+
+
+def outproj_fold_fwd(win, bin, wo, bo=None, out: Optional[dict] = None) -> dict:
+    """out_proj folded into the value projection of one-head encoder layers (``bbbp_outproj_fold_fwd``), all layers in one launch.
+    ``win`` [3F, F], ``bin`` [3F], ``wo`` [F, F] and (optional) ``bo`` [F]: lists with one tensor per layer.  Returns lists by name:
+    wf [3F, F] = Wq; Wk; Wo Wv, bf [3F] = bq; bk; Wo bv (+ bo), wvt [F + 1, F] = [Wv | bv]^T.  ``out``: lists of tensors to write instead."""
+    layers = len(win)
+    if layers < 1 or not (len(bin) == len(wo) == layers) or (bo is not None and len(bo) != layers):
+        raise RuntimeError("outproj_fold_fwd: win, bin, wo (and bo) must list one tensor per layer, at least one")
+    F = _chk(wo[0], "wo[0]").shape[-1]
+    L = _lib.lib()
+    if not L.bbbp_outproj_fold_supported(F, 1, layers):
+        raise RuntimeError(f"outproj_fold_fwd: F {F} with {layers} layers is not supported")
+    ptrs = [[_dense(t, f"{n}[{i}]", shape) for i, t in enumerate(ts)]
+            for n, ts, shape in (("win", win, (3 * F, F)), ("bin", bin, (3 * F,)), ("wo", wo, (F, F)))]
+    bo_arr = None if bo is None else _lib.ptr_array([_dense(t, f"bo[{i}]", (F,)) for i, t in enumerate(bo)])
+    o = _output_lists(out, {"wf": (3 * F, F), "bf": (3 * F,), "wvt": (F + 1, F)}, layers, wo[0].device)
+    _lib.check(L.bbbp_outproj_fold_fwd(_stream(), layers, F, *[_lib.ptr_array(p) for p in ptrs], bo_arr,
+                                       *[_lib.ptr_array([t.data_ptr() for t in o[n]]) for n in ("wf", "bf", "wvt")]), "bbbp_outproj_fold_fwd")
+    return o
+
+
+def outproj_fold_bwd(tdw: torch.Tensor, tdb: torch.Tensor, wo: torch.Tensor, wvt: torch.Tensor, dz: torch.Tensor,
+                     out: Optional[dict] = None) -> dict:
+    """The gradients of a folded layer unfolded (``bbbp_outproj_fold_bwd``): from ``tdw`` [F, F] = dW', ``tdb`` [F] = db', ``wo`` [F, F],
+    ``wvt`` [F + 1, F] and ``dz`` [B, F] (rows may be padded) returns g_outw [F, F], g_outb [F], g_inw_v [F, F], g_inb_v [F] by name."""
+    B, F, lddz = _rowmajor_2d(_chk(dz, "dz"), "dz")
+    L = _lib.lib()
+    if B < 1 or not L.bbbp_outproj_fold_supported(F, 1, 1):
+        raise RuntimeError(f"outproj_fold_bwd: dz of shape {tuple(dz.shape)} is not supported")
+    ins = [_dense(tdw, "tdw", (F, F)), _dense(tdb, "tdb", (F,)), _dense(wo, "wo", (F, F)), _dense(wvt, "wvt", (F + 1, F))]
+    o = _outputs(out, {"g_outw": (F, F), "g_outb": (F,), "g_inw_v": (F, F), "g_inb_v": (F,)}, dz.device)
+    _lib.check(L.bbbp_outproj_fold_bwd(_stream(), F, B, *ins, dz.data_ptr(), lddz, *[t.data_ptr() for t in o.values()]), "bbbp_outproj_fold_bwd")
+    return o
+
+
+def ln_param_grad(dy, z, mean, rstd, out: Optional[dict] = None) -> dict:
+    """LayerNorm weight / bias gradients of n norms over [rows, cols] tensors (``bbbp_ln_param_grad``): ``dy``, ``z`` list [rows, cols]
+    tensors, ``mean``, ``rstd`` [rows] tensors, one per norm.  Returns dgamma, dbeta: lists of n [cols] tensors."""
+    n = len(dy)
+    if n < 1 or not (len(z) == len(mean) == len(rstd) == n):
+        raise RuntimeError("ln_param_grad: dy, z, mean and rstd must list one tensor per norm, at least one")
+    if _chk(dy[0], "dy[0]").dim() != 2 or dy[0].shape[0] < 1 or dy[0].shape[1] < 1:
+        raise RuntimeError(f"ln_param_grad: dy[0] must be a non-empty [rows, cols] tensor, got shape {tuple(dy[0].shape)}")
+    rows, cols = dy[0].shape
+    ptrs = [[_dense(t, f"{name}[{i}]", shape) for i, t in enumerate(ts)]
+            for name, ts, shape in (("dy", dy, (rows, cols)), ("z", z, (rows, cols)), ("mean", mean, (rows,)), ("rstd", rstd, (rows,)))]
+    o = _output_lists(out, {"dgamma": (cols,), "dbeta": (cols,)}, n, dy[0].device)
+    _lib.check(_lib.lib().bbbp_ln_param_grad(_stream(), n, *[_lib.ptr_array(p) for p in ptrs],
+                                             *[_lib.ptr_array([t.data_ptr() for t in o[k]]) for k in ("dgamma", "dbeta")], rows, cols),
+               "bbbp_ln_param_grad")
+    return o
+
+
+def _encoder_rows_shapes(F: int, DFF: int) -> dict:
+    return {"wo": (F, F), "bo": (F,), "g1": (F,), "be1": (F,), "w1": (DFF, F), "b1": (DFF,), "w2": (F, DFF), "b2": (F,), "g2": (F,), "be2": (F,)}
+
+
+def encoder_rows_fwd(ctx: torch.Tensor, xin: torch.Tensor, weights: dict, p: float = 0.0, seeds=(0, 0, 0), nxt: Optional[dict] = None,
+                     out: Optional[dict] = None) -> dict:
+    """The row-local stretch of a post-norm encoder layer, forward, as one launch (``bbbp_encoder_rows_fwd``).  ``ctx``, ``xin`` [B, F];
+    ``weights``: wo, bo, g1, be1, w1 [DFF, F], b1, w2 [F, DFF], b2, g2, be2; ``seeds``: the dropout streams of the three sites.  ``nxt``
+    (optional): the next projection, dict(wn [nn, F], bn [nn], act (None or "relu"), outn (optional [B, nn] tensor, which may be a column
+    slice of a wider buffer)).  Returns z1, y1, hff, z2, y2, mean1, rstd1, mean2, rstd2 and outn (None without ``nxt``) by name."""
+    if _chk(ctx, "ctx").dim() != 2 or ctx.shape[0] < 1:
+        raise RuntimeError(f"encoder_rows_fwd: ctx must be a non-empty [B, F] tensor, got shape {tuple(ctx.shape)}")
+    B, F = ctx.shape
+    DFF = _chk(weights["w1"], "w1").shape[0]
+    L = _lib.lib()
+    if not L.bbbp_encoder_rows_supported(F, 1, DFF):
+        raise RuntimeError(f"encoder_rows_fwd: F {F}, DFF {DFF} is not supported")
+    d = _lib.EncoderRowsFwdDesc(B=B, F=F, DFF=DFF, dropout_p=float(p), seed1=int(seeds[0]), seed2=int(seeds[1]), seed3=int(seeds[2]),
+                                ctx=_dense(ctx, "ctx", (B, F)), xin=_dense(xin, "xin", (B, F)))
+    for name, shape in _encoder_rows_shapes(F, DFF).items():
+        setattr(d, name, _dense(weights[name], name, shape))
+    out = dict(out or {})
+    outn = out.pop("outn", None)
+    if nxt is not None:
+        nn = _chk(nxt["wn"], "wn").shape[0]
+        d.wn, d.bn, d.nn, d.actn = _dense(nxt["wn"], "wn", (nn, F)), _dense(nxt["bn"], "bn", (nn,)), nn, ACT[nxt.get("act")]
+        outn = nxt.get("outn", outn)
+        if outn is None:
+            outn = torch.empty((B, nn), device=ctx.device, dtype=torch.float32)
+        rows, cols, ldn = _rowmajor_2d(_chk(outn, "outn"), "outn")
+        if (rows, cols) != (B, nn):
+            raise RuntimeError(f"encoder_rows_fwd: outn must be shaped {(B, nn)}, got {tuple(outn.shape)}")
+        d.outn, d.ldn = outn.data_ptr(), ldn
+    elif outn is not None:
+        raise RuntimeError("encoder_rows_fwd: outn given without a next projection")
+    o = _outputs(out, {"z1": (B, F), "y1": (B, F), "hff": (B, DFF), "z2": (B, F), "y2": (B, F), "mean1": (B,), "rstd1": (B,),
+                       "mean2": (B,), "rstd2": (B,)}, ctx.device)
+    for name, t in o.items():
+        setattr(d, name, t.data_ptr())
+    _lib.check(L.bbbp_encoder_rows_fwd(_stream(), ctypes.byref(d)), "bbbp_encoder_rows_fwd")
+    o["outn"] = outn
+    return o
+
+
+def encoder_rows_bwd(saved: dict, weights: dict, dyout: Optional[torch.Tensor] = None, up: Optional[dict] = None, p: float = 0.0,
+                     seeds=(0, 0), out: Optional[dict] = None) -> dict:
+    """The row-local stretch of a post-norm encoder layer, backward, as one launch (``bbbp_encoder_rows_bwd``).  ``saved``: z1, z2, hff,
+    mean1, rstd1, mean2, rstd2 as ``encoder_rows_fwd`` returns them (taken as given); ``weights``: g1, g2, w1, w2, wo; ``seeds``: the streams
+    of sites 1 and 3.  Either ``dyout`` [B, F], the gradient of the layer's output, or ``up`` = dict(dqkv_up [B, 3F], win_up [3F, F],
+    dz1_up [B, F]) of the layer above, from which stage 0 forms it (into ``out["dyout"]`` or a new tensor).  Returns dyout, dz2, dff, dhff,
+    dy1, dz1, dsa, dctx by name."""
+    if _chk(saved["z1"], "z1").dim() != 2 or saved["z1"].shape[0] < 1:
+        raise RuntimeError(f"encoder_rows_bwd: z1 must be a non-empty [B, F] tensor, got shape {tuple(saved['z1'].shape)}")
+    B, F = saved["z1"].shape
+    DFF = _chk(weights["w1"], "w1").shape[0]
+    L = _lib.lib()
+    if not L.bbbp_encoder_rows_supported(F, 1, DFF):
+        raise RuntimeError(f"encoder_rows_bwd: F {F}, DFF {DFF} is not supported")
+    if (dyout is None) == (up is None):
+        raise RuntimeError("encoder_rows_bwd: pass either dyout or up (dqkv_up, win_up, dz1_up)")
+    d = _lib.EncoderRowsBwdDesc(B=B, F=F, DFF=DFF, dropout_p=float(p), seed1=int(seeds[0]), seed3=int(seeds[1]))
+    for name, shape in (("z1", (B, F)), ("z2", (B, F)), ("hff", (B, DFF)), ("mean1", (B,)), ("rstd1", (B,)), ("mean2", (B,)), ("rstd2", (B,))):
+        setattr(d, name, _dense(saved[name], name, shape))
+    shapes = _encoder_rows_shapes(F, DFF)
+    for name in ("g1", "g2", "w1", "w2", "wo"):
+        setattr(d, name, _dense(weights[name], name, shapes[name]))
+    outs = {"dz2": (B, F), "dff": (B, F), "dhff": (B, DFF), "dy1": (B, F), "dz1": (B, F), "dsa": (B, F), "dctx": (B, F)}
+    if up is not None:
+        d.dqkv_up, d.win_up, d.dz1_up = (_dense(up["dqkv_up"], "dqkv_up", (B, 3 * F)), _dense(up["win_up"], "win_up", (3 * F, F)),
+                                         _dense(up["dz1_up"], "dz1_up", (B, F)))
+        outs = {"dyout": (B, F), **outs}
+        o = _outputs(out, outs, saved["z1"].device)
+    else:
+        o = {"dyout": dyout, **_outputs(out, outs, saved["z1"].device)}
+        _dense(dyout, "dyout", (B, F))
+    for name, t in o.items():
+        setattr(d, name, t.data_ptr())
+    _lib.check(L.bbbp_encoder_rows_bwd(_stream(), ctypes.byref(d)), "bbbp_encoder_rows_bwd")
+    return o
 
 
 def dropout(x: torch.Tensor, p: float, seed: int) -> torch.Tensor:

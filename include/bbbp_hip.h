@@ -1159,6 +1159,55 @@ int bbbp_attention_bwd(void* stream, const float* qkv, const float* ctx, const f
 size_t bbbp_attention_b3_workspace_bytes(int B, int nhead, int head_dim);
 int bbbp_attention_b3_fwd(void* stream, const float* qkv, float* ctx, int B, int F, int nhead, float scale, float* workspace,
                           size_t workspace_bytes);
+/* ---- the encoder layer outside attention, as ops of their own (csrc/fold.hip, csrc/encoder.hip; nn.TransformerEncoderLayer, R:75-78) ----
+ * Thin entry points over the launchers bbbp_mixed_forward / _backward use: same kernels, same bits.  Every one refuses a null required
+ * pointer, an unsupported width and an empty extent with BBBP_ERR_ARG before any HIP call.  The pointer lists are HOST arrays of device
+ * pointers.
+ * bbbp_outproj_fold_fwd, per layer l < layers (one head, F = 1 .. 255, at most 32 layers: bbbp_outproj_fold_supported): from in_proj
+ * win[l] [3F][F] = Wq; Wk; Wv, bin[l] [3F], out_proj wo[l] [F][F] and bo[l] [F] (the list or an entry may be NULL: not added) the folded
+ * wf[l] [3F][F] = Wq; Wk; Wo Wv, bf[l] [3F] = bq; bk; Wo bv (+ bo) and wvt[l] [F + 1][F] = [Wv | bv]^T.
+ * bbbp_outproj_fold_bwd: the gradients unfolded from tdw [F][F] = dW', tdb [F] = db' and dz [B][F] (row stride lddz >= F), the gradient of
+ * out_proj's output: g_outw [F][F] = dW' Wv^T + db' bv^T, g_outb [F] = column sums of dz, g_inw_v [F][F] | g_inb_v [F] = Wo^T [dW' | db'].
+ * bbbp_ln_param_grad: dgamma[i] [cols] = sum_rows dy[i] * (z[i] - mean[i]) * rstd[i] and dbeta[i] [cols] = sum_rows dy[i] of n >= 1
+ * LayerNorms over [rows][cols] tensors (twelve norms per launch). */
+int bbbp_outproj_fold_supported(int F, int nhead, int layers);
+int bbbp_outproj_fold_fwd(void* stream, int layers, int F, const float* const* win, const float* const* bin, const float* const* wo,
+                          const float* const* bo, float* const* wf, float* const* bf, float* const* wvt);
+int bbbp_outproj_fold_bwd(void* stream, int F, int B, const float* tdw, const float* tdb, const float* wo, const float* wvt, const float* dz,
+                          int lddz, float* g_outw, float* g_outb, float* g_inw_v, float* g_inb_v);
+int bbbp_ln_param_grad(void* stream, int n, const float* const* dy, const float* const* z, const float* const* mean,
+                       const float* const* rstd, float* const* dgamma, float* const* dbeta, int rows, int cols);
+/* The row-local stretch of a post-norm encoder layer as one launch per direction (bit 0 of bbbp_set_fused_encoder), for F = 4 .. 192 and
+ * DFF >= 16 (bbbp_encoder_rows_supported).  Forward, per row of ctx / xin [B][F]:
+ *   z1 = dropout1(ctx Wo^T + bo) + xin, y1 = LayerNorm(z1; g1, be1), hff = dropout2(relu(y1 W1^T + b1)) [B][DFF],
+ *   z2 = dropout3(hff W2^T + b2) + y1, y2 = LayerNorm(z2; g2, be2), and when wn is not NULL outn[b][0 .. nn) = act(y2 Wn^T + bn) with row
+ *   stride ldn >= nn (actn: 0 none, 1 ReLU); wn [nn][F].  Dropout site i scales element row * F + col (site 2: row * DFF + col) by the
+ *   keep-scale of Philox stream seed_i, as bbbp_dropout does for a contiguous tensor (bbbp_set_seed_base applies); eps = 1e-5.
+ * Backward, from dyout [B][F], the gradient of y2 -- read, or, when dqkv_up is not NULL (then win_up [3F][F] and dz1_up [B][F] too),
+ * first written as dqkv_up [B][3F] win_up + dz1_up -- and the forward's z1, z2, hff, mean*, rstd*:
+ *   dz2 (gradient of z2), dff = dropout3 of it, dhff = (dff W2) where hff > 0, times 1 / (1 - p), dy1 = dhff W1 + dz2, dz1 (gradient of
+ *   z1), dsa = dropout1 of it, dctx = dsa Wo.  All [B][F] but dhff [B][DFF]. */
+typedef struct bbbp_encoder_rows_fwd_desc {
+    int B, F, DFF;
+    float dropout_p;
+    unsigned long long seed1, seed2, seed3;
+    const float *ctx, *xin;
+    const float *wo, *bo, *g1, *be1, *w1, *b1, *w2, *b2, *g2, *be2;
+    const float *wn, *bn; float* outn; int nn, ldn, actn;          /* the next projection: optional */
+    float *z1, *y1, *hff, *z2, *y2, *mean1, *rstd1, *mean2, *rstd2;
+} bbbp_encoder_rows_fwd_desc;
+typedef struct bbbp_encoder_rows_bwd_desc {
+    int B, F, DFF;
+    float dropout_p;
+    unsigned long long seed1, seed3;
+    const float *dqkv_up, *win_up, *dz1_up;                        /* stage 0: all three or none */
+    float* dyout;
+    const float *z2, *mean2, *rstd2, *g2, *w2, *hff, *w1, *z1, *mean1, *rstd1, *g1, *wo;
+    float *dz2, *dff, *dhff, *dy1, *dz1, *dsa, *dctx;
+} bbbp_encoder_rows_bwd_desc;
+int bbbp_encoder_rows_supported(int F, int nhead, int dff);
+int bbbp_encoder_rows_fwd(void* stream, const bbbp_encoder_rows_fwd_desc* d);
+int bbbp_encoder_rows_bwd(void* stream, const bbbp_encoder_rows_bwd_desc* d);
 /* Products that take the 128 x 128 tile plan (the F = 2048 encoder's GEMMs, the 65536-wide image FC): 1 (default; initial value
  * BBBP_GEMM_SPLIT_BF16) runs them on the bf16 matrix pipe with every float32 operand split into three bf16 pieces (six MFMAs per
  * k-step, f32 accumulate, float32 accuracy; csrc/gemm.hip: gemm_b3_kernel), 0 on the f32 MFMA.  Returns the previous setting. */

@@ -129,3 +129,86 @@ def test_round4_entry_points_validate_their_arguments_before_touching_the_gpu():
     buf = (ctypes.c_ulonglong * 3)()
     assert L.bbbp_mlp_profile_groups(ctypes.cast(buf, ctypes.c_void_p), 5000) == ERR_ARG
     assert L.bbbp_mlp_profile_groups(None, 1) == ERR_ARG
+
+
+def test_encoder_row_fold_and_ln_grad_entry_points_validate_their_arguments_before_touching_the_gpu():
+    """bbbp_outproj_fold_fwd / _bwd, bbbp_ln_param_grad, bbbp_encoder_rows_fwd / _bwd: a null required pointer, an empty extent, an
+    unsupported width and a malformed next projection are BBBP_ERR_ARG with a message before any HIP call; the optional arguments (bo, the
+    next projection, stage 0 of the backward) are the only ones that may be NULL."""
+    L = _lib.lib()
+    ERR_ARG, FAKE = 1, 4096                              # never dereferenced: validation comes first
+
+    def refused(rc, *words):
+        msg = L.bbbp_last_error()
+        return rc == ERR_ARG and all(w in msg for w in words)
+
+    # ---- the predicates ----
+    assert [L.bbbp_outproj_fold_supported(F, 1, 1) for F in (0, 1, 255, 256)] == [0, 1, 1, 0]
+    assert [L.bbbp_outproj_fold_supported(167, 1, n) for n in (0, 1, 32, 33)] == [0, 1, 1, 0] and L.bbbp_outproj_fold_supported(64, 8, 6) == 0
+    assert [L.bbbp_encoder_rows_supported(F, 1, 16) for F in (3, 4, 192, 193)] == [0, 1, 1, 0]
+    assert [L.bbbp_encoder_rows_supported(167, 1, d) for d in (15, 16, 18, 2048)] == [0, 1, 1, 1] and L.bbbp_encoder_rows_supported(64, 0, 64) == 0
+
+    # ---- fold forward: host lists of device pointers ----
+    one, none = _lib.ptr_array([FAKE]), _lib.ptr_array([None])
+    lists = [one] * 3 + [None] + [one] * 3                # win, bin, wo, bo (optional), wf, bf, wvt
+    for F, layers in ((0, 1), (256, 1), (167, 0), (167, 33)):
+        assert refused(L.bbbp_outproj_fold_fwd(None, layers, F, *lists), b"not supported"), (F, layers)
+    for i in (0, 1, 2, 4, 5, 6):
+        assert refused(L.bbbp_outproj_fold_fwd(None, 1, 167, *[None if j == i else a for j, a in enumerate(lists)]), b"null"), i
+        assert refused(L.bbbp_outproj_fold_fwd(None, 1, 167, *[none if j == i else a for j, a in enumerate(lists)]), b"null"), i
+    # ---- fold backward ----
+    ptrs = [FAKE] * 5, [FAKE] * 4                         # tdw, tdb, wo, wvt, dz | g_outw, g_outb, g_inw_v, g_inb_v
+    for F, B, lddz, word in ((0, 4, 8, b"not supported"), (256, 4, 256, b"not supported"), (167, 0, 167, b"B 0"), (167, 4, 166, b"lddz 166")):
+        assert refused(L.bbbp_outproj_fold_bwd(None, F, B, *ptrs[0], lddz, *ptrs[1]), word), (F, B, lddz)
+    for i in range(9):
+        a = [None if j == i else FAKE for j in range(9)]
+        assert refused(L.bbbp_outproj_fold_bwd(None, 167, 4, *a[:5], 167, *a[5:]), b"null"), i
+    # ---- LayerNorm parameter gradients ----
+    two = _lib.ptr_array([FAKE, FAKE])
+    for n, rows, cols in ((0, 4, 4), (-1, 4, 4), (2, 0, 4), (2, 4, 0)):
+        assert refused(L.bbbp_ln_param_grad(None, n, *[two] * 6, rows, cols), b"n %d, rows %d, cols %d" % (n, rows, cols))
+    for i in range(6):
+        assert refused(L.bbbp_ln_param_grad(None, 2, *[None if j == i else two for j in range(6)], 4, 4), b"null"), i
+        assert refused(L.bbbp_ln_param_grad(None, 2, *[_lib.ptr_array([FAKE, None]) if j == i else two for j in range(6)], 4, 4), b"norm 1"), i
+
+    # ---- row forward ----
+    def fwd(**kw):
+        d = _lib.EncoderRowsFwdDesc(B=37, F=167, DFF=2048, dropout_p=0.1, seed1=1, seed2=2, seed3=3)
+        for name in _lib.ENCODER_ROWS_FWD_INPUTS + _lib.ENCODER_ROWS_FWD_OUTPUTS:
+            setattr(d, name, FAKE)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return L.bbbp_encoder_rows_fwd(None, ctypes.byref(d))
+
+    assert refused(L.bbbp_encoder_rows_fwd(None, None), b"null descriptor")
+    for name in _lib.ENCODER_ROWS_FWD_INPUTS + _lib.ENCODER_ROWS_FWD_OUTPUTS:
+        assert refused(fwd(**{name: None}), b"null pointer"), name
+    for B in (0, -3):
+        assert refused(fwd(B=B), b"B %d" % B)
+    for kw in (dict(F=3), dict(F=193), dict(DFF=15), dict(DFF=0)):
+        assert refused(fwd(**kw), b"not supported"), kw
+    for p in (-0.1, 1.0):
+        assert refused(fwd(dropout_p=p), b"dropout_p"), p
+    nxt = dict(wn=FAKE, bn=FAKE, outn=FAKE, nn=128, ldn=256, actn=1)
+    for bad in (dict(nn=0), dict(nn=-1), dict(ldn=127), dict(bn=None), dict(outn=None)):
+        assert refused(fwd(**{**nxt, **bad}), b"next projection"), bad
+
+    # ---- row backward ----
+    def bwd(**kw):
+        d = _lib.EncoderRowsBwdDesc(B=37, F=167, DFF=2048, dropout_p=0.1, seed1=1, seed3=3, dyout=FAKE)
+        for name in _lib.ENCODER_ROWS_BWD_INPUTS + _lib.ENCODER_ROWS_BWD_OUTPUTS:
+            setattr(d, name, FAKE)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return L.bbbp_encoder_rows_bwd(None, ctypes.byref(d))
+
+    assert refused(L.bbbp_encoder_rows_bwd(None, None), b"null descriptor")
+    for name in ("dyout",) + _lib.ENCODER_ROWS_BWD_INPUTS + _lib.ENCODER_ROWS_BWD_OUTPUTS:
+        assert refused(bwd(**{name: None}), b"null pointer"), name
+    assert refused(bwd(B=0), b"B 0")
+    for kw in (dict(F=3), dict(F=193), dict(DFF=15)):
+        assert refused(bwd(**kw), b"not supported"), kw
+    assert refused(bwd(dropout_p=1.0), b"dropout_p")
+    stage0 = ("dqkv_up", "win_up", "dz1_up")
+    for given in ((0,), (1,), (2,), (0, 1), (0, 2), (1, 2)):
+        assert refused(bwd(**{stage0[i]: FAKE for i in given}), b"stage 0"), given
