@@ -13,6 +13,16 @@ right_children, split_indices, split_conditions, default_left; ``learner.learner
 ``CatBoostTrees`` does the same for the cat learner (``CatBoostRegressor(iterations=300, depth=10)``, ...20250108.py:192-195) from
 CatBoost's JSON export (``model.save_model(path, format="json")``): oblivious trees over float features.
 
+Staged prediction (``Models/multi_input_data_regression_opt_transformer_cnn_20250113.py:289-391``: the per-iteration RMSE curves of both
+learners, and CatBoost's ``use_best_model=True``, which keeps the trees up to the best validation iteration).  Both families predict by
+adding leaves in ascending tree order, so the predictions of every prefix of a model come from ONE walk of its trees:
+``staged_predict_device(X, tree_start, tree_end, period)`` returns ``[K, n]`` on the GPU, stage ``k`` covering the trees ``[tree_start,
+stage_ends(...)[k])`` and equal bit for bit to ``truncated(tree_start, e_k).predict_device(X)`` (``bbbp_gbt_staged_predict`` /
+``bbbp_oblivious_staged_predict``: the walk kernels over the tree range and one summing kernel, two launches per row chunk whatever ``K``
+is).  ``rmse_curve`` scores such a matrix in one launch, ``best_iteration`` reads a curve as early stopping would, ``truncated`` cuts a
+model on the host.  The stage convention for ``period > 1`` (the last stage always ends at ``tree_end``) is this module's; whether the
+packages' ``eval_period`` / ``iteration_range`` conventions agree with it beyond period 1 is unpinned like the rest.
+
 PARITY UNPINNED: neither xgboost nor catboost is installed in the build image (and the reference ships no fitted CatBoost model), so outputs cannot be compared with the library's own
 ``predict``; the predict rule is XGBoost's published one (csrc/forest.hip) and the tests check the GPU path against the numpy
 restatement in ``oracle/reference_cpu.py`` only.  The same holds for fitting: ``bbbp_amd.xgb`` has never been compared with the package,
@@ -28,6 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from ._tree_host import is_int as _is_int
 
 _INT = {"i": (">b", 1), "U": (">B", 1), "I": (">h", 2), "l": (">i", 4), "L": (">q", 8)}
 _NUM = dict(_INT, d=(">f", 4), D=(">d", 8))
@@ -138,6 +149,75 @@ def lift_raw_from_pickle(path: str) -> bytes:
     if not best:
         raise ValueError(f"{path}: no byte string in the pickle stream")
     return best
+
+
+def _check_tree_range(who, n_trees, tree_start, tree_end):
+    if not _is_int(tree_start) or not _is_int(tree_end) or not 0 <= tree_start < tree_end <= n_trees:
+        raise ValueError(f"{who}: the tree range [{tree_start!r}, {tree_end!r}) must be a non-empty integer range inside [0, {n_trees}]")
+
+
+def stage_ends(n_trees: int, tree_start: int = 0, tree_end=None, period: int = 1) -> np.ndarray:
+    """int64 [K]: the exclusive tree ends of a staged prediction over the trees ``[tree_start, tree_end)`` of ``n_trees``: stage ``k``
+    covers ``[tree_start, e_k)`` with ``e_k = min(tree_start + (k + 1) period, tree_end)``, so the last stage always ends at ``tree_end``
+    and ``K = ceil((tree_end - tree_start) / period)`` (``bbbp_staged_count``).  ``tree_end`` of ``None`` or 0 means ``n_trees``
+    (CatBoost's ``ntree_end=0``).  An empty or outlying range and a period below 1 raise ``ValueError``."""
+    if not _is_int(n_trees) or n_trees < 1:
+        raise ValueError(f"stage_ends: n_trees must be an int >= 1, got {n_trees!r}")
+    if tree_end is None or (_is_int(tree_end) and tree_end == 0):
+        tree_end = n_trees
+    _check_tree_range("stage_ends", n_trees, tree_start, tree_end)
+    if not _is_int(period) or period < 1:
+        raise ValueError(f"stage_ends: period must be an int >= 1, got {period!r}")
+    count = int(tree_end) - int(tree_start)
+    step = min(int(period), count)                               # a period beyond the range is one stage; keeps the product inside int64
+    return np.minimum(int(tree_start) + (np.arange(-(-count // step), dtype=np.int64) + 1) * step, int(tree_end))
+
+
+def best_iteration(curve, early_stopping_rounds=None) -> Tuple[int, int]:
+    """``(best, stop)`` of a validation curve that is to be minimised (one value per boosting iteration): ``stop`` is the number of
+    iterations a run with the patience ``early_stopping_rounds`` would have trained -- the first ``i + 1`` at which ``i`` lies that many
+    iterations behind the best one so far, else ``len(curve)`` -- and ``best`` the first index of the minimum of ``curve[:stop]``: only a
+    strictly smaller value replaces the best so far, so ties go to the earlier iteration.  Host only."""
+    c = np.asarray(curve, dtype=np.float64)
+    if c.ndim != 1 or c.size < 1 or not np.isfinite(c).all():
+        raise ValueError("best_iteration: the curve must be a non-empty 1-D sequence of finite values")
+    if early_stopping_rounds is not None and (not _is_int(early_stopping_rounds) or early_stopping_rounds < 1):
+        raise ValueError(f"best_iteration: early_stopping_rounds must be None or an int >= 1, got {early_stopping_rounds!r}")
+    best = 0
+    for i in range(c.size):
+        if c[i] < c[best]:
+            best = i
+        if early_stopping_rounds is not None and i - best >= early_stopping_rounds:
+            return best, i + 1
+    return best, int(c.size)
+
+
+def rmse_curve(staged, y) -> list:
+    """One RMSE per row of a staged prediction matrix ``[K, n]`` against ``y`` [n], as Python floats: the matrix goes as it is (on its
+    device) to ``metrics.squared_error_sums`` with ``y`` as float64 -- one launch for all ``K`` rows -- and ``sqrt(sse / n)`` is formed
+    in float64 on the host with the division of ``metrics.regression_from_sums``.  A non-finite value on either side raises that
+    module's ``ValueError``."""
+    from . import metrics
+    mse = metrics.regression_from_sums(*metrics.squared_error_sums(y, staged))["MSE"][:, 0]
+    return [float(v) for v in np.sqrt(mse)]
+
+
+def eval_pairs(eval_set, who, single=False) -> list:
+    """``[(X, y), ...]`` from a non-empty sequence of ``(X, y)`` pairs or, where ``single``, from one bare pair (CatBoost's ``eval_set``)."""
+    if single and isinstance(eval_set, (tuple, list)) and len(eval_set) == 2 and hasattr(eval_set[0], "shape"):
+        eval_set = [eval_set]
+    if not isinstance(eval_set, (tuple, list)) or not eval_set or not all(isinstance(p, (tuple, list)) and len(p) == 2 for p in eval_set):
+        raise ValueError(f"{who}: eval_set must be {'an (X, y) pair or ' if single else ''}a non-empty list of (X, y) pairs")
+    return [tuple(p) for p in eval_set]
+
+
+def _device_rows(X, device, n_features: int) -> torch.Tensor:
+    """``X`` (numpy or tensor) as a contiguous float32 [n, n_features] tensor on ``device``."""
+    Xd = X.to(device, torch.float32).contiguous() if isinstance(X, torch.Tensor) else \
+        torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(device)
+    if Xd.dim() != 2 or Xd.shape[1] != n_features:
+        raise ValueError(f"X must be [n, {n_features}]")
+    return Xd
 
 
 GBT_MAX_DEPTH = 1024          # csrc/forest.hip: the device walk gives up (NaN) after this many levels
@@ -258,10 +338,7 @@ class XGBTrees:
     def predict_device(self, X, rows_per_call: int = 1 << 16) -> torch.Tensor:
         """``X``: [n, n_features] float32 (numpy or CUDA tensor; NaN = missing).  Returns float32 predictions on the GPU."""
         d = self._on_device()
-        Xd = X.to(self.device, torch.float32).contiguous() if isinstance(X, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(self.device)
-        if Xd.dim() != 2 or Xd.shape[1] != self.n_features:
-            raise ValueError(f"X must be [n, {self.n_features}]")
+        Xd = _device_rows(X, self.device, self.n_features)
         n = Xd.shape[0]
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         L = _lib.lib()
@@ -275,6 +352,36 @@ class XGBTrees:
 
     def predict(self, X) -> np.ndarray:
         return self.predict_device(X).cpu().numpy()
+
+    def staged_predict_device(self, X, tree_start: int = 0, tree_end=None, period: int = 1, rows_per_call: int = 1 << 16) -> torch.Tensor:
+        """float32 ``[K, n]`` on the GPU: row ``k`` is, bit for bit, ``truncated(tree_start, e_k).predict_device(X)`` with ``e_k =
+        stage_ends(n_trees, tree_start, tree_end, period)[k]``, from one walk of the trees (``bbbp_gbt_staged_predict``: two launches per
+        row chunk whatever ``K`` is)."""
+        ends = stage_ends(self.n_trees, tree_start, tree_end, period)
+        d = self._on_device()
+        Xd = _device_rows(X, self.device, self.n_features)
+        n, end = Xd.shape[0], int(ends[-1])
+        out = torch.empty((len(ends), n), dtype=torch.float32, device=self.device)
+        L = _lib.lib()
+        scratch = torch.empty((end - tree_start) * min(max(n, 1), rows_per_call), dtype=torch.float32, device=self.device)
+        for lo in range(0, n, rows_per_call):
+            m = min(rows_per_call, n - lo)
+            _lib.check(L.bbbp_gbt_staged_predict(ops._stream(), Xd[lo:lo + m].data_ptr(), m, self.n_features, d["left"].data_ptr(),
+                                                 d["right"].data_ptr(), d["feature"].data_ptr(), d["cond"].data_ptr(), d["default_left"].data_ptr(),
+                                                 d["root"].data_ptr(), self.n_trees, self.base_score, int(tree_start), end, min(int(period), end),
+                                                 scratch.data_ptr(), out[:, lo:].data_ptr(), n), "bbbp_gbt_staged_predict")
+        return out
+
+    def truncated(self, tree_start: int, tree_end: int) -> "XGBTrees":
+        """A new ``XGBTrees`` of the trees ``[tree_start, tree_end)`` alone, node indices re-based; same features, offset and device.
+        Host only."""
+        _check_tree_range("XGBTrees.truncated", self.n_trees, tree_start, tree_end)
+        a = self.arrays
+        root = a["root"].astype(np.int64)
+        lo, hi = int(root[tree_start]), int(root[tree_end])
+        left, right = a["left"][lo:hi].astype(np.int64), a["right"][lo:hi].astype(np.int64)
+        return XGBTrees(np.where(left >= 0, left - lo, -1), np.where(right >= 0, right - lo, -1), a["feature"][lo:hi], a["cond"][lo:hi],
+                        a["default_left"][lo:hi], root[tree_start:tree_end + 1] - lo, self.n_features, self.base_score, device=self.device)
 
 
 def validate_oblivious(split_feature, split_border, nan_true, tree_first_split, tree_first_leaf, leaf_values, n_features: int) -> None:
@@ -353,17 +460,19 @@ class CatBoostTrees:
         doc = json.loads(text_or_doc) if isinstance(text_or_doc, (str, bytes)) else text_or_doc
         return cls(*cls.flatten(doc, n_features), device=device)
 
-    def predict_device(self, X, rows_per_call: int = 1 << 16) -> torch.Tensor:
-        """``X``: [n, n_features] float32 (numpy or CUDA tensor; NaN = missing).  Returns float64 predictions on the GPU."""
+    def _on_device(self):
         if self.device is None or self.device.type != "cuda":
             raise RuntimeError("CatBoostTrees.predict needs a GPU (no CPU fallback; oracle/reference_cpu.py holds the checker)")
         if self._dev is None:
-            self._dev = {k: torch.from_numpy(v).to(self.device) for k, v in self.arrays.items()}
-        d = self._dev
-        Xd = X.to(self.device, torch.float32).contiguous() if isinstance(X, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(self.device)
-        if Xd.dim() != 2 or Xd.shape[1] != self.n_features:
-            raise ValueError(f"X must be [n, {self.n_features}]")
+            # a model of depth-0 trees only (a truncation can be one) has no split: the entry points refuse a null pointer, so an empty array
+            # goes up as one element that no kernel reads
+            self._dev = {k: torch.from_numpy(v if v.size else np.zeros(1, v.dtype)).to(self.device) for k, v in self.arrays.items()}
+        return self._dev
+
+    def predict_device(self, X, rows_per_call: int = 1 << 16) -> torch.Tensor:
+        """``X``: [n, n_features] float32 (numpy or CUDA tensor; NaN = missing).  Returns float64 predictions on the GPU."""
+        d = self._on_device()
+        Xd = _device_rows(X, self.device, self.n_features)
         n = Xd.shape[0]
         out = torch.empty(n, dtype=torch.float64, device=self.device)
         scratch = torch.empty(self.n_trees * min(max(n, 1), rows_per_call), dtype=torch.float64, device=self.device)
@@ -378,3 +487,36 @@ class CatBoostTrees:
 
     def predict(self, X) -> np.ndarray:
         return self.predict_device(X).cpu().numpy()
+
+    def staged_predict_device(self, X, tree_start: int = 0, tree_end=None, period: int = 1, rows_per_call: int = 1 << 16) -> torch.Tensor:
+        """float64 ``[K, n]`` on the GPU: row ``k`` is, bit for bit, ``truncated(tree_start, e_k).predict_device(X)`` with ``e_k =
+        stage_ends(n_trees, tree_start, tree_end, period)[k]``, from one walk of the trees (``bbbp_oblivious_staged_predict``: two
+        launches per row chunk whatever ``K`` is)."""
+        ends = stage_ends(self.n_trees, tree_start, tree_end, period)
+        d = self._on_device()
+        Xd = _device_rows(X, self.device, self.n_features)
+        n, end = Xd.shape[0], int(ends[-1])
+        out = torch.empty((len(ends), n), dtype=torch.float64, device=self.device)
+        scratch = torch.empty((end - tree_start) * min(max(n, 1), rows_per_call), dtype=torch.float64, device=self.device)
+        L = _lib.lib()
+        for lo in range(0, n, rows_per_call):
+            m = min(rows_per_call, n - lo)
+            _lib.check(L.bbbp_oblivious_staged_predict(ops._stream(), Xd[lo:lo + m].data_ptr(), m, self.n_features, d["split_feature"].data_ptr(),
+                                                       d["split_border"].data_ptr(), d["nan_true"].data_ptr(), d["tree_first_split"].data_ptr(),
+                                                       d["tree_first_leaf"].data_ptr(), d["leaf_values"].data_ptr(), self.n_trees, self.scale,
+                                                       self.bias, int(tree_start), end, min(int(period), end), scratch.data_ptr(),
+                                                       out[:, lo:].data_ptr(), n), "bbbp_oblivious_staged_predict")
+        return out
+
+    def truncated(self, tree_start: int, tree_end: int) -> "CatBoostTrees":
+        """A new ``CatBoostTrees`` of the trees ``[tree_start, tree_end)`` alone: their splits and leaf values, offsets re-based; same
+        features, NaN treatment, scale, bias and device.  Host only."""
+        _check_tree_range("CatBoostTrees.truncated", self.n_trees, tree_start, tree_end)
+        a = self.arrays
+        fs, fl = a["tree_first_split"].astype(np.int64), a["tree_first_leaf"]
+        s0, s1 = int(fs[tree_start]), int(fs[tree_end])
+        sizes = 1 << np.diff(fs[tree_start:tree_end + 1])
+        leaves = [a["leaf_values"][int(fl[t]):int(fl[t]) + int(m)] for t, m in zip(range(tree_start, tree_end), sizes)]
+        return CatBoostTrees(a["split_feature"][s0:s1], a["split_border"][s0:s1], a["nan_true"], fs[tree_start:tree_end + 1] - s0,
+                             np.concatenate([[0], np.cumsum(sizes)[:-1]]), np.concatenate(leaves), self.n_features, self.scale, self.bias,
+                             device=self.device)

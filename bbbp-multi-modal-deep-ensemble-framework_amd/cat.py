@@ -60,6 +60,16 @@ roundings; an empty leaf has 0.0.  Then ``s_i += v[leaf(i)]``; ``leaf_weights`` 
 
 *Model.*  A ``boosters.CatBoostTrees`` with ``scale = 1``, ``bias``, no NaN treatment, float32 borders and float64 leaf values.
 
+*Curves, the best iteration and ``use_best_model``, after the fit.*  ``eval_set`` / ``use_best_model`` stay refused inside ``fit``: the fit is
+deterministic and no validation row influences a tree, so the reference's ``fit(X, y, eval_set=(X_test, y_test), use_best_model=True)``
+(``Models/multi_input_data_regression_opt_transformer_cnn_20250113.py:337-369``) is ``fit(X, y)``, ``eval_curves((X_test, y_test),
+learn=(X, y))`` -- which sets ``evals_result_`` (``{"learn": {"RMSE": [...]}, "validation": {"RMSE": [...]}}``) and ``best_iteration_`` -- and
+``shrink(get_best_iteration() + 1)``.  ``staged_predict``, ``eval_metrics`` and ``predict(X, ntree_start, ntree_end)`` carry CatBoost's
+names; all of them come from one walk of the trees (``boosters.CatBoostTrees.staged_predict_device``), a curve from one
+``metrics.squared_error_sums`` launch for all its stages.  No training stops early: a fit of T trees is a prefix of a longer one, so
+cutting the full fit gives the same model.  RMSE only.  Unpinned: CatBoost's stage convention for ``eval_period > 1`` and which eval set
+it takes the best iteration from (``best_on``, the last by default).
+
 
 ``catboost.CatBoostClassifier`` for two classes under Logloss, fitted by ``csrc/catc.hip``
 ==========================================================================================
@@ -352,14 +362,85 @@ class CatBoostRegressor(_estimator.Params):
             raise RuntimeError(f"{_WHO}: not fitted")
         return self.model_
 
-    def predict(self, X):
+    def predict(self, X, ntree_start=0, ntree_end=0):
         """float64 [m]: ``bias_`` behind the sum of the trees' leaf values (``bbbp_oblivious_predict``); numpy for numpy queries, a CUDA
-        tensor for a CUDA tensor."""
-        out = self._fitted().predict_device(X)
+        tensor for a CUDA tensor.  ``ntree_start`` / ``ntree_end`` are CatBoost's: the trees ``[ntree_start, ntree_end)`` only, ``ntree_end
+        = 0`` meaning all of them (one stage of ``bbbp_oblivious_staged_predict``)."""
+        model = self._fitted()
+        if _is_int(ntree_start) and _is_int(ntree_end) and ntree_start == 0 and ntree_end == 0:
+            out = model.predict_device(X)
+        else:
+            out = model.staged_predict_device(X, ntree_start, ntree_end, period=model.n_trees)[0]
         return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
 
     def predict_device(self, X):
         return self._fitted().predict_device(X)
+
+    def staged_predict(self, X, ntree_start=0, ntree_end=0, eval_period=1):
+        """float64 ``[K, m]``: row ``k`` is the prediction of the trees ``[ntree_start, min(ntree_start + (k + 1) eval_period, ntree_end))``,
+        all from one walk of the trees (``boosters.CatBoostTrees.staged_predict_device``); iterating over the result gives one stage per
+        step, which is what CatBoost's generator yields.  numpy for numpy queries, a CUDA tensor for a CUDA tensor."""
+        out = self._fitted().staged_predict_device(X, ntree_start, ntree_end, eval_period)
+        return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
+
+    def eval_metrics(self, data, metrics=("RMSE",), ntree_start=0, ntree_end=0, eval_period=1):
+        """``{"RMSE": [...]}`` for ``data = (X, y)``: the RMSE of every stage of ``staged_predict`` against ``y`` (``boosters.rmse_curve``:
+        the staged matrix is scored on the device in one launch).  Any other metric is refused by name."""
+        names = [metrics] if isinstance(metrics, str) else list(metrics)
+        for name in names:
+            if name != "RMSE":
+                raise ValueError(f"{_WHO}: eval_metrics: the metric {name!r} is not supported (only 'RMSE')")
+        if not names:
+            raise ValueError(f"{_WHO}: eval_metrics: no metric is named")
+        if not isinstance(data, (tuple, list)) or len(data) != 2:
+            raise ValueError(f"{_WHO}: eval_metrics: data must be an (X, y) pair")
+        X, y = data
+        return {"RMSE": boosters.rmse_curve(self._fitted().staged_predict_device(X, ntree_start, ntree_end, eval_period), y)}
+
+    def eval_curves(self, eval_set, learn=None, best_on=-1):
+        """``{"learn": {"RMSE": [...]}, "validation": {"RMSE": [...]}}``, the layout of CatBoost's ``evals_result_``, with one value per
+        iteration: what ``fit(..., eval_set=...)`` records in CatBoost, computed after the fit (the fit is deterministic and no validation
+        row influences a tree).  ``eval_set`` is one ``(X, y)`` pair, keyed ``"validation"``, or a list of pairs, keyed ``"validation_0"``,
+        ``"validation_1"``, ... when there are several; ``learn=(X, y)`` adds the ``"learn"`` curve.  Sets ``evals_result_`` and
+        ``best_iteration_``: ``boosters.best_iteration`` of eval set number ``best_on`` (the last by default; which set CatBoost itself
+        takes is unpinned).  ``shrink(get_best_iteration() + 1)`` then gives the model of ``use_best_model=True``."""
+        model = self._fitted()
+        pairs = boosters.eval_pairs(eval_set, _WHO, single=True)
+        if not _is_int(best_on) or not -len(pairs) <= best_on < len(pairs):
+            raise ValueError(f"{_WHO}: best_on={best_on!r} does not name one of the {len(pairs)} eval sets")
+        result = {}
+        if learn is not None:
+            if not isinstance(learn, (tuple, list)) or len(learn) != 2:
+                raise ValueError(f"{_WHO}: learn must be an (X, y) pair")
+            X, y = learn
+            result["learn"] = {"RMSE": boosters.rmse_curve(model.staged_predict_device(X), y)}
+        for i, (X, y) in enumerate(pairs):
+            result["validation" if len(pairs) == 1 else f"validation_{i}"] = {"RMSE": boosters.rmse_curve(model.staged_predict_device(X), y)}
+        keys = [k for k in result if k != "learn"]
+        self.evals_result_, self.best_iteration_ = result, boosters.best_iteration(result[keys[best_on]]["RMSE"])[0]
+        return result
+
+    def get_best_iteration(self):
+        """``best_iteration_`` of the last ``eval_curves`` call (0-based, as CatBoost's)."""
+        if not hasattr(self, "best_iteration_"):
+            raise RuntimeError(f"{_WHO}: no best iteration: call eval_curves(eval_set) first (fit takes no eval_set)")
+        return self.best_iteration_
+
+    def shrink(self, ntree_end, ntree_start=0):
+        """Keep the trees ``[ntree_start, ntree_end)`` in place (CatBoost's ``shrink``): ``trees_``, ``model_`` and ``tree_count_`` are
+        rebuilt, ``train_approx_`` becomes ``None``, the constructor parameters stay.  With ``ntree_start = 0`` the result is the model a
+        fit of ``ntree_end`` iterations gives: a shorter fit is a prefix of a longer one.  Returns ``self``."""
+        self._fitted()
+        t = self.trees_
+        boosters._check_tree_range(f"{_WHO}.shrink", self.tree_count_, ntree_start, ntree_end)
+        fs = np.asarray(t["tree_first_split"]).astype(np.int64)
+        fl = np.concatenate([t["tree_first_leaf"], [len(t["leaf_values"])]]).astype(np.int64)
+        s0, s1, l0, l1 = int(fs[ntree_start]), int(fs[ntree_end]), int(fl[ntree_start]), int(fl[ntree_end])
+        trees = {k: np.asarray(t[k])[s0:s1].copy() for k in ("split_feature", "split_border", "split_bin") if k in t}
+        trees.update({k: np.asarray(t[k])[l0:l1].copy() for k in ("leaf_values", "leaf_weights") if k in t})
+        trees["tree_first_split"] = (fs[ntree_start:ntree_end + 1] - s0).astype(np.int32)
+        trees["tree_first_leaf"] = fl[ntree_start:ntree_end] - l0
+        return self._adopt({k: trees[k] for k in t}, self.bias_, self.n_features_in_)
 
     # ---- export -----------------------------------------------------------------------------------------------------
     def get_model_json(self):

@@ -175,3 +175,107 @@ extern "C" int bbbp_oblivious_predict(void* stream, const float* X, long n, int 
     BBBP_CHECK_LAUNCH();
     return BBBP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Staged prediction of both boosted families: the predictions of the models made of trees [tree_start, e_k), e_k = min(tree_start +
+// (k + 1) period, tree_end), k = 0 .. K - 1, from ONE walk of the trees -- the per-iteration curves the reference plots
+// (Models/multi_input_data_regression_opt_transformer_cnn_20250113.py:289-391: evals_result() of the xgb and cat learners) and the
+// truncated model CatBoost's use_best_model keeps.  The walk kernels above run over the tree range only (their per-tree arrays are
+// offset by tree_start; the node, split and leaf indices those hold are absolute), then one lane per row adds its leaves in ascending
+// tree order exactly as gbt_sum_kernel / obl_sum_kernel do and stores the running sum at every stage end: stage k holds the bits the
+// predict entry point returns for a model of the trees [tree_start, e_k) alone.  Two launches whatever K is; a stage end is counted,
+// not looked up; every element of out[k][0 .. n) is written once and nothing else of out or of the scratch is read before it is written.
+namespace {
+// One row's running sum over the `count` leaves leaf[t * n + i], emit(k, s) at the end of stage k.  Eight loads are in flight before the
+// first of them is added (the additions are a dependent chain, the loads are not); the order of the additions is the tree order.
+#define BBBP_STAGED_BATCH 8
+template <class T, class Emit>
+__device__ __forceinline__ void staged_sum(const T* __restrict__ leaf, long n, long i, int count, int period, Emit emit) {
+    T s = 0;
+    long k = 0;
+    int in_stage = 0;
+    for (int t0 = 0; t0 < count; t0 += BBBP_STAGED_BATCH) {
+        T v[BBBP_STAGED_BATCH];
+#pragma unroll
+        for (int j = 0; j < BBBP_STAGED_BATCH; ++j) v[j] = t0 + j < count ? leaf[(long)(t0 + j) * n + i] : T(0);
+#pragma unroll
+        for (int j = 0; j < BBBP_STAGED_BATCH; ++j) {
+            if (t0 + j < count) {
+                s += v[j];
+                if (++in_stage == period || t0 + j + 1 == count) {      // (t + 1) % period == 0, or the last tree of the range
+                    emit(k++, s);
+                    in_stage = 0;
+                }
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void gbt_staged_sum_kernel(const float* __restrict__ leaf, long n, int count, int period, float base_score,
+                                                            float* __restrict__ out, long ldo) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    staged_sum(leaf, n, i, count, period, [=](long k, float s) { out[k * ldo + i] = base_score + s; });
+}
+__global__ __launch_bounds__(256) void obl_staged_sum_kernel(const double* __restrict__ leaf, long n, int count, int period, double scale,
+                                                            double bias, double* __restrict__ out, long ldo) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    staged_sum(leaf, n, i, count, period, [=](long k, double s) {
+#pragma clang fp contract(off)                               // two roundings, as obl_sum_kernel
+        const double prod = scale * s;
+        out[k * ldo + i] = prod + bias;
+    });
+}
+// the argument rules the two staged entry points share; 0 when they hold
+int staged_check(const char* who, long n, int n_features, int n_trees, int tree_start, int tree_end, int period, long ldo) {
+    BBBP_CHECK_ARG(n >= 0 && n_features >= 1 && n_trees >= 1 && n_trees <= 65535, "%s: bad sizes (n_trees 1..65535)", who);
+    BBBP_CHECK_ARG(tree_start >= 0 && tree_start < tree_end && tree_end <= n_trees, "%s: tree range [%d, %d) is not inside 0 .. n_trees = %d, or is empty",
+                   who, tree_start, tree_end, n_trees);
+    BBBP_CHECK_ARG(period >= 1, "%s: period %d (at least 1)", who, period);
+    BBBP_CHECK_ARG(ldo >= n, "%s: ldo %ld is below n = %ld", who, ldo, n);
+    BBBP_CHECK_ARG((n + 255) / 256 <= 0x7fffffffL, "%s: too many rows", who);
+    return BBBP_OK;
+}
+}  // namespace
+
+extern "C" int bbbp_staged_count(int tree_start, int tree_end, int period) {
+    if (tree_start < 0 || tree_end <= tree_start || period < 1) return 0;
+    return (int)(((long)(tree_end - tree_start) + period - 1) / period);
+}
+
+extern "C" int bbbp_gbt_staged_predict(void* stream, const float* X, long n, int n_features, const int* left, const int* right, const int* feature,
+                                       const float* split_condition, const uint8_t* default_left, const int* root, int n_trees, float base_score,
+                                       int tree_start, int tree_end, int period, float* leaf_scratch, float* out, long ldo) {
+    if (int rc = staged_check("gbt_staged_predict", n, n_features, n_trees, tree_start, tree_end, period, ldo)) return rc;
+    BBBP_CHECK_ARG(X && left && right && feature && split_condition && default_left && root && leaf_scratch && out,
+                   "gbt_staged_predict: null pointer");
+    if (n == 0) return BBBP_OK;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    const int count = tree_end - tree_start;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(gbt_walk_kernel, dim3(blocks, count), dim3(256), 0, st, X, n, n_features, left, right, feature, split_condition, default_left,
+                       root + tree_start, leaf_scratch);
+    BBBP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gbt_staged_sum_kernel, dim3(blocks), dim3(256), 0, st, leaf_scratch, n, count, period, base_score, out, ldo);
+    BBBP_CHECK_LAUNCH();
+    return BBBP_OK;
+}
+
+extern "C" int bbbp_oblivious_staged_predict(void* stream, const float* X, long n, int n_features, const int* split_feature,
+                                             const float* split_border, const uint8_t* nan_true, const int* tree_first_split,
+                                             const long* tree_first_leaf, const double* leaf_values, int n_trees, double scale, double bias,
+                                             int tree_start, int tree_end, int period, double* leaf_scratch, double* out, long ldo) {
+    if (int rc = staged_check("oblivious_staged_predict", n, n_features, n_trees, tree_start, tree_end, period, ldo)) return rc;
+    BBBP_CHECK_ARG(X && split_feature && split_border && nan_true && tree_first_split && tree_first_leaf && leaf_values && leaf_scratch && out,
+                   "oblivious_staged_predict: null pointer");
+    if (n == 0) return BBBP_OK;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    const int count = tree_end - tree_start;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(obl_walk_kernel, dim3(blocks, count), dim3(256), 0, st, X, n, n_features, split_feature, split_border, nan_true,
+                       tree_first_split + tree_start, tree_first_leaf + tree_start, leaf_values, leaf_scratch);
+    BBBP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(obl_staged_sum_kernel, dim3(blocks), dim3(256), 0, st, leaf_scratch, n, count, period, scale, bias, out, ldo);
+    BBBP_CHECK_LAUNCH();
+    return BBBP_OK;
+}

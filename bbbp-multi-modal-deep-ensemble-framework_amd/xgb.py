@@ -46,6 +46,14 @@ Refused, each by name: objectives other than ``reg:squarederror``, ``subsample``
 ``y``, ``max_depth`` outside 1..1024, more than 8 192 rows, more than 65 536 live features, more than 10 000 trees, more than one GPU.
 There is no CPU path.
 
+*Curves and the best iteration, after the fit.*  ``eval_set`` stays refused inside ``fit``: the fit is deterministic and no validation row
+influences a tree, so ``eval_curves(eval_set, period=1)`` computes XGBoost's ``evals_result()`` (``{"validation_k": {"rmse": [...]}}``)
+afterwards, from one walk of the trees per eval set (``boosters.XGBTrees.staged_predict_device``) and one ``metrics.squared_error_sums``
+launch for all stages; ``staged_predict``, ``predict(X, iteration_range=(begin, end))``, ``boosters.best_iteration`` and ``shrink(tree_end)``
+complete it (the reference's ``Models/multi_input_data_regression_opt_transformer_cnn_20250113.py:291-312``).  No training stops early: a
+fit of T trees is a prefix of a longer one, so cutting the full fit gives the same model.  RMSE takes ``y`` as float64; XGBoost's float32
+labels and its stage convention for periods above 1 are unpinned.
+
 ``XGBClassifier``: the same trees under ``binary:logistic``, fitted by ``csrc/xgbc.hip``.  The reference's newest classification script stacks
 and votes with ``XGBClassifier(use_label_encoder=False, eval_metric="logloss", learning_rate=0.02, n_estimators=500, max_depth=7,
 colsample_bytree=0.8, subsample=0.8, reg_lambda=3, tree_method="hist", device="cuda")`` (``Models/model_opt_20250130.py:445-456``) and searches
@@ -394,13 +402,61 @@ class XGBRegressor:
             raise RuntimeError(f"{_WHO}: not fitted")
         return self.booster_
 
-    def predict(self, X):
-        """float32 [m]: ``base_score_`` plus the trees' leaf values (``bbbp_gbt_predict``); numpy for numpy queries, a CUDA tensor for a CUDA tensor."""
-        out = self._fitted().predict_device(X)
+    def predict(self, X, iteration_range=None):
+        """float32 [m]: ``base_score_`` plus the trees' leaf values (``bbbp_gbt_predict``); numpy for numpy queries, a CUDA tensor for a CUDA tensor.
+        ``iteration_range=(begin, end)`` is XGBoost's: the trees ``[begin, end)`` only, ``end = 0`` meaning all of them (one stage of
+        ``bbbp_gbt_staged_predict``); ``None`` and ``(0, 0)`` are the whole model."""
+        booster = self._fitted()
+        if iteration_range is None or tuple(iteration_range) == (0, 0):
+            out = booster.predict_device(X)
+        else:
+            if len(iteration_range) != 2 or not all(_is_int(v) for v in iteration_range):
+                raise ValueError(f"{_WHO}: iteration_range must be two ints (begin, end), got {iteration_range!r}")
+            begin, end = iteration_range
+            end = booster.n_trees if end == 0 else end
+            boosters._check_tree_range(f"{_WHO}.predict", booster.n_trees, begin, end)
+            out = booster.staged_predict_device(X, begin, end, period=end - begin)[0]
         return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
 
     def predict_device(self, X):
         return self._fitted().predict_device(X)
+
+    def staged_predict(self, X, period=1):
+        """float32 ``[K, m]``: row ``k`` is the prediction of the first ``min((k + 1) period, T)`` trees, all from one walk of the trees
+        (``boosters.XGBTrees.staged_predict_device``); the last row is ``predict(X)`` bit for bit.  numpy for numpy queries, a CUDA tensor
+        for a CUDA tensor."""
+        out = self._fitted().staged_predict_device(X, period=period)
+        return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
+
+    def eval_curves(self, eval_set, period=1):
+        """``{"validation_0": {"rmse": [...]}, "validation_1": ...}``, the layout of XGBoost's ``evals_result()``, for a list of ``(X, y)``
+        pairs: the RMSE of every stage of ``staged_predict(X, period)`` against ``y``.  What ``fit(..., eval_set=...)`` records in XGBoost,
+        computed after the fit: the fit is deterministic and no validation row influences a tree.  Per pair the staged matrix stays on the
+        device and ``metrics.squared_error_sums`` scores its ``K`` rows in one launch (``y`` as float64 -- XGBoost's float32 labels are not
+        reproduced); ``sqrt(sse / n)`` is formed on the host.  A non-finite ``y`` or prediction raises ``ValueError``.  The result is kept
+        in ``evals_result_``."""
+        booster = self._fitted()
+        result = {f"validation_{i}": {"rmse": boosters.rmse_curve(booster.staged_predict_device(X, period=period), y)}
+                  for i, (X, y) in enumerate(boosters.eval_pairs(eval_set, _WHO))}
+        self.evals_result_ = result
+        return result
+
+    def evals_result(self):
+        """What the last ``eval_curves`` call returned."""
+        if not hasattr(self, "evals_result_"):
+            raise RuntimeError(f"{_WHO}: no evaluation results: call eval_curves(eval_set) first (fit takes no eval_set)")
+        return self.evals_result_
+
+    def shrink(self, tree_end):
+        """Keep the trees ``[0, tree_end)`` in place: ``trees_`` and ``booster_`` are rebuilt, ``train_margin_`` becomes ``None``, the
+        constructor parameters stay (``n_estimators`` included, so a clone fits the full count again).  The result is the model a fit of
+        ``tree_end`` trees gives: a shorter fit is a prefix of a longer one.  Returns ``self``."""
+        self._fitted()
+        t = self.trees_
+        boosters._check_tree_range(f"{_WHO}.shrink", len(t["root"]) - 1, 0, tree_end)
+        nodes = int(t["root"][tree_end])
+        trees = {k: (np.asarray(v)[:tree_end + 1] if k == "root" else np.asarray(v)[:nodes]).copy() for k, v in t.items()}
+        return self._adopt(trees, self.base_score_, self.n_features_in_)
 
     # ---- export -----------------------------------------------------------------------------------------------------
     def get_model_json(self):

@@ -409,6 +409,23 @@ int bbbp_oblivious_predict(void* stream, const float* X, long n, int n_features,
                            const uint8_t* nan_true, const int* tree_first_split, const long* tree_first_leaf, const double* leaf_values,
                            int n_trees, double scale, double bias, double* leaf_scratch, double* out);
 
+/* ---- staged prediction of both boosted families (the per-iteration curves of ...20250113.py:289-391 and the truncated model of
+ * use_best_model=True, from one walk of the trees).  Stage k = 0 .. K - 1 covers the trees [tree_start, e_k), e_k = min(tree_start +
+ * (k + 1) * period, tree_end); K = bbbp_staged_count(tree_start, tree_end, period) = ceil((tree_end - tree_start) / period), 0 for a bad
+ * range or period.  out[k * ldo + i] holds, bit for bit, what bbbp_gbt_predict / bbbp_oblivious_predict return for row i and a model of
+ * the trees [tree_start, e_k) alone (float32 / float64, summed in ascending tree order, the offset last).  The model arrays are the whole
+ * model's, as for the predict entry points; 0 <= tree_start < tree_end <= n_trees, period >= 1, ldo >= n (a caller that works in row
+ * chunks passes the full row count as ldo and out + its first row).  leaf_scratch: (tree_end - tree_start) * n floats / doubles.  Two
+ * launches whatever K is; nothing of out or leaf_scratch is read before it is written, out[k][n .. ldo) is not touched. */
+int bbbp_staged_count(int tree_start, int tree_end, int period);
+int bbbp_gbt_staged_predict(void* stream, const float* X, long n, int n_features, const int* left, const int* right, const int* feature,
+                            const float* split_condition, const uint8_t* default_left, const int* root, int n_trees, float base_score,
+                            int tree_start, int tree_end, int period, float* leaf_scratch, float* out, long ldo);
+int bbbp_oblivious_staged_predict(void* stream, const float* X, long n, int n_features, const int* split_feature, const float* split_border,
+                                  const uint8_t* nan_true, const int* tree_first_split, const long* tree_first_leaf,
+                                  const double* leaf_values, int n_trees, double scale, double bias, int tree_start, int tree_end, int period,
+                                  double* leaf_scratch, double* out, long ldo);
+
 /* ---- PCA: float64 column means and centred products on the float64 matrix pipe (csrc/pca.hip) -----------------------
  * sklearn.decomposition.PCA(n).fit_transform in front of the PCA-fusion models (Models/multi_input_data_regression_opt_transformer_cnn_opt.py:30-33,
  * its _morgan / _rdkit / _opt_more siblings) and of the MLPClassifier grid (Models/model_opt_maccs.py:104-109).  bbbp_amd/decomposition.py
